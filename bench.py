@@ -2,6 +2,7 @@
 """Benchmark of pyspeedy_amd on MI355X: ensemble SPEEDY T30L8 (96x48x8), whole model step on the GPU.
 
     python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config cfg4|cfg5] [--members M]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one call of the reference's do_single_step (speedy.f90:20-74) for EVERY ensemble member resident on each
 GPU: daily forcing when due, shortwave every third step, the leapfrog step (spectral->grid transforms, grid-point
@@ -19,6 +20,13 @@ broadcast of the boundary fields from rank 0 (RCCL, device buffers), outside the
 reference's own initial state (example boundary fields, resting atmosphere, first_step), are perturbed as
 examples/Ensemble_forecast.ipynb does (t_grid += N(0, 0.01 K), grid2spectral; seed = global member id) and spun up
 `warmup` steps.
+
+A plain run sets up, warms up, times EXACTLY K steps (one region; `--regions R` asks for R regions of K steps), writes
+`--dump-outputs DIR` when asked and prints its line: value, ms_per_step, config, collective.  `--dump-outputs DIR` writes the
+prognostic state the timed steps left (vor, div, t, tr, ps: float64, complex split into (re, im), members.npy = their global
+ids; a fixed seeded sample of the members when all of them exceed 60 MiB) -- the same inputs and step count in every run, so
+two builds can be compared output for output.  Everything else below -- cpu_baseline, roofline, the range check after the
+timed steps and every secondary object -- is measured only with `--full`.
 
 What the ONE JSON line of rank 0 holds:
   value / ms_per_step   the headline: `spd_model_step(m, K)` regions in the library's default launch plan (two member groups
@@ -73,8 +81,8 @@ What the ONE JSON line of rank 0 holds:
                         `ms_per_step` is the multi-step device loop spd_model_step(m, K); the reference's step() contract -- one
                         call per model step with the range check and the codes back -- is config.step_contract_ms_per_step_*.
 
-Wall-clock budget: `--budget SECONDS` (default 300) bounds the WHOLE run.  The headline, the roofline regions and the host
-baseline always run; every secondary object (the legs above, cfg4_strong, one_process and its cfg4_strong) starts only while
+Wall-clock budget: `--budget SECONDS` (default 300) bounds the WHOLE run.  With `--full` the headline, the roofline regions
+and the host baseline always run; every secondary object (the legs above, cfg4_strong, one_process and its cfg4_strong) starts only while
 the time that is left covers its allowance, and says `{"skipped": "budget"}` otherwise.  The child processes of the one_process
 object get timeouts that sum to at most 150 s, and the ranks that wait for them wait exactly that long: a secondary leg that
 hangs on the first contact with a second GPU cannot out-wait the driver's own timeout and cost the line its headline.
@@ -84,9 +92,9 @@ relays rank 0's JSON line and fails if any rank fails.  Under `python -m torch.d
 process is one rank.  PYSPEEDY_AMD_BENCH_BACKEND=gloo rehearses the N-rank control flow when the ranks share one GPU.
 
 Timing: W warm-up steps, then regions of EXACTLY K steps, each bracketed by barrier + synchronize on both sides and reduced
-with MAX over ranks.  Regions are repeated until `--min-seconds` (default 5) of timed GPU work have accumulated (the run
-stays inside the SST-anomaly months it allocates) and `ms_per_step` is the MEDIAN region (minimum and count beside it): a
-20-step run is then several hundred 5-ms samples, and the GPU is busy for seconds, not milliseconds.
+with MAX over ranks.  The headline times one region (or `--regions R`) and `ms_per_step` is the MEDIAN region (minimum and
+count beside it).  With `--full` the serial-plan regions of the roofline are repeated until min(`--min-seconds`, 1 s) of timed
+GPU work have accumulated (the run stays inside the SST-anomaly months it allocates).
 """
 import argparse
 import json
@@ -135,8 +143,16 @@ def parse(argv=None):
     ap.add_argument("--config", choices=("cfg4", "cfg5"), default="cfg4")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--members", type=int, default=None, help="members per GPU (weak) or in total (strong)")
-    ap.add_argument("--regions", type=int, default=0, help="timed regions of `steps` steps (0 = automatic)")
-    ap.add_argument("--min-seconds", type=float, default=5.0, help="timed regions are repeated until this much GPU time")
+    ap.add_argument("--regions", type=int, default=0,
+                    help="timed regions of `steps` steps (0 = automatic: the headline times exactly one region)")
+    ap.add_argument("--min-seconds", type=float, default=5.0,
+                    help="--full: the serial-plan regions of the roofline are repeated until this much GPU time (at most 1 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: host baseline, roofline and kernel table, range check, the secondary "
+                         "legs (cfg2 / cfg3 / cfg5, drop-in, facade, cfg4_strong, one_process).  Off: set up, warm up, time the "
+                         "steps, write --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the ensemble's prognostic state (vor, div, t, tr, ps) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true",
                     help="headline and roofline only: no drop_in_step / every_step_stores / cfg4_strong objects (profiles of "
@@ -205,7 +221,7 @@ def launch_ranks(args, argv):
     port = str(free_port())
     procs = []
     baseline_file = None
-    if not args.no_cpu_baseline:  # the host baseline of an N-rank line: measured here, before any rank exists
+    if args.full and not args.no_cpu_baseline:  # the host baseline of an N-rank line: measured here, before any rank exists
         import tempfile
         fd, baseline_file = tempfile.mkstemp(prefix="pyspeedy_bench_cpu_", suffix=".json")
         with os.fdopen(fd, "w") as fh:
@@ -499,6 +515,31 @@ def timed_regions(model, args, barrier, dist, coll_device, steps_left, min_secon
         regions = max(1, min(regions, steps_left // max(args.steps, 1)))
         r += 1
     return out
+
+
+DUMP_VARIABLES = ("vor", "div", "t", "tr", "ps")  # the prognostic state a caller of spd_model_step(m, K) continues from
+DUMP_BYTES = 60 * 2 ** 20                         # at most this much in all (the members of every rank together)
+
+
+def dump_outputs(model, out_dir, first_id, rank, world):
+    """--dump-outputs: the prognostic state after the timed steps as DIR/<name>.npy, float64 [members, *reference shape] with
+    complex variables split into a trailing (re, im) axis, and DIR/members.npy, the global ids of the members written.  When
+    all members do not fit in DUMP_BYTES, a fixed sample of them (seeded, the same in every run) is written.  With N ranks each
+    rank writes its own members as <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    per_member = sum(np.dtype(model.shape(n)[0]).itemsize * int(np.prod(model.shape(n)[1])) for n in DUMP_VARIABLES)
+    keep = max(1, min(model.nmembers, DUMP_BYTES // world // per_member))
+    members = np.arange(model.nmembers)
+    if keep < model.nmembers:
+        members = np.sort(np.random.default_rng(0).choice(model.nmembers, keep, replace=False))
+    suffix = ".rank%d" % rank if world > 1 else ""
+    for name in DUMP_VARIABLES:
+        a = np.stack([model.get(name, int(m)) for m in members])
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    np.save(os.path.join(out_dir, "members" + suffix + ".npy"), (first_id + members).astype(np.float64))
 
 
 def median(values):
@@ -1209,7 +1250,7 @@ def one_process_timeouts(budget):
 
 def run_one_process(args):
     """`--one-process`: this process alone drives --gpus devices; the line's value is the begin / end loop over all containers."""
-    baseline = None if args.no_cpu_baseline else cpu_baseline(args.cpu_seconds)  # (before the GPU is touched)
+    baseline = cpu_baseline(args.cpu_seconds) if args.full and not args.no_cpu_baseline else None  # (before the GPU is touched)
     import torch
     import pyspeedy_amd
     pyspeedy_amd.lib()
@@ -1340,7 +1381,7 @@ def run_rank(args):
         if rank_env == 0:
             with open(os.environ["PYSPEEDY_AMD_BENCH_CPU_BASELINE"]) as fh:
                 baseline = json.load(fh)
-    elif not args.no_cpu_baseline:
+    elif args.full and not args.no_cpu_baseline:
         # spawns processes: must come before the first GPU call of this process.  Under torch.distributed.run rank 0 measures
         # it while the other ranks -- torch imported, GPU untouched -- wait for it in the rendezvous of the process group.
         if world_env > 1:
@@ -1399,9 +1440,11 @@ def run_rank(args):
     plan = plan_name(cfg, M)
     model.run(args.warmup)
     budget = MAX_STEPS - args.warmup - 36  # model steps this ensemble may still take (36: the bracketed one-day pass)
-    # ---- headline: the library's default plan
-    region_s = timed_regions(model, args, barrier, dist, coll_device, budget * 3 // 4, args.min_seconds)
+    # ---- headline: the library's default plan, exactly --steps steps (one region unless --regions asks for more)
+    region_s = timed_regions(model, args, barrier, dist, coll_device, budget * 3 // 4, 0.0)
     budget -= len(region_s) * args.steps
+    if args.dump_outputs:
+        dump_outputs(model, args.dump_outputs, first_id, rank, n_gpus)
     plan = plan_name(model.config(), M)
     # (every rank's group streams, not only rank 0's: one all_gather_object; a rank whose streams share a hardware queue is the
     # slowest rank, and the line's time is the slowest rank's)
@@ -1409,102 +1452,102 @@ def run_rank(args):
     if dist is not None:
         apart_by_rank = [None] * n_gpus
         dist.all_gather_object(apart_by_rank, bool(model.config()["group_streams_apart"]))
-    # ---- roofline: the dominant transform kernel by HIP events on its launch stream, serial plan (profiling implies it)
-    model.profile(1)
-    saved_regions, args.regions = args.regions, (min(args.regions, 10) if args.regions else 0)
-    serial_s = timed_regions(model, args, barrier, dist, coll_device, budget, min(args.min_seconds, 1.0), 200)
-    args.regions = saved_regions
-    kern_ms, launches, nfields = model.profile_read()
-    codes = model.check(2)
-    if (codes != 0).any():
-        raise SystemExit("bench.py: %d members left the accepted range (diagnostics.f90)" % int((codes != 0).sum()))
-    model.profile(0)
-    kernels = kernel_table(model, M, nfields // M, sppt) if rank == 0 or dist is None else None
-    model.close()
-    stream_ceiling = None
-    if rank == 0:  # (own probe kernels on the idle GPU of rank 0; the other ranks' GPUs have nothing timed in flight either)
-        stream_ceiling = (stream_ceiling_object(sp, kernels) if wall.allows("stream_ceiling", LEG_ALLOWANCE["stream_ceiling"])
-                          else {"skipped": "budget"})
-    sp.close()
+    stream_ceiling = kern_ms = launches = nfields = kernels = serial_s = None
     legs = {}
-    if not args.no_legs:
-        def leg(name, fn):  # a secondary object of the one-GPU line: only while the budget covers its allowance
-            legs[name] = fn() if wall.allows(name, LEG_ALLOWANCE[name]) else {"skipped": "budget"}
+    if args.full:
+        # ---- roofline: the dominant transform kernel by HIP events on its launch stream, serial plan (profiling implies it)
+        model.profile(1)
+        saved_regions, args.regions = args.regions, (min(args.regions, 10) if args.regions else 0)
+        serial_s = timed_regions(model, args, barrier, dist, coll_device, budget, min(args.min_seconds, 1.0), 200)
+        args.regions = saved_regions
+        kern_ms, launches, nfields = model.profile_read()
+        codes = model.check(2)
+        if (codes != 0).any():
+            raise SystemExit("bench.py: %d members left the accepted range (diagnostics.f90)" % int((codes != 0).sum()))
+        model.profile(0)
+        kernels = kernel_table(model, M, nfields // M, sppt) if rank == 0 or dist is None else None
+        model.close()
+        stream_ceiling = None
+        if rank == 0:  # (own probe kernels on the idle GPU of rank 0; the other ranks' GPUs have nothing timed in flight either)
+            stream_ceiling = (stream_ceiling_object(sp, kernels) if wall.allows("stream_ceiling", LEG_ALLOWANCE["stream_ceiling"])
+                              else {"skipped": "budget"})
+        sp.close()
+        if not args.no_legs:
+            def leg(name, fn):  # a secondary object of the one-GPU line: only while the budget covers its allowance
+                legs[name] = fn() if wall.allows(name, LEG_ALLOWANCE[name]) else {"skipped": "budget"}
 
-        if n_gpus == 1 and args.config == "cfg4":
-            leg("every_step_stores", lambda: fidelity_leg(args, M, first_id, device, dist, rank, coll_device, barrier))
-            leg("beyond_infinity_cache", lambda: beyond_infinity_cache_leg(args, device, dist, rank, coll_device, barrier))
+            if n_gpus == 1 and args.config == "cfg4":
+                leg("every_step_stores", lambda: fidelity_leg(args, M, first_id, device, dist, rank, coll_device, barrier))
+                leg("beyond_infinity_cache", lambda: beyond_infinity_cache_leg(args, device, dist, rank, coll_device, barrier))
 
-            def drop_in():
-                out = drop_in_leg(M, 360)
-                out.update(small_drop_in_legs(360))
-                return out
-            leg("drop_in_step", drop_in)
-            leg("facade_run", facade_leg)
-            # the other BASELINE configs on the same clock (SURVEY 8d "Configs as concrete inputs")
-            leg("cfg2_transforms", lambda: transforms_leg(args, device))
-            leg("cfg3", lambda: config_leg(args, "cfg4", 1, "BASELINE cfg 3: one member, fp64, the full step on the GPU", device, dist, rank,
-                                           coll_device, barrier))
-            leg("cfg4_shard8", lambda: config_leg(args, "cfg4", 8, "BASELINE cfg 4 as worded: one GPU's share of 64 members on 8 GPUs = 8 "
-                                                  "members, fp64", device, dist, rank, coll_device, barrier))
-            leg("cfg5", lambda: config_leg(args, "cfg5", 32, "BASELINE cfg 5: one GPU's share of 256 members on 8 GPUs = 32 members, SPPT "
-                                           "on, fp32 arithmetic in the column physics (fp64 state)", device, dist, rank, coll_device, barrier))
-        if n_gpus > 1 and args.scaling == "weak" and args.config == "cfg4" and args.members is None and not agreed(
-                dist, wall.allows("cfg4_strong", LEG_ALLOWANCE["cfg4_strong"])):
-            legs["cfg4_strong"] = {"skipped": "budget"}
-        elif n_gpus > 1 and args.scaling == "weak" and args.config == "cfg4" and args.members is None:
-            # BASELINE cfg 4 to the letter next to the weak headline: 64 members in total, block-sharded over the ranks
-            strong = argparse.Namespace(**dict(vars(args), scaling="strong", members=None))
-            Ms, first_s, total_s = workload(strong, world, rank)
-            sp2, m2 = build_ensemble(strong, Ms, first_s, device, dist, rank, coll_device)
-            m2.run(args.warmup)
-            secs = timed_regions(m2, strong, barrier, dist, coll_device, MAX_STEPS - args.warmup - 36, 1.0, 500)
-            ok = (m2.check(2) == 0).all()
-            scfg = m2.config()
-            m2.close()
-            sp2.close()
-            if not ok:
-                raise SystemExit("bench.py: members left the accepted range in the cfg4_strong leg")
-            ms_s = median(secs) / args.steps * 1e3
-            legs["cfg4_strong"] = {
-                "members_total": total_s, "members_per_gpu": Ms, "ms_per_step": ms_s, "regions": len(secs), "scaling": "strong",
-                "value": E.simulated_years_per_day(total_s, ms_s * 1e-3, STEPS_PER_YEAR), "unit": "simulated-years/day",
-                "plan": plan_name(scfg, Ms),
-                "note": "BASELINE cfg 4 as worded: 64 members sharded %d per GPU over %d GPUs, same timing rules" % (Ms, n_gpus)}
-        if n_gpus > 1 and args.config == "cfg4":
-            # The reference's own shape beside the process-per-GPU headline: ONE process (rank 0) drives every GPU through
-            # spd_parallel_step.  The other ranks have released their models and wait on the host (a file, not a collective: a
-            # pending RCCL barrier would keep a kernel spinning on the very GPUs that are being measured).
-            # The measurement runs in a CHILD process of rank 0 (`bench.py --one-process`): it is ONE process by construction,
-            # and whatever its first contact with a second GPU does, the headline of this line survives it.
-            # Its children get timeouts cut from what is left of the budget (at most 100 + 50 s), rank 0 decides and tells the
-            # others, and they wait exactly that long: whatever the first contact with a second GPU does inside this SECONDARY
-            # object, every rank is back in time to print the line.
-            t_child, t_strong = agreed(dist, one_process_timeouts(wall))
-            if not (args.scaling == "weak" and args.members is None):
-                t_strong = 0.0
-            barrier()
-            if t_child <= 0:
-                legs["one_process"] = {"skipped": "budget"}
-                if rank == 0:
-                    wall.skipped.append({"leg": "one_process", "allowance_s": ONE_PROCESS_TIMEOUT, "left_s": round(wall.left(), 1)})
-            elif rank == 0:
-                op = one_process_child(n_gpus, ["--scaling", "strong", "--members", str(total_members)], timeout=t_child)
-                if "error" not in op and t_strong > 0:
-                    op["cfg4_strong"] = one_process_child(n_gpus, ["--scaling", "strong", "--members", "64"], timeout=t_strong)
-                op["timeouts_s"] = [round(t_child, 1), round(t_strong, 1)]
-                legs["one_process"] = op
-                file_flag("one_process_done", set_it=True)
-            else:
-                file_flag("one_process_done", wait_seconds=t_child + t_strong + 25.0)  # (+ the grace of two killed children)
-
+                def drop_in():
+                    out = drop_in_leg(M, 360)
+                    out.update(small_drop_in_legs(360))
+                    return out
+                leg("drop_in_step", drop_in)
+                leg("facade_run", facade_leg)
+                # the other BASELINE configs on the same clock (SURVEY 8d "Configs as concrete inputs")
+                leg("cfg2_transforms", lambda: transforms_leg(args, device))
+                leg("cfg3", lambda: config_leg(args, "cfg4", 1, "BASELINE cfg 3: one member, fp64, the full step on the GPU", device, dist, rank,
+                                               coll_device, barrier))
+                leg("cfg4_shard8", lambda: config_leg(args, "cfg4", 8, "BASELINE cfg 4 as worded: one GPU's share of 64 members on 8 GPUs = 8 "
+                                                      "members, fp64", device, dist, rank, coll_device, barrier))
+                leg("cfg5", lambda: config_leg(args, "cfg5", 32, "BASELINE cfg 5: one GPU's share of 256 members on 8 GPUs = 32 members, SPPT "
+                                               "on, fp32 arithmetic in the column physics (fp64 state)", device, dist, rank, coll_device, barrier))
+            if n_gpus > 1 and args.scaling == "weak" and args.config == "cfg4" and args.members is None and not agreed(
+                    dist, wall.allows("cfg4_strong", LEG_ALLOWANCE["cfg4_strong"])):
+                legs["cfg4_strong"] = {"skipped": "budget"}
+            elif n_gpus > 1 and args.scaling == "weak" and args.config == "cfg4" and args.members is None:
+                # BASELINE cfg 4 to the letter next to the weak headline: 64 members in total, block-sharded over the ranks
+                strong = argparse.Namespace(**dict(vars(args), scaling="strong", members=None))
+                Ms, first_s, total_s = workload(strong, world, rank)
+                sp2, m2 = build_ensemble(strong, Ms, first_s, device, dist, rank, coll_device)
+                m2.run(args.warmup)
+                secs = timed_regions(m2, strong, barrier, dist, coll_device, MAX_STEPS - args.warmup - 36, 1.0, 500)
+                ok = (m2.check(2) == 0).all()
+                scfg = m2.config()
+                m2.close()
+                sp2.close()
+                if not ok:
+                    raise SystemExit("bench.py: members left the accepted range in the cfg4_strong leg")
+                ms_s = median(secs) / args.steps * 1e3
+                legs["cfg4_strong"] = {
+                    "members_total": total_s, "members_per_gpu": Ms, "ms_per_step": ms_s, "regions": len(secs), "scaling": "strong",
+                    "value": E.simulated_years_per_day(total_s, ms_s * 1e-3, STEPS_PER_YEAR), "unit": "simulated-years/day",
+                    "plan": plan_name(scfg, Ms),
+                    "note": "BASELINE cfg 4 as worded: 64 members sharded %d per GPU over %d GPUs, same timing rules" % (Ms, n_gpus)}
+            if n_gpus > 1 and args.config == "cfg4":
+                # The reference's own shape beside the process-per-GPU headline: ONE process (rank 0) drives every GPU through
+                # spd_parallel_step.  The other ranks have released their models and wait on the host (a file, not a collective: a
+                # pending RCCL barrier would keep a kernel spinning on the very GPUs that are being measured).
+                # The measurement runs in a CHILD process of rank 0 (`bench.py --one-process`): it is ONE process by construction,
+                # and whatever its first contact with a second GPU does, the headline of this line survives it.
+                # Its children get timeouts cut from what is left of the budget (at most 100 + 50 s), rank 0 decides and tells the
+                # others, and they wait exactly that long: whatever the first contact with a second GPU does inside this SECONDARY
+                # object, every rank is back in time to print the line.
+                t_child, t_strong = agreed(dist, one_process_timeouts(wall))
+                if not (args.scaling == "weak" and args.members is None):
+                    t_strong = 0.0
+                barrier()
+                if t_child <= 0:
+                    legs["one_process"] = {"skipped": "budget"}
+                    if rank == 0:
+                        wall.skipped.append({"leg": "one_process", "allowance_s": ONE_PROCESS_TIMEOUT, "left_s": round(wall.left(), 1)})
+                elif rank == 0:
+                    op = one_process_child(n_gpus, ["--scaling", "strong", "--members", str(total_members)], timeout=t_child)
+                    if "error" not in op and t_strong > 0:
+                        op["cfg4_strong"] = one_process_child(n_gpus, ["--scaling", "strong", "--members", "64"], timeout=t_strong)
+                    op["timeouts_s"] = [round(t_child, 1), round(t_strong, 1)]
+                    legs["one_process"] = op
+                    file_flag("one_process_done", set_it=True)
+                else:
+                    file_flag("one_process_done", wait_seconds=t_child + t_strong + 25.0)  # (+ the grace of two killed children)
+    else:
+        model.close()
+        sp.close()
     if rank == 0:
         ms_step, ms_min = median(region_s) / args.steps * 1e3, min(region_s) / args.steps * 1e3
         value = E.simulated_years_per_day(total_members, ms_step * 1e-3, STEPS_PER_YEAR)
-        # (cfg 5 stores 27 of a member's fields as fp32: those count S + G / 2)
-        s2g_bytes = (S_BYTES + G_BYTES) * nfields - (G_BYTES // 2) * S2G_FLOAT_FIELDS * M * (1 if cfg["physics_storage32"] else 0)
-        achieved = s2g_bytes / (kern_ms * 1e-3) / 1e9
-        traffic, traffic_src, traffic_stale = load_traffic(nfields)
         beyond = legs.pop("beyond_infinity_cache", None)
         physics = "fp64 column physics" if args.config == "cfg4" else "SPPT on, fp32 arithmetic in the column physics (fp64 state)"
         all_cores = (baseline or {}).get("all_cores")
@@ -1523,9 +1566,10 @@ def run_rank(args):
             "ms_per_step_min": ms_min, "regions": len(region_s), "timed_seconds": sum(region_s),
             "config": {
                 "workload": "BASELINE %s ensemble (%s scaling): %d members per GPU, %d in total, T30L8 96x48x8, %s; full "
-                            "do_single_step per member (%d spec2grid + grid-point dynamics + fused column physics + 73 "
+                            "do_single_step per member (%s spec2grid + grid-point dynamics + fused column physics + 73 "
                             "grid2spec + spectral tendencies/semi-implicit/diffusion/RAW filter + coupler + daily "
-                            "forcing), all on the GPU" % (args.config, args.scaling, M, total_members, physics, nfields // M),
+                            "forcing), all on the GPU" % (args.config, args.scaling, M, total_members, physics,
+                                                          ("%d" % (nfields // M)) if nfields else "the"),
                 "members_per_gpu": M, "members_total": total_members, "plan": plan,
                 "group_streams_side_by_side_by_rank": apart_by_rank,
                 "ms_per_member_step": ms_step * n_gpus / total_members, "simulated_days_per_region": args.steps / 36.0,
@@ -1533,7 +1577,13 @@ def run_rank(args):
                 "backend": backend if dist is not None else "none (single process)",
             },
             "collective": collective,
-            "roofline": {
+        }
+        if args.full:
+            # (cfg 5 stores 27 of a member's fields as fp32: those count S + G / 2)
+            s2g_bytes = (S_BYTES + G_BYTES) * nfields - (G_BYTES // 2) * S2G_FLOAT_FIELDS * M * (1 if cfg["physics_storage32"] else 0)
+            achieved = s2g_bytes / (kern_ms * 1e-3) / 1e9
+            traffic, traffic_src, traffic_stale = load_traffic(nfields)
+            line["roofline"] = {
                 "kernel": "spec2grid_table_kernel (inverse Legendre + inverse FFT-96, with vort2vel / gradient applied while "
                           "staging the wind and pressure-gradient fields of each member), %d fields/launch" % nfields,
                 "bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
@@ -1554,8 +1604,7 @@ def run_rank(args):
                 "kernels_note": "one simulated day (36 steps, serial plan) with events attached to every kernel's dispatch (the "
                                 "kernels' own begin / end time stamps, as in rocprofv3's kernel trace); the rows sum to less than "
                                 "serial_plan_ms_per_step by the gaps between dependent launches",
-            },
-        }
+            }
         if "ms_per_step" in (legs.get("cfg4_shard8") or {}):
             legs["projected_8gpu_cfg4"] = projection_8gpu(legs["cfg4_shard8"], value, total_members, all_cores)
         line["config"].update(step_contract_keys(legs, ms_step, total_members))
@@ -1585,6 +1634,8 @@ def main():
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
     if args.one_process:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the ensemble of the rank path; --one-process has no such ensemble")
         return run_one_process(args)  # one process whatever --gpus says: no ranks are started
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, argv)  # this process never touches the GPU

@@ -30,6 +30,17 @@ def test_workload_partition():
         bench.workload(a, 3, 2)
 
 
+def test_a_plain_run_is_the_headline_alone():
+    """Without --full the line is set-up, warm-up, exactly --steps timed steps and the line: no host baseline, no legs."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.regions == 0
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    assert bench.DUMP_BYTES <= 64 * 2 ** 20
+
+
 def test_launcher_reports_a_failing_rank():
     """Without a GPU every rank stops with an error: the launcher must return non-zero and print no result line."""
     if os.path.exists("/dev/kfd"):  # (not torch.cuda.is_available(): that would initialise the GPU in the test process, which
@@ -142,7 +153,7 @@ def _result(run):
 def test_bench_two_ranks_share_the_gpu():
     env = dict(os.environ, PYSPEEDY_AMD_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    common = ["--steps", "6", "--warmup", "3", "--regions", "2", "--no-cpu-baseline"]
+    common = ["--full", "--steps", "6", "--warmup", "3", "--regions", "2", "--no-cpu-baseline"]
     strong = _result(subprocess.run([sys.executable, BENCH, "--gpus", "2", "--scaling", "strong", "--members", "6"] + common,
                                     capture_output=True, text=True, timeout=900, env=env))
     assert strong["n_gpus"] == 2 and strong["scaling"] == "strong"
@@ -174,8 +185,8 @@ def test_a_hanging_one_process_child_does_not_cost_the_line():
                PYSPEEDY_AMD_BENCH_ONE_PROCESS_CMD="%s -c 'import time; time.sleep(3600)'" % sys.executable)
     env.pop("WORLD_SIZE", None)
     t0 = time.time()
-    res = _result(subprocess.run([sys.executable, BENCH, "--gpus", "2", "--members", "4", "--steps", "6", "--warmup", "3", "--regions", "2",
-                                  "--no-cpu-baseline", "--budget", "90"], capture_output=True, text=True, timeout=600, env=env))
+    res = _result(subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--members", "4", "--steps", "6", "--warmup", "3",
+                                  "--regions", "2", "--no-cpu-baseline", "--budget", "90"], capture_output=True, text=True, timeout=600, env=env))
     wall = time.time() - t0
     assert wall < 90 + 30, wall
     assert res["n_gpus"] == 2 and res["value"] > 0 and res["roofline"]["frac"] > 0
@@ -183,7 +194,7 @@ def test_a_hanging_one_process_child_does_not_cost_the_line():
     assert "no answer within" in op["error"] and op["timeouts_s"][0] <= 30.0 and op["timeouts_s"][1] == 0.0
     assert res["budget"]["budget_s"] == 90.0 and res["budget"]["used_s"] < 90.0
     # ... and with no time left at all nothing secondary is started: the headline alone
-    res = _result(subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "6", "--warmup", "3", "--regions", "2",
+    res = _result(subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--steps", "6", "--warmup", "3", "--regions", "2",
                                   "--no-cpu-baseline", "--budget", "1"], capture_output=True, text=True, timeout=600, env=env))
     assert res["value"] > 0 and res["one_process"] == {"skipped": "budget"} and res["cfg4_strong"] == {"skipped": "budget"}
     assert {k["leg"] for k in res["budget"]["skipped"]} == {"cfg4_strong", "one_process", "stream_ceiling"}
@@ -213,7 +224,7 @@ def test_the_n_rank_line_is_complete():
     it, and BASELINE cfg 4 to the letter (64 members in total, sharded) beside the weak headline."""
     env = dict(os.environ, PYSPEEDY_AMD_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    res = _result(subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "6", "--warmup", "3", "--regions", "2",
+    res = _result(subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--steps", "6", "--warmup", "3", "--regions", "2",
                                   "--cpu-seconds", "1.5"], capture_output=True, text=True, timeout=1200, env=env))
     assert res["n_gpus"] == 2 and res["scaling"] == "weak" and res["config"]["members_total"] == 128
     assert res["config"]["plan"].startswith("2 member groups")
@@ -248,7 +259,7 @@ def test_the_one_gpu_line_carries_the_drop_in_and_every_store_legs():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "PYSPEEDY_AMD_BENCH_BACKEND"):
         env.pop(k, None)
-    res = _result(subprocess.run([sys.executable, BENCH, "--members", "8", "--steps", "6", "--warmup", "3", "--regions", "2",
+    res = _result(subprocess.run([sys.executable, BENCH, "--full", "--members", "8", "--steps", "6", "--warmup", "3", "--regions", "2",
                                   "--cpu-seconds", "1.5", "--leg-seconds", "0.05"], capture_output=True, text=True, timeout=1200,
                                  env=env))
     assert res["n_gpus"] == 1 and res["config"]["members_total"] == 8
@@ -344,6 +355,32 @@ def test_bench_one_rank_world_through_rccl():
 
 
 @pytest.mark.gpu
+def test_a_plain_run_times_its_steps_and_dumps_the_same_outputs_every_time(tmp_path):
+    """`--steps K` times exactly K steps (one region), the line leaves out everything --full adds, and --dump-outputs writes the
+    state those steps left: float64, complex split into (re, im), bit for bit the same in a second run with the same arguments."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "PYSPEEDY_AMD_BENCH_BACKEND"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        res = _result(subprocess.run([sys.executable, BENCH, "--gpus", "1", "--members", "4", "--steps", "12", "--warmup", "3",
+                                      "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env))
+        assert res["steps"] == 12 and res["regions"] == 1 and res["ms_per_step"] > 0 and res["higher_is_better"] is True
+        assert abs(res["timed_seconds"] - res["ms_per_step"] * 12 * 1e-3) < 1e-9 * res["timed_seconds"] + 1e-12
+        assert res["dtype"] == "f64" and res["unit"] == "simulated-years/day" and res["vs_baseline"] is None
+        assert not {"roofline", "cpu_baseline", "drop_in_step", "facade_run", "cfg3", "cfg5"} & set(res)
+        dumps.append({n: np.load(out / (n + ".npy")) for n in ("vor", "div", "t", "tr", "ps", "members")})
+    a, b = dumps
+    assert list(a["members"]) == [0.0, 1.0, 2.0, 3.0]
+    assert a["vor"].shape == (4, 31, 32, 8, 2, 2) and a["ps"].shape == (4, 31, 32, 2, 2)
+    for name in a:
+        assert a[name].dtype == np.float64 and np.isfinite(a[name]).all() and np.array_equal(a[name], b[name]), name
+    assert np.abs(a["t"]).max() > 0 and not np.array_equal(a["t"][0], a["t"][1])  # (the members are perturbed apart)
+
+
+@pytest.mark.gpu
 def test_bench_one_process_mode():
     """`--one-process`: no ranks, this process drives the devices through spd_parallel_step -- rehearsed on the one GPU of the
     box, where 40 containers are kept as two device models (both enqueued before either is waited for)."""
@@ -372,7 +409,7 @@ def test_bench_under_torchrun_measures_the_host_baseline_on_rank_0():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(bench.free_port()), BENCH, "--gpus", "2", "--members", "4", "--steps", "6", "--warmup", "3",
-           "--regions", "2", "--cpu-seconds", "1.5"]
+           "--regions", "2", "--cpu-seconds", "1.5", "--full"]
     res = _result(subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env))
     assert res["n_gpus"] == 2 and res["config"]["members_total"] == 8
     assert res["cpu_baseline"]["all_cores"]["cores"] >= 1 and res["vs_baseline"] > 0

@@ -27,8 +27,9 @@ def test_registry_covers_the_reference_state():
 
 def test_model_state_def_has_the_layout_of_the_references_json():
     """`pyspeedy.speedy.MODEL_STATE_DEF` is the reference's data/model_state.json; here the same mapping is generated from the
-    registry.  Where the reference is at hand (build container) every entry is compared with it: Fortran type, dimension string,
-    run-length dimension, export name and export dimensions, and the units of the default output variables."""
+    registry.  Every entry is compared with the reference's file (tests/golden/reference_fixtures/model_state.json): Fortran
+    type, dimension string, run-length dimension, export name and export dimensions, and the units of the default output
+    variables."""
     import json
     import pyspeedy_amd
     from pyspeedy_amd import registry as R
@@ -38,10 +39,7 @@ def test_model_state_def_has_the_layout_of_the_references_json():
     assert set(mine["vor"]) == {"dtype", "dims", "desc", "time_dim", "units", "nc_dims", "alt_name", "std_name"}
     assert ERROR_CODES[0] == "Run successful." and "range" in ERROR_CODES[-2] and "Unexpected" in ERROR_CODES[-77]
     assert pyspeedy_amd.example_sst_anomaly_file().endswith("sst_anomaly.nc")
-    path = "/root/reference/pyspeedy/data/model_state.json"
-    if not os.path.isfile(path):
-        pytest.skip("the reference is not on this machine")
-    with open(path) as fh:
+    with open(os.path.join(GOLD, "reference_fixtures", "model_state.json")) as fh:  # the reference's pyspeedy/data/model_state.json
         ref = json.load(fh)
     squash = lambda s: None if s is None else s.replace(" ", "")
     for name, r in ref.items():

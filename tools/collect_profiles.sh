@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/final
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-SER="--serial-plan --no-legs --no-cpu-baseline"
+SER="--full --serial-plan --no-legs --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k64 -o run -- python3 $R/bench.py $SER > $OUT/k64.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k8 -o run -- python3 $R/bench.py --scaling strong --members 8 $SER > $OUT/k8.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k1 -o run -- python3 $R/bench.py --scaling strong --members 1 $SER > $OUT/k1.log 2>&1
@@ -39,10 +39,10 @@ unset PYSPEEDY_AMD_PHYS_STORE32
 # the copy that is committed comes back through gpurun_out/final like everything else.
 mkdir -p $R/profiles && cp $OUT/${TAG}_pmc_model_step.json $OUT/${TAG}_pmc_cfg5_storage32_1.json $R/profiles/ 2>/dev/null || true
 # the default line carries every BASELINE config since round 4 (cfg3, cfg4_shard8, cfg5, cfg2_transforms legs)
-python3 $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
-python3 $R/bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_20.json 2>> $OUT/bench.err
-python3 $R/bench.py --serial-plan --no-legs --no-cpu-baseline > $OUT/${TAG}_bench_serial_plan.json 2>> $OUT/bench.err
-python3 $R/bench.py --config cfg5 --no-cpu-baseline --no-legs > $OUT/${TAG}_bench_cfg5.json 2>> $OUT/bench.err
+python3 $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_20.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --serial-plan --no-legs --no-cpu-baseline > $OUT/${TAG}_bench_serial_plan.json 2>> $OUT/bench.err
+python3 $R/bench.py --full --config cfg5 --no-cpu-baseline --no-legs > $OUT/${TAG}_bench_cfg5.json 2>> $OUT/bench.err
 python3 $R/bench.py --one-process --gpus 1 --no-cpu-baseline --steps 360 > $OUT/${TAG}_bench_one_process.json 2>> $OUT/bench.err
 echo "bench lines done"
 # the Legendre stage on its own at 16 384 fields (north_star's literal target): kernel stats, then the two PMC passes

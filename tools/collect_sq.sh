@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 D=/tmp/sq_$TAG
 rm -rf $D
-PMC="--steps 36 --warmup 6 --regions 1 --serial-plan --no-legs --no-cpu-baseline"
+PMC="--full --steps 36 --warmup 6 --regions 1 --serial-plan --no-legs --no-cpu-baseline"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES \
     --output-format csv -d $D/a -o run -- python3 $R/bench.py $PMC > $OUT/sq_a_$TAG.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR \

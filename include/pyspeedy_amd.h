@@ -367,13 +367,44 @@ int spd_model_grid_filter(spd_model_handle m, int first, int count, void *stream
  * hosts that write files: narrowing, level order and byte order happen on the GPU, and what crosses PCIe is the file's payload. */
 int spd_model_export_pack(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes,
                           void *stream);
+/* Time-mean statistics of grid-space fields, accumulated on the device inside spd_model_step / spd_model_step_checked_begin calls
+ * of any length: per member and grid point the number of samples, the mean and (optionally) the unbiased time variance, fp64
+ * (Welford's update).  Variables: any of u_grid, v_grid, t_grid, q_grid, phi_grid (kx levels), ps_grid, precnv, precls, in the
+ * units and layout spd_model_spectral2grid + spd_model_get give (q kg/kg, phi m, ps Pa; precnv / precls as the column physics
+ * stores them).  A sample is taken after every step that leaves the model's absolute step counter at a multiple of `every` --
+ * whatever way the host cuts its calls -- and equals what spd_model_spectral2grid would give if the call had ended there.
+ * Sampling changes nothing of the run: the state and every registry variable, u_grid ... ps_grid included, are bitwise those of a
+ * run without statistics.  Each member group samples its own members on its own stream behind its last launch of the step.
+ *   _configure  allocates the accumulators (synchronises the device) and starts a new period; n_names = 0 switches sampling off.
+ *               SPD_E_ARG for an unknown or repeated name, every < 1, or while a checked call is in flight.
+ *   _reset      starts a new averaging period (host only, no device work).  spd_model_init does the same.
+ *   _samples    samples taken since the period started.
+ *   _read       members [first, first + count) of one variable, kind SPD_STATS_MEAN or SPD_STATS_VARIANCE, as fp64 into
+ *               dst_device[count][levels][48][96] (the layout of the registry variable), stream-ordered.
+ *   _ensemble   over all members of the model, per point: kind SPD_STATS_MEAN (the mean of the members' time means) or
+ *               SPD_STATS_STD (their standard deviation, ddof 1) into dst_device[levels][48][96], fp64, stream-ordered.
+ * Reads fail (SPD_E_ARG, with the reason) before configuring, for a variable that is not configured, before the first sample
+ * (before the second for the variance), while a checked call is in flight, and after a checked call that reported a failed
+ * range check: the samples behind a failed step are garbage; the statistics stay invalid until _reset or spd_model_init.
+ * spd_model_copy_member does not carry statistics, and the outer boundary (spd_parallel_step*, include/pyspeedy_amd_driver.h)
+ * does not keep them across the models it merges and splits. */
+#define SPD_STATS_MEAN 0
+#define SPD_STATS_VARIANCE 1
+#define SPD_STATS_STD 2
+int spd_model_stats_configure(spd_model_handle m, const char *const *names, int n_names, int every, int with_variance);
+int spd_model_stats_reset(spd_model_handle m);
+int spd_model_stats_samples(spd_model_handle m);
+int spd_model_stats_read(spd_model_handle m, const char *name, int kind, int first, int count, void *dst_device, size_t dst_bytes,
+                         void *stream);
+int spd_model_stats_ensemble(spd_model_handle m, const char *name, int kind, void *dst_device, size_t dst_bytes, void *stream);
 /* modelstate_init_sst_anom (speedy_driver.f90.j2:225-237): sst_anom(ix, il, 0:n_months+1) per member, zero-filled */
 int spd_model_init_sst_anom(spd_model_handle m, int n_months);
 /* Stochastically perturbed parametrisation tendencies (sppt.f90; compile-time off and non-functional in the reference:
  * PARITY UNPINNED, see csrc/sppt.hip).  Deterministic: the noise is a function of (seed, first_member_id + member, step,
  * level, coefficient).  While on, every step advances the AR(1) spectral pattern (registry names sppt_spec, sppt_pattern). */
 int spd_model_set_sppt(spd_model_handle m, int on, uint64_t seed, int64_t first_member_id);
-/* device-to-device copy of every registered variable of one member into a member of another model on the same GPU */
+/* device-to-device copy of every registered variable of one member into a member of another model on the same GPU (not its
+ * time statistics: spd_model_stats_*) */
 int spd_model_copy_member(spd_model_handle dst, int dst_member, spd_model_handle src, int src_member, void *stream);
 /* the named registry variables only; the two models may live on different GPUs (device-to-device over xGMI,
  * hipMemcpyPeerAsync): how one process hands the shared boundary fields to the members it keeps on its other devices */

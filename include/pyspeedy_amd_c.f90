@@ -12,6 +12,7 @@ module pyspeedy_amd_c
     implicit none
 
     integer(c_int), parameter :: SPD_OK = 0, SPD_E_ARG = -1, SPD_E_DEVICE = -2, SPD_E_SIZE = -3
+    integer(c_int), parameter :: SPD_STATS_MEAN = 0, SPD_STATS_VARIANCE = 1, SPD_STATS_STD = 2
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -136,6 +137,39 @@ module pyspeedy_amd_c
             import :: c_ptr, c_int
             type(c_ptr), value :: model, stream
             integer(c_int), value :: first, count
+        end function
+        ! time-mean statistics accumulated on the device inside spd_model_step calls (pyspeedy_amd.h: spd_model_stats_*).
+        ! names: an array of c_ptr to NUL-terminated strings ("t_grid"//c_null_char, ...); kind: SPD_STATS_MEAN / _VARIANCE / _STD
+        integer(c_int) function spd_model_stats_configure(model, names, n_names, every, with_variance) &
+                bind(C, name="spd_model_stats_configure")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), value :: n_names, every, with_variance
+        end function
+        integer(c_int) function spd_model_stats_reset(model) bind(C, name="spd_model_stats_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_stats_samples(model) bind(C, name="spd_model_stats_samples")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_stats_read(model, name, kind, first, count, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_stats_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: kind, first, count
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_stats_ensemble(model, name, kind, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_stats_ensemble")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: kind
+            integer(c_size_t), value :: dst_bytes
         end function
         integer(c_int) function spd_model_current_step(model) bind(C, name="spd_model_current_step")
             import :: c_ptr, c_int

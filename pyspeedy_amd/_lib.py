@@ -16,6 +16,7 @@ IX, IL, IY, KX, MX, NX, TRUNC = 96, 48, 24, 8, 31, 32, 30
 NSPEC, NFOUR, NGRID = MX * NX, 2 * MX * IL, IX * IL
 
 SPD_OK, SPD_E_ARG, SPD_E_DEVICE, SPD_E_SIZE = 0, -1, -2, -3
+SPD_STATS_MEAN, SPD_STATS_VARIANCE, SPD_STATS_STD = 0, 1, 2  # kinds of spd_model_stats_read / _ensemble
 
 
 class SpeedyHipError(RuntimeError):
@@ -129,6 +130,11 @@ _SIGNATURES = {
     "spd_model_init_sst_anom": (C.c_int, [C.c_void_p, C.c_int]),
     "spd_model_set_sppt": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int64]),
     "spd_model_copy_member": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "spd_model_stats_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
+    "spd_model_stats_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_stats_samples": (C.c_int, [C.c_void_p]),
+    "spd_model_stats_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_stats_ensemble": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     # outer boundary (include/pyspeedy_amd_driver.h): the procedures of speedy_driver.f90.j2
     "spd_modelstate_init": (C.c_int, [C.POINTER(C.c_int64)]),
     "spd_modelstate_init_ensemble": (C.c_int, [C.POINTER(C.c_int64), C.c_int32]),

@@ -25,6 +25,7 @@
 #include "bounded_call.hpp"
 #include "launch_events.hpp"
 #include "sppt_point.hpp"
+#include "stats.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
 
@@ -215,6 +216,26 @@ struct spd_model {
     // grid-space copies of the prognostic variables in output units (prognostics.f90:125-219) and their transform tables
     double *u_grid = nullptr, *v_grid = nullptr, *t_grid = nullptr, *q_grid = nullptr, *phi_grid = nullptr, *ps_grid = nullptr;
     FieldDesc *exp_inv_table[2] = {nullptr, nullptr}, *exp_fwd_table[2] = {nullptr, nullptr};  // 41 / 40 per member; [phi buffer]
+    // Running time statistics (spd_model_stats_*): sampled by the step loop after every step that ends on a multiple of `every`,
+    // behind each member group's last launch of that step on the group's stream.  One allocation (own hipMalloc, not the arena:
+    // a reconfiguration frees it): the accumulators [variable][M][levels][4608] (mean, and M2 with variance), the sample slab
+    // [M][slab_fields][4608] the export transforms write instead of the registry's grid arrays, their descriptor tables
+    // ([phi buffer]) and the plane descriptors of the accumulate kernel.
+    struct Stats {
+        struct Var {
+            int id, levels;
+            size_t offset;  // doubles from `mean` / `m2` to member 0 of the variable
+        };
+        bool on = false, variance = false, valid = true, uv = false, precip = false;
+        int every = 1, slab_fields = 0, nplanes = 0;
+        long long samples = 0;
+        std::string invalid_why;
+        std::vector<Var> vars;
+        void *alloc = nullptr;
+        double *mean = nullptr, *m2 = nullptr, *slab = nullptr;
+        FieldDesc *table[2] = {nullptr, nullptr};
+        StatsPlane *planes = nullptr;
+    } stats;
 };
 
 namespace spd {
@@ -688,6 +709,7 @@ int spd_model_destroy(spd_model_handle m) {
         if (m->cstream[i]) (void)hipStreamDestroy(m->cstream[i]);
         if (m->cev[i]) (void)hipEventDestroy(m->cev[i]);
     }
+    if (m->stats.alloc) (void)hipFree(m->stats.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1229,6 +1251,8 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->step_poison.clear();  // (every array of the state is rebuilt below)
     m->steps_pending = 0;
     m->fail_launch_after = -1;
+    m->stats.samples = 0;  // (a new run: a new averaging period)
+    m->stats.valid = true;
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1333,6 +1357,8 @@ static int ensure_group_streams(spd_model *m, int G) {
 // diagnostics.f90 is available separately through spd_model_check (the reference runs it after every step).
 // record: the range check of every step is left in m->h_steps_err[step][member] (spd_model_step_checked_begin) -- the check of step
 // k rides in the spectral -> grid launch of step k + 1 of the same members, the last one is a launch of its own behind the call.
+static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_stats_configure)
+
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
     if (int rc = usable(m, who)) return rc;
@@ -1420,7 +1446,9 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     note_accepted(0);
     bool launched = false, device_failed = false;  // a launch of this call went out / a device call of it failed
     const int tl_check = 1;  // the check looks at time level 2 (do_single_step checks the state the step has just produced)
+    const long long samples0 = m->stats.samples;  // (statistics: every round takes the same samples)
     for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
+        long long taken = 0;
         const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
         if (round > 0) {  // the same steps again, for the next members
             m->cal = start.cal;
@@ -1438,7 +1466,10 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             ZonalDevice zd{};
             if (new_day) zd = forcing_host(m, 1);
             const int sw = (m->current_step % 3 == 0) ? 1 : 0;
-            const int diag = (m->diag_every_step || it == nsteps - 1) ? 1 : 0;
+            // a step whose state the statistics sample: its diagnostics-only outputs are stored when precnv / precls are sampled
+            const bool sample = m->stats.on && (m->current_step + 1) % m->stats.every == 0;
+            if (sample) ++taken;
+            const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip)) ? 1 : 0;
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
             // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
@@ -1496,6 +1527,14 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                     }
                     ++m->checks_alone;
                 }
+                if (rc == SPD_OK && sample) {  // behind this group's last launch of the step, on its stream
+                    const hipError_t e = stats_sample(m, first, count, samples0 + taken, gs[g]);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": time statistics: " + hipGetErrorString(e));
+                        device_failed = true;
+                    }
+                }
                 first += count;
             }
             if (rc != SPD_OK) break;
@@ -1504,6 +1543,7 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             m->cal = next;
             m->surf_cache_valid = true;
             if (round == 0) note_accepted(it + 1);
+            if (round == 0 && sample) m->stats.samples = samples0 + taken;
         }
         round_first += round_count;
     }
@@ -1559,6 +1599,12 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
             const int c = codes[static_cast<size_t>(k) * M + i];
             if ((c >> 2) != m->steps_ticket) return m_fail(SPD_E_DEVICE, std::string(who) + ": a range check finished without publishing its code");
             if (c & 1) first_failed_step[i] = k;
+        }
+    for (int i = 0; i < M && m->stats.on && m->stats.valid; ++i)
+        if (first_failed_step[i] >= 0) {  // the samples behind a failed step are taken from a state the model does not accept
+            m->stats.valid = false;
+            m->stats.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
+                                   " of a checked call";
         }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)
@@ -1913,6 +1959,224 @@ int spd_model_set_sppt(spd_model_handle m, int on, uint64_t seed, int64_t first_
     m->sppt_member_base = first_member_id;
     m->sppt_first = true;
     m->sppt_step = 0;
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// time-mean statistics sampled inside multi-step calls (spd_model_stats_*; kernels: stats.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct StatsCatalogueEntry {
+    const char *name;
+    int levels, unit;  // unit: as StatsPlane::unit
+};
+// ids 0 ... 5: from the spectral state through the export transforms; 6, 7: the column kernel's precipitation outputs
+constexpr StatsCatalogueEntry kStatsCatalogue[] = {{"u_grid", KX, 0},   {"v_grid", KX, 0}, {"t_grid", KX, 0}, {"q_grid", KX, 1},
+                                                   {"phi_grid", KX, 2}, {"ps_grid", 1, 3}, {"precnv", 1, 0}, {"precls", 1, 0}};
+constexpr int kStatsCatalogueSize = sizeof(kStatsCatalogue) / sizeof(kStatsCatalogue[0]);
+static int stats_id(const char *name) {
+    for (int v = 0; v < kStatsCatalogueSize; ++v)
+        if (std::strcmp(name, kStatsCatalogue[v].name) == 0) return v;
+    return -1;
+}
+}  // namespace
+
+// the sample of members [first, first + count) after the step just issued on `s`: what spd_model_spectral2grid would leave in the
+// grid arrays (the same vort2vel into sv, the same transforms, into the slab), then the moments
+static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
+    const spd_model::Stats &st = m->stats;
+    const DeviceTables &T = m->ctx->dev;
+    const size_t S = NSPEC * C, half = static_cast<size_t>(m->M) * 16, off = static_cast<size_t>(first) * 16;
+    hipError_t e = hipSuccess;
+    if (st.uv) e = run_vort2vel(T, m->P.vor + off * S, m->P.div + off * S, m->P.sv + off * S, m->P.sv + (half + off) * S, count * 16, s);
+    if (e == hipSuccess && st.slab_fields > 0)
+        e = run_spec2grid_table(T, st.table[m->phi_cur] + static_cast<size_t>(first) * st.slab_fields, count * st.slab_fields, s);
+    if (e == hipSuccess) e = run_stats_accumulate(st.planes, st.nplanes, st.slab, st.slab_fields, first, count, n, m->stored32 ? 1 : 0, s);
+    return e;
+}
+
+int spd_model_stats_configure(spd_model_handle m, const char *const *names, int n_names, int every, int with_variance) {
+    const char *who = "spd_model_stats_configure";
+    // (the arguments first: nothing below needs the device)
+    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
+    std::vector<int> ids;
+    for (int k = 0; k < n_names; ++k) {
+        const int id = names[k] ? stats_id(names[k]) : -1;
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
+                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls)");
+        if (std::find(ids.begin(), ids.end(), id) != ids.end())
+            return m_fail(SPD_E_ARG, std::string(who) + ": variable '" + names[k] + "' named twice");
+        ids.push_back(id);
+    }
+    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
+    spd_model::Stats &st = m->stats;
+    if (st.alloc) M_HIP(hipFree(st.alloc));
+    st = spd_model::Stats{};
+    if (n_names == 0) return SPD_OK;  // off
+    spd_model::Stats next;
+    next.every = every;
+    next.variance = with_variance != 0;
+    const size_t M = static_cast<size_t>(m->M);
+    size_t planes = 0;
+    for (int id : ids) {
+        next.vars.push_back({id, kStatsCatalogue[id].levels, M * planes * NG});
+        planes += static_cast<size_t>(kStatsCatalogue[id].levels);
+        if (id < 6) next.slab_fields += kStatsCatalogue[id].levels;
+        next.uv = next.uv || id < 2;
+        next.precip = next.precip || id >= 6;
+    }
+    next.nplanes = static_cast<int>(planes);
+    // one allocation: mean | m2 | slab | tables[2] | plane descriptors
+    constexpr size_t kAlign = 256;
+    auto up = [](size_t b) { return (b + kAlign - 1) / kAlign * kAlign; };
+    const size_t acc = up(M * planes * NG * sizeof(double)), slab = up(M * next.slab_fields * NG * sizeof(double)),
+                 table = up(M * next.slab_fields * sizeof(FieldDesc)), desc = up(planes * sizeof(StatsPlane));
+    const size_t total = acc * (next.variance ? 2 : 1) + slab + 2 * table + desc;
+    void *p = nullptr;
+    M_HIP(hipMalloc(&p, total));
+    char *at = static_cast<char *>(p);
+    next.alloc = p;
+    next.mean = reinterpret_cast<double *>(at), at += acc;
+    if (next.variance) next.m2 = reinterpret_cast<double *>(at), at += acc;
+    next.slab = reinterpret_cast<double *>(at), at += slab;
+    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += table;
+    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += table;
+    next.planes = reinterpret_cast<StatsPlane *>(at);
+    // the export descriptors of spd_model_spectral2grid (build_tables), with the slab as destination, for the chosen variables
+    const ModelPtrs &P = m->P;
+    auto spec = [](double *base, size_t field) { return base + field * NSPEC * C; };
+    const size_t half = M * 16;
+    std::vector<FieldDesc> host_table[2];
+    for (int par = 0; par < 2; ++par) {
+        host_table[par].reserve(M * next.slab_fields);
+        for (size_t i = 0; i < M; ++i) {
+            const size_t w = i * 8, s1 = i * 16;
+            size_t j = 0;
+            for (const auto &v : next.vars) {
+                for (int k = 0; k < v.levels && v.id < 6; ++k, ++j) {
+                    double *dst = next.slab + (i * next.slab_fields + j) * NG;
+                    switch (v.id) {
+                        case 0: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
+                        case 1: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
+                        case 2: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
+                        case 3: host_table[par].push_back({spec(P.tr, s1 + k), dst, 1, 0}); break;
+                        case 4: host_table[par].push_back({spec(m->phi_buf[par], w + k), dst, 1, 0}); break;
+                        default: host_table[par].push_back({spec(P.ps, i * 2), dst, 1, 0}); break;
+                    }
+                }
+            }
+        }
+    }
+    std::vector<StatsPlane> host_planes;
+    int slab_plane = 0;
+    for (const auto &v : next.vars)
+        for (int k = 0; k < v.levels; ++k) {
+            StatsPlane d{};
+            d.slab_plane = v.id < 6 ? slab_plane++ : -1;
+            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
+            d.unit = kStatsCatalogue[v.id].unit;
+            d.mean = next.mean + v.offset + static_cast<size_t>(k) * NG;
+            d.m2 = next.variance ? next.m2 + v.offset + static_cast<size_t>(k) * NG : nullptr;
+            d.member_stride = static_cast<long>(v.levels) * NG;
+            host_planes.push_back(d);
+        }
+    hipError_t e = hipSuccess;
+    if (next.slab_fields > 0) {
+        e = hipMemcpy(next.table[0], host_table[0].data(), host_table[0].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(next.table[1], host_table[1].data(), host_table[1].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(StatsPlane), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    next.on = true;
+    st = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_stats_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_stats_reset: null model");
+    if (!m->stats.on) return m_fail(SPD_E_ARG, "spd_model_stats_reset: no statistics configured (spd_model_stats_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_stats_reset: a checked multi-step call is in flight; end it first");
+    m->stats.samples = 0;  // (the next sample overwrites the accumulators instead of reading them: no device work)
+    m->stats.valid = true;
+    m->stats.invalid_why.clear();
+    return SPD_OK;
+}
+
+int spd_model_stats_samples(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_stats_samples: null model");
+    if (!m->stats.on) return m_fail(SPD_E_ARG, "spd_model_stats_samples: no statistics configured (spd_model_stats_configure)");
+    return static_cast<int>(m->stats.samples);
+}
+
+// what every read checks; -> the variable's entry
+static int stats_readable(spd_model *m, const char *name, const char *who, const spd_model::Stats::Var **out) {
+    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::Stats &st = m->stats;
+    if (!st.on) return m_fail(SPD_E_ARG, std::string(who) + ": no statistics configured (spd_model_stats_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (!st.valid)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the statistics are invalid until spd_model_stats_reset: " + st.invalid_why);
+    const int id = stats_id(name);
+    for (const auto &v : st.vars)
+        if (v.id == id) {
+            if (st.samples == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no sample taken since the statistics were (re)started");
+            *out = &v;
+            return SPD_OK;
+        }
+    return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
+}
+
+int spd_model_stats_read(spd_model_handle m, const char *name, int kind, int first, int count, void *dst_device, size_t dst_bytes,
+                         void *stream) {
+    const char *who = "spd_model_stats_read";
+    const spd_model::Stats::Var *v = nullptr;
+    if (int rc = stats_readable(m, name, who, &v)) return rc;
+    if (!dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    if (kind != SPD_STATS_MEAN && kind != SPD_STATS_VARIANCE)
+        return m_fail(SPD_E_ARG, std::string(who) + ": kind must be SPD_STATS_MEAN or SPD_STATS_VARIANCE");
+    const spd_model::Stats &st = m->stats;
+    if (kind == SPD_STATS_VARIANCE && !st.variance) return m_fail(SPD_E_ARG, std::string(who) + ": configured without variance");
+    if (kind == SPD_STATS_VARIANCE && st.samples < 2) return m_fail(SPD_E_ARG, std::string(who) + ": the variance needs two samples");
+    const size_t per = static_cast<size_t>(v->levels) * NG, need = static_cast<size_t>(count) * per * sizeof(double);
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (count == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t at = v->offset + static_cast<size_t>(first) * per;
+    if (kind == SPD_STATS_MEAN) {
+        M_HIP(hipMemcpyAsync(dst_device, st.mean + at, need, hipMemcpyDeviceToDevice, s));
+    } else {
+        const hipError_t e = run_stats_variance(st.m2 + at, static_cast<double *>(dst_device), static_cast<long>(count * per), st.samples, s);
+        if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    return SPD_OK;
+}
+
+int spd_model_stats_ensemble(spd_model_handle m, const char *name, int kind, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_stats_ensemble";
+    const spd_model::Stats::Var *v = nullptr;
+    if (int rc = stats_readable(m, name, who, &v)) return rc;
+    if (!dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (kind != SPD_STATS_MEAN && kind != SPD_STATS_STD) return m_fail(SPD_E_ARG, std::string(who) + ": kind must be SPD_STATS_MEAN or SPD_STATS_STD");
+    const size_t per = static_cast<size_t>(v->levels) * NG, need = per * sizeof(double);
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    M_HIP(hipSetDevice(m->ctx->device));
+    const hipError_t e = run_stats_ensemble(m->stats.mean + v->offset, m->M, static_cast<long>(per), kind == SPD_STATS_STD ? 1 : 0,
+                                            static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
 }
 

@@ -310,6 +310,60 @@ class EnsembleModel:
         check(self._lib.spd_model_profile_read(self._m, C.byref(ms), C.byref(n), C.byref(f)), "spd_model_profile_read")
         return ms.value, n.value, f.value
 
+    # ---- time-mean statistics accumulated on the device (spd_model_stats_*, include/pyspeedy_amd.h) ---------------------
+    STATS_VARIABLES = ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid", "ps_grid", "precnv", "precls")
+
+    def stats_configure(self, variables, every, variance=True):
+        """Sample `variables` (any of STATS_VARIABLES) after every step that leaves current_step at a multiple of `every`, inside
+        run() / run_checked() calls of any length; per member and grid point the mean and, with `variance`, the unbiased time
+        variance.  Starts a new averaging period; an empty list switches sampling off.  Synchronises the device."""
+        names = [str(v) for v in variables]
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        check(self._lib.spd_model_stats_configure(self._m, arr, len(names), int(every), int(bool(variance))),
+              "spd_model_stats_configure")
+
+    def stats_reset(self):
+        """Start a new averaging period (e.g. at a month boundary a call was made to end at)."""
+        check(self._lib.spd_model_stats_reset(self._m), "spd_model_stats_reset")
+
+    @property
+    def stats_samples(self):
+        n = self._lib.spd_model_stats_samples(self._m)
+        if n < 0:
+            check(n, "spd_model_stats_samples")
+        return int(n)
+
+    def _stats_shape(self, name):
+        levels = 8 if name in ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid") else 1
+        return (levels, 48, 96) if levels > 1 else (48, 96)
+
+    def _stats_read(self, name, kind, first, count):
+        first, count = self._range(first, count)
+        out = torch.empty((count,) + self._stats_shape(name), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_stats_read(self._m, name.encode(), kind, first, count, C.c_void_p(out.data_ptr()),
+                                                 out.numel() * 8, self._stream()), "spd_model_stats_read(%s)" % name)
+        return out
+
+    def stats_mean(self, name, first=0, count=None):
+        """Time mean of members [first, first + count): float64 tensor on the model's device, laid out as device_view(name)."""
+        return self._stats_read(name, _lib.SPD_STATS_MEAN, first, count)
+
+    def stats_var(self, name, first=0, count=None):
+        """Unbiased time variance (ddof 1) of members [first, first + count), laid out as stats_mean."""
+        return self._stats_read(name, _lib.SPD_STATS_VARIANCE, first, count)
+
+    def stats_ensemble(self, name):
+        """(mean, std) over the members of their time means, per point (std: ddof 1); float64 tensors [levels,] 48, 96."""
+        out = []
+        for kind in (_lib.SPD_STATS_MEAN, _lib.SPD_STATS_STD):
+            t = torch.empty(self._stats_shape(name), dtype=torch.float64, device=self.sp.device)
+            with torch.cuda.device(self.sp.device):
+                check(self._lib.spd_model_stats_ensemble(self._m, name.encode(), kind, C.c_void_p(t.data_ptr()), t.numel() * 8,
+                                                         self._stream()), "spd_model_stats_ensemble(%s)" % name)
+            out.append(t)
+        return tuple(out)
+
     def set_flags(self, land_coupling_flag=True, sst_anomaly_coupling_flag=True, increase_co2=False):
         check(self._lib.spd_model_set_flags(self._m, int(land_coupling_flag), int(sst_anomaly_coupling_flag),
                                             int(increase_co2)), "spd_model_set_flags")

@@ -187,7 +187,7 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model
             integer(c_int), value :: fp32
         end function
-        ! launch-plan switches by name ("diag_every_step", "coupler_in_spectral", "spectral_early", "split_dyn"); name is
+        ! launch-plan switches by name ("diag_every_step", "spectral_early", "split_dyn"); name is
         ! a C string: pass "diag_every_step"//c_null_char
         integer(c_int) function spd_model_set_option(model, name, value) bind(C, name="spd_model_set_option")
             import :: c_ptr, c_int, c_char, c_int32_t

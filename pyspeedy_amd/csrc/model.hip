@@ -197,9 +197,6 @@ struct spd_model {
     // The coupler's climatology interpolation is valid for a day (surface.hip): true after a coupling, false after anything
     // wrote to the state from outside the step
     bool surf_cache_valid = false;
-    // The coupling of the step rides in the launch of spectral_step_kernel (tail blocks, dynamics.hip) instead of being a
-    // launch of its own: PYSPEEDY_AMD_COUPLER_IN_SPECTRAL=0 / 1
-    bool coupler_in_spectral = true;
     int spectral_early = -1;  // spectral_step_kernel with all loads up front: -1 = for launches of up to 8 members, 0 / 1 = never / always
     int land_coupling_flag = 1, sst_anomaly_flag = 1, increase_co2 = 0, anom_planes = 3;
     double ablco2_ref = 6.0;
@@ -561,7 +558,6 @@ int spd_model_create(spd_handle h, int nmembers, spd_model_handle *out) {
     if (const char *env = getenv("PYSPEEDY_AMD_PRUNE_DEAD")) m->inv_per_member = atoi(env) != 0 ? 77 : 91;
     if (const char *env = getenv("PYSPEEDY_AMD_DIAG_EVERY_STEP")) m->diag_every_step = atoi(env) != 0;
     m->fold_geo = nmembers <= 8;
-    if (const char *env = getenv("PYSPEEDY_AMD_COUPLER_IN_SPECTRAL")) m->coupler_in_spectral = atoi(env) != 0;
     if (const char *env = getenv("PYSPEEDY_AMD_SPECTRAL_EARLY")) m->spectral_early = atoi(env);
     if (const char *env = getenv("PYSPEEDY_AMD_FOLD_GEO")) m->fold_geo = atoi(env) != 0;
     if (const char *env = getenv("PYSPEEDY_AMD_PHYS_STORE32")) m->phys_store32 = atoi(env) != 0;
@@ -1019,10 +1015,9 @@ static int next_ticket(spd_model *m) {
 // Wait for the codes of the range-check launch that carries `ticket` by watching the pinned memory it writes them to: the host
 // sees each code the moment its store lands (a system-scope release store of 4 * ticket + flag), a few microseconds before a
 // completion event behind the kernel would have been signalled and noticed -- for a host that makes one synchronous call per
-// model step that wait is on the critical path of every step (PYSPEEDY_AMD_POLL_CODES=0: wait for the event / the stream
-// instead).  The event (or the stream) is still asked every few thousand looks, so that a device fault ends the wait.
+// model step that wait is on the critical path of every step (3 ... 5 us per step less than waiting for the event).  The event
+// (or the stream) is still asked every few thousand looks, so that a device fault ends the wait.
 static int wait_codes(spd_model *m, const int *pinned, int ticket, hipEvent_t ev, hipStream_t s, int32_t *out, const char *who) {
-    static const bool poll = !(getenv("PYSPEEDY_AMD_POLL_CODES") && atoi(getenv("PYSPEEDY_AMD_POLL_CODES")) == 0);
     const volatile int *codes = pinned;
     const int M = m->M;
     auto all_there = [&]() {
@@ -1031,18 +1026,13 @@ static int wait_codes(spd_model *m, const int *pinned, int ticket, hipEvent_t ev
         return true;
     };
     bool there = false;
-    if (poll) {
-        for (unsigned spin = 1; !(there = all_there()); ++spin) {
-            if ((spin & 0xfff) == 0) {
-                const hipError_t q = ev ? hipEventQuery(ev) : hipStreamQuery(s);
-                if (q == hipSuccess) break;  // the launch is over: its stores are visible now if they ever will be
-                if (q != hipErrorNotReady) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(q));
-            }
-            __builtin_ia32_pause();
+    for (unsigned spin = 1; !(there = all_there()); ++spin) {
+        if ((spin & 0xfff) == 0) {
+            const hipError_t q = ev ? hipEventQuery(ev) : hipStreamQuery(s);
+            if (q == hipSuccess) break;  // the launch is over: its stores are visible now if they ever will be
+            if (q != hipErrorNotReady) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(q));
         }
-    } else {
-        if (ev) M_HIP(hipEventSynchronize(ev));
-        else M_HIP(hipStreamSynchronize(s));
+        __builtin_ia32_pause();
     }
     if (!there && !all_there()) return m_fail(SPD_E_DEVICE, std::string(who) + ": the range check finished without publishing its codes");
     std::atomic_thread_fence(std::memory_order_acquire);
@@ -1403,11 +1393,10 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     // latency-bound transforms run beside the other's streaming column / spectral kernels.  Measured at 64 members: 0.241 ms
     // per step every time, against 0.243 ... 0.250 when left to chance (profiles/r03_member_groups.txt); 96 members -2.8 %;
     // nothing at 32 / 48 members or with 3 groups.  It costs a call the time its first and last three quarters of a step run
-    // alone; applied to calls of at least 36 steps (PYSPEEDY_AMD_GROUP_OFFSET=n: from n steps, 0: never -- in 20-step calls it
-    // measured 0 ... +1.5 %; in the 36-step calls of a time loop with daily hooks -1.8 %: 9.58 -> 9.41 ms per simulated day,
-    // round 6; 72 until then).
-    static const int offset_from = getenv("PYSPEEDY_AMD_GROUP_OFFSET") ? atoi(getenv("PYSPEEDY_AMD_GROUP_OFFSET")) : 36;
-    const bool offset = offset_from > 0 && G == 2 && nsteps >= offset_from;
+    // alone; applied to calls of at least kOffsetFrom steps (in 20-step calls it measured 0 ... +1.5 %; in the 36-step calls of
+    // a time loop with daily hooks -1.8 %: 9.58 -> 9.41 ms per simulated day, round 6; 72 until then).
+    constexpr int kOffsetFrom = 36;
+    const bool offset = G == 2 && nsteps >= kOffsetFrom;
     if (offset && !m->ev_offset) M_HIP(hipEventCreateWithFlags(&m->ev_offset, hipEventDisableTiming));
     // rounds (see block_members): the members of a round go through all steps of the call before the next round starts
     // (also with ONE group when the caller says so by setting member_groups to 1 on a large model -- the outer boundary does for
@@ -1473,6 +1462,8 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
             // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
+            // It rides as tail blocks in the step's spectral_step_kernel launch (dynamics.hip; as a launch of its own the step
+            // was 2 ... 7 % slower).
             Calendar next = m->cal;
             next.advance();
             const TimeInterp w = time_interp(next);
@@ -1493,7 +1484,6 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                 }
                 CouplerArgs cpl{m->S, w, first, count, 1 + (m->current_step + 1) / 36, m->land_coupling_flag, m->sst_anomaly_flag,
                                 m->anom_planes, fresh};
-                const bool ride = m->coupler_in_spectral;
                 if (rc == SPD_OK) {
                     hipError_t e = hipSuccess;
                     if (offset && first_of_call && g == 1) e = hipStreamWaitEvent(gs[1], m->ev_offset, 0);
@@ -1501,20 +1491,11 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                     const CheckArgs chk{m->P.vor, m->P.div, m->P.t, tl_check, record && it > 0 ? m->h_steps_err + static_cast<size_t>(it - 1) * m->M : nullptr,
                                         nullptr, m->steps_ticket, first};
                     if (e == hipSuccess)
-                        e = step_range(m, 2, 2, 2 * delt, sw, first, count, diag, run_geo, ride ? &cpl : nullptr, gs[g],
+                        e = step_range(m, 2, 2, 2 * delt, sw, first, count, diag, run_geo, &cpl, gs[g],
                                        (offset && first_of_call && g == 0) ? m->ev_offset : nullptr, record && it > 0 ? &chk : nullptr);
                     if (e != hipSuccess) {
                         (void)hipGetLastError();
                         rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
-                }
-                if (rc == SPD_OK && !ride) {
-                    ProfScope ps(m, SPD_K_COUPLER, count, gs[g]);
-                    const hipError_t e = run_coupler(m->S, first, count, w, 1 + (m->current_step + 1) / 36, m->land_coupling_flag,
-                                                     m->sst_anomaly_flag, m->anom_planes, fresh, gs[g]);
-                    if (e != hipSuccess) {
-                        rc = m_fail(SPD_E_DEVICE, std::string("couple_sea_land: ") + hipGetErrorString(e));
                         device_failed = true;
                     }
                 }
@@ -1751,7 +1732,7 @@ int spd_model_get_config(spd_model_handle m, int32_t *cfg) {
     cfg[2] = m->nchunks;
     cfg[3] = m->split_dyn_physics ? 1 : 0;
     cfg[4] = m->fold_geo ? 1 : 0;
-    cfg[5] = m->coupler_in_spectral ? 1 : 0;
+    cfg[5] = 1;  // (the coupling always rides in spectral_step_kernel)
     cfg[6] = m->phys_fp32;
     cfg[7] = m->stored32 ? 1 : 0;
     return SPD_OK;
@@ -1761,7 +1742,6 @@ int spd_model_get_option(spd_model_handle m, const char *name, int32_t *value) {
     if (!m || !name || !value) return m_fail(SPD_E_ARG, "spd_model_get_option: null argument");
     const std::string key(name);
     if (key == "diag_every_step") *value = m->diag_every_step ? 1 : 0;
-    else if (key == "coupler_in_spectral") *value = m->coupler_in_spectral ? 1 : 0;
     else if (key == "split_dyn") *value = m->split_dyn_physics ? 1 : 0;
     else if (key == "spectral_early") *value = m->spectral_early;
     else if (key == "member_groups") *value = m->nchunks;
@@ -1776,7 +1756,6 @@ int spd_model_set_option(spd_model_handle m, const char *name, int32_t value) {
     const std::string key(name);
     const bool flag = value == 0 || value == 1;
     if (key == "diag_every_step" && flag) m->diag_every_step = value != 0;
-    else if (key == "coupler_in_spectral" && flag) m->coupler_in_spectral = value != 0;
     else if (key == "split_dyn" && flag) m->split_dyn_physics = value != 0;
     else if (key == "spectral_early" && value >= -1 && value <= 1) m->spectral_early = value;
     else if (key == "member_groups" && value >= 1 && value <= 4) m->nchunks = value < m->M ? value : m->M;

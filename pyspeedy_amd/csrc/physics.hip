@@ -117,8 +117,9 @@ ColTables<R> col_tables(const DeviceTables &T) {
 
 }  // namespace
 
-// W = minimum waves per SIMD the register allocator must leave room for (launch-bounds hint): 2 by default (256 VGPRs, no
-// scratch), 1 with PYSPEEDY_AMD_PHYS_WAVES=1 for comparison; 3 and 4 spill heavily and were 1.5-2x slower.
+// W = minimum waves per SIMD the register allocator must leave room for (launch-bounds hint): 2 for fp64 (256 VGPRs, no
+// scratch; a 1-wave build has been no faster since the kernel requests its loads in batches, and 14 % slower from 16 members
+// up; 3 and 4 spill heavily and were 1.5-2x slower), 2 or 3 for fp32 (physics_waves32).
 //
 // FUSED: the kernel first runs the grid-point dynamics of the column (dyn_column.hpp, tendencies.f90:125-224) and keeps the
 // temperature / humidity tendencies it produces in registers -- the physics adds to exactly those -- so they are written
@@ -867,17 +868,6 @@ __global__ __launch_bounds__(kPhysThreads, W) void physics_kernel(spd_physics_ar
     if (a.clstr) stream_store(&a.clstr[o2], clstr);
 }
 
-// Launch-bounds variant of the fp64 kernels: 2 waves per SIMD (256 VGPRs, no scratch in the fused kernel).  The 1-wave build
-// (PYSPEEDY_AMD_PHYS_WAVES=1) exists for comparison: it was 2.8 % faster per step at 8 members before the kernel requested its
-// loads in batches and is equal since (14 % slower at 16 members and above); with -ffp-contract=on (Makefile) the two builds
-// give the same bits, which they did not while the back end was free to fuse across statements.
-static int physics_waves(int) {
-    static const int waves = [] {
-        const char *e = getenv("PYSPEEDY_AMD_PHYS_WAVES");
-        return e ? atoi(e) : 2;
-    }();
-    return waves;
-}
 // launch-bounds variant of the fp32 kernels (waves per SIMD the register allocator leaves room for: 2 or 3; a 4-wave build
 // spilled 368 bytes per lane and was 40 % slower): profiles/r02_cfg5_fp32_vs_fp64.txt.  By the size of the launch since round 4
 // (profiles/r04_cfg5_fp32_storage.txt): the 3-wave build (168 VGPRs, 100 bytes of scratch) wins when the launch brings more than
@@ -913,7 +903,6 @@ hipError_t run_physics(const DeviceTables &T, const spd_physics_args &a, int nme
             default: return launch_physics<3, false, false, float>(T, a, 0, nmembers, mp, md, 1, s);
         }
     }
-    if (physics_waves(nmembers) == 1) return launch_physics<1, false, false, double>(T, a, 0, nmembers, mp, md, 1, s);
     return launch_physics<2, false, false, double>(T, a, 0, nmembers, mp, md, 1, s);
 }
 
@@ -939,7 +928,6 @@ hipError_t run_dyn_physics(const ModelPtrs &P, const DynDeviceTables &D, const D
         }
     }
     if (a.sppt_pattern) return launch_physics<2, true, true, double>(T, a, first, nmembers, P, D, diag, s);
-    if (physics_waves(nmembers) == 1) return launch_physics<1, true, false, double>(T, a, first, nmembers, P, D, diag, s);
     return launch_physics<2, true, false, double>(T, a, first, nmembers, P, D, diag, s);
 }
 

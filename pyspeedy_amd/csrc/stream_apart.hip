@@ -55,8 +55,7 @@ hipError_t sleep_time(SleepEvents &ev, hipStream_t a, hipStream_t b, double *sec
 }  // namespace
 
 hipError_t create_stream_apart(hipStream_t *out, const hipStream_t *others, int n_others, unsigned flags, bool *apart) {
-    static const int mode = getenv("PYSPEEDY_AMD_STREAMS_APART") ? atoi(getenv("PYSPEEDY_AMD_STREAMS_APART")) : 1;  // 0: off, 2: report
-    const bool measure = mode != 0;
+    static const bool report = getenv("PYSPEEDY_AMD_STREAMS_APART") && atoi(getenv("PYSPEEDY_AMD_STREAMS_APART")) == 2;
     hipStream_t cand = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&cand, flags);
     if (e != hipSuccess) return e;
@@ -64,8 +63,8 @@ hipError_t create_stream_apart(hipStream_t *out, const hipStream_t *others, int 
     hipStream_t rejected[kApartTries];
     int n_rejected = 0;
     SleepEvents ev;
-    if (measure && n_others > 0) e = ev.create();
-    if (measure && n_others > 0 && e == hipSuccess) {
+    if (n_others > 0) e = ev.create();
+    if (n_others > 0 && e == hipSuccess) {
         for (int attempt = 0;; ++attempt) {
             double alone = 0.0;
             e = sleep_time(ev, cand, nullptr, &alone);  // (also the first launch on the stream: its queue exists from here on)
@@ -77,14 +76,14 @@ hipError_t create_stream_apart(hipStream_t *out, const hipStream_t *others, int 
                 if (hipStreamQuery(others[i]) != hipSuccess) {  // busy: it cannot be measured now (and is not made to wait)
                     (void)hipGetLastError();
                     all_measured = false;  // ... so nothing is claimed about it: the verdict below is "not known to be apart"
-                    if (mode == 2)
+                    if (report)
                         std::fprintf(stderr, "create_stream_apart: attempt %d, against stream %d of %d: busy, not measured\n", attempt, i, n_others);
                     continue;
                 }
                 double both = 0.0;
                 e = sleep_time(ev, cand, others[i], &both);
                 ok = both < 1.5 * alone;
-                if (mode == 2)
+                if (report)
                     std::fprintf(stderr, "create_stream_apart: attempt %d, against stream %d of %d: alone %.1f us, both %.1f us -> %s\n", attempt, i,
                                  n_others, alone * 1e6, both * 1e6, ok ? "side by side" : "one queue");
             }
@@ -103,7 +102,7 @@ hipError_t create_stream_apart(hipStream_t *out, const hipStream_t *others, int 
         if (cand) (void)hipStreamDestroy(cand);
         return e;
     }
-    if (apart) *apart = ok && all_measured && (measure || n_others == 0);  // (side by side with ALL of them, and measured to be)
+    if (apart) *apart = ok && all_measured;  // (side by side with ALL of them, and measured to be)
     *out = cand;
     return hipSuccess;
 }

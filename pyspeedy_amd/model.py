@@ -263,7 +263,8 @@ class EnsembleModel:
         return reserved.value, used.value
 
     def config(self):
-        """How the step is configured: dict(inv_per_member, diag_every_step, chunks, split_dyn) -- spd_model_get_config."""
+        """How the step is configured: dict(inv_per_member, diag_every_step, chunks, split_dyn, ...) -- spd_model_get_config.
+        The land / sea-ice coupling always rides in spectral_step_kernel: its key is always True."""
         cfg = (C.c_int32 * 8)()
         check(self._lib.spd_model_get_config(self._m, cfg), "spd_model_get_config")
         created, apart = C.c_int32(0), C.c_int32(1)
@@ -282,8 +283,8 @@ class EnsembleModel:
                     block_members=block.value, rounds=rounds)
 
     def set_option(self, name, value):
-        """A launch-plan switch of the live model by name (spd_model_set_option: diag_every_step, coupler_in_spectral,
-        spectral_early, split_dyn, member_groups, block_members, physics_storage32); none of them changes the state a step leaves behind.
+        """A launch-plan switch of the live model by name (spd_model_set_option: diag_every_step, spectral_early, split_dyn,
+        member_groups, block_members, physics_storage32); none of them changes the state a step leaves behind.
         ValueError for an unknown name."""
         rc = self._lib.spd_model_set_option(self._m, name.encode(), int(value))
         if rc == _lib.SPD_E_ARG:

@@ -1,7 +1,7 @@
-"""Kernel variants that are chosen once per process (launch-bounds builds of the column kernel) must give the same bits: a
-member's trajectory must not depend on which variant stepped it.  The device code is built with -ffp-contract=on for exactly
-that (csrc/Makefile); with the compiler's default the 1- and 2-wave builds of the column kernel differed in 35 of 92 registry
-variables after 40 steps.  Each variant runs in a process of its own (tests/dump_state.py)."""
+"""Kernel variants that are chosen once per process (launch-bounds builds and launch plans of the column kernel) must give the
+same bits: a member's trajectory must not depend on which variant stepped it.  The device code is built with -ffp-contract=on
+for exactly that (csrc/Makefile); with the compiler's default two launch-bounds builds of the column kernel differed in 35 of
+92 registry variables after 40 steps.  Each variant runs in a process of its own (tests/dump_state.py)."""
 import os
 import subprocess
 import sys
@@ -21,15 +21,12 @@ def _state(tmp_path, tag, **env):
 
 
 @pytest.mark.gpu
-def test_launch_bounds_builds_of_the_column_kernel_agree_bitwise(tmp_path):
-    a = _state(tmp_path, "w2", PYSPEEDY_AMD_PHYS_WAVES="2")
-    b = _state(tmp_path, "w1", PYSPEEDY_AMD_PHYS_WAVES="1")
-    c = _state(tmp_path, "split", PYSPEEDY_AMD_SPLIT_DYN="1")
+def test_fused_and_split_column_launches_agree_bitwise(tmp_path):
+    a = _state(tmp_path, "fused")
+    b = _state(tmp_path, "split", PYSPEEDY_AMD_SPLIT_DYN="1")
     assert len(a.files) > 80
-    for n in a.files:
-        assert np.array_equal(a[n], b[n]), ("1-wave build", n)
     # separate dynamics / physics launches write the dynamics' tendencies to memory and read them back: same values
-    differing = [n for n in a.files if not np.array_equal(a[n], c[n])]
+    differing = [n for n in a.files if not np.array_equal(a[n], b[n])]
     assert not differing, ("split launches", differing[:5])
 
 

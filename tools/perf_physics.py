@@ -24,4 +24,4 @@ for sw in (True, False):
     a.record()
     for _ in range(20): phys(fields, tend, forcing, st, sw, 0.3)
     b.record(); torch.cuda.synchronize()
-    print("waves=%s M=%d sw=%d  %.1f us/launch  %.3f ns/column" % (os.environ.get("PYSPEEDY_AMD_PHYS_WAVES", "1"), M, sw, a.elapsed_time(b) / 20 * 1e3, a.elapsed_time(b) / 20 * 1e6 / (M * 4608)))
+    print("M=%d sw=%d  %.1f us/launch  %.3f ns/column" % (M, sw, a.elapsed_time(b) / 20 * 1e3, a.elapsed_time(b) / 20 * 1e6 / (M * 4608)))

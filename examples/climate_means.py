@@ -5,11 +5,12 @@ Every member gets the same boundary fields and a tiny random change of its grid-
 temperature and precipitation every `--every` steps inside its own multi-step calls (EnsembleModel.stats_*: nothing is copied to
 the host while a month runs); each call ends at a month boundary, where the script reads the month's statistics and starts the
 next averaging period.  It prints zonal means per month, ensemble mean and spread (the standard deviation over the members of
-their monthly means), for a few latitudes.
+their monthly means), for a few latitudes, and -- from the 500 hPa height and the mean sea-level pressure the model interpolates
+on the GPU at every sample (EnsembleModel.plev_configure) -- the time mean and standard deviation of Z500 and mslp.
 
     python examples/climate_means.py [--members 16] [--months 2] [--every 9] [--start 1982-01] [--noise 0.01]
 
-API surface used: EnsembleModel.stats_configure / stats_mean / stats_ensemble / stats_reset, run_checked (the reference's range
+API surface used: EnsembleModel.plev_configure, stats_configure / stats_mean / stats_var / stats_ensemble / stats_reset, run_checked (the reference's range
 check of every step, recorded on the device), device_view + grid2spectral for the perturbation.
 """
 import argparse
@@ -62,7 +63,8 @@ def main():
 
     lat = np.degrees(sp.table("radang"))  # Gaussian latitudes, south to north (j = 0 southernmost)
     rows = list(range(2, 48, 5))
-    model.stats_configure(["t_grid", "precnv", "precls"], args.every, variance=False)
+    model.plev_configure([500.0])  # hPa: Z500 and the mean sea-level pressure are interpolated on the GPU at every sample
+    model.stats_configure(["t_grid", "precnv", "precls", "z_plev", "mslp"], args.every, variance=True)
     for _ in range(args.months):
         steps = calendar.monthrange(year, month)[1] * 36
         failed, _ = model.run_checked(steps)  # one device call for the whole month
@@ -80,6 +82,11 @@ def main():
         for j in rows:
             print("%6.1f  %8.2f (%8.2e)    %8.2f (%8.2e)    %8.4f (%8.2e)" % (
                 lat[j], te[7, j], tz[:, 7, j].std(ddof=1), te[3, j], tz[:, 3, j].std(ddof=1), pz[:, j].mean(), pz[:, j].std(ddof=1)))
+        # storm tracks and stationary waves: time mean and standard deviation of Z500 and mslp, and the members' spread of Z500
+        z_mean, z_std, z_spread = model.stats_mean("z_plev"), model.stats_var("z_plev").sqrt(), model.stats_ensemble("z_plev")[1]
+        p_mean, p_std = model.stats_mean("mslp") / 100.0, model.stats_var("mslp").sqrt() / 100.0
+        print("   Z500 [m]: mean %.1f, time std %.1f (largest %.1f), ensemble spread of the mean %.2e;  mslp [hPa]: mean %.2f, time std %.2f"
+              % (float(z_mean.mean()), float(z_std.mean()), float(z_std.max()), float(z_spread.mean()), float(p_mean.mean()), float(p_std.mean())))
         model.stats_reset()
         month += 1
         if month == 13:

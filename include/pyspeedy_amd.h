@@ -368,7 +368,8 @@ int spd_model_export_pack(spd_model_handle m, const char *name, int first, int c
                           void *stream);
 /* Time-mean statistics of grid-space fields, accumulated on the device inside spd_model_step / spd_model_step_checked_begin calls
  * of any length: per member and grid point the number of samples, the mean and (optionally) the unbiased time variance, fp64
- * (Welford's update).  Variables: any of u_grid, v_grid, t_grid, q_grid, phi_grid (kx levels), ps_grid, precnv, precls, in the
+ * (Welford's update).  Variables: any of u_grid, v_grid, t_grid, q_grid, phi_grid (kx levels), ps_grid, precnv, precls (and the
+ * pressure-level variables of spd_model_plev_* below), in the
  * units and layout spd_model_spectral2grid + spd_model_get give (q kg/kg, phi m, ps Pa; precnv / precls as the column physics
  * stores them).  A sample is taken after every step that leaves the model's absolute step counter at a multiple of `every` --
  * whatever way the host cuts its calls -- and equals what spd_model_spectral2grid would give if the call had ended there.
@@ -396,6 +397,36 @@ int spd_model_stats_samples(spd_model_handle m);
 int spd_model_stats_read(spd_model_handle m, const char *name, int kind, int first, int count, void *dst_device, size_t dst_bytes,
                          void *stream);
 int spd_model_stats_ensemble(spd_model_handle m, const char *name, int kind, void *dst_device, size_t dst_bytes, void *stream);
+/* Pressure-level fields and mean sea-level pressure, computed on the device from the sigma-level grid fields in export units
+ * (what spd_model_spectral2grid leaves: T in K, u, v in m/s, q in kg/kg, phi_grid in m, ps_grid in Pa).  Target pressures p_j in
+ * Pa (the Python layer speaks hPa), at most 32, strictly positive, strictly increasing or strictly decreasing; results keep the
+ * caller's order.  Per member and column, with s = ln(p_j / ps) and the full levels at sigl[k] = ln(fsg[k]) (k = 0 top ... 7):
+ *   inside  (sigl[0] <= s <= sigl[7])  X[k] + w (X[k+1] - X[k]), w = (s - sigl[k]) / (sigl[k+1] - sigl[k]): linear in ln p
+ *   above   (s < sigl[0])              u, v, T, q of level 0; Z = Z[0] + (R/g) T[0] (sigl[0] - s)        (isothermal)
+ *   below   (s > sigl[7])              u, v, q of level 7; T = T[7] exp(kappa (s - sigl[7])), Z = Z[7] - (T - T[7]) / gamma,
+ *                                      kappa = R gamma / g                               (constant lapse rate, hydrostatic)
+ *   mslp    ps (1 + gamma z_s / T_s)^(g / (R gamma)), T_s = T[7] exp(-kappa sigl[7]), z_s = phis0 / g
+ * with the library's R, g and gamma = 6 K/km.  Points under the ground (p_j > ps) are extrapolated like any other point below
+ * level 7: they are NOT masked; ps_grid tells which they are.  Names: u_plev, v_plev, t_plev, q_plev, z_plev (n levels), mslp.
+ * They are derived fields, not state: spd_model_get / _set, restarts and spd_model_copy_member do not know them.
+ *   _configure  sets the target levels (n = 0 clears them; host only).  SPD_E_ARG for more than 32, a non-positive or unsorted
+ *               level, and while statistics of a pressure-level variable are configured.
+ *   _levels     the configured levels into out[0 .. cap); returns their number.
+ *   _compute    members [first, first + count): with refresh = 1 first spd_model_spectral2grid of those members; with
+ *               refresh = 0 the grid arrays are taken as they are (the caller has just made that call, or has written fields of
+ *               its own there).  Then one kernel from u_grid ... ps_grid and phis0 into the result arrays, which are allocated
+ *               the first time a variable is asked for.  n_names = 0: all six.  The spectral state is not touched.
+ *   _read       a computed result as fp64 into dst_device[count][n][48][96] (mslp: [count][48][96]), device to device,
+ *               stream-ordered.
+ * spd_model_stats_configure takes the six names next to its own once levels are configured: a sample then also transforms T, phi
+ * and ln ps where a pressure-level variable needs them, and the pressure-level kernel runs on the group's stream between the
+ * transforms and the accumulation.  spd_model_stats_read / _ensemble give [count][n][48][96] / [n][48][96] for them. */
+int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n);
+int spd_model_plev_levels(spd_model_handle m, double *out, int cap);
+int spd_model_plev_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, int refresh,
+                           void *stream);
+int spd_model_plev_read(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes,
+                        void *stream);
 /* modelstate_init_sst_anom (speedy_driver.f90.j2:225-237): sst_anom(ix, il, 0:n_months+1) per member, zero-filled */
 int spd_model_init_sst_anom(spd_model_handle m, int n_months);
 /* Stochastically perturbed parametrisation tendencies (sppt.f90; compile-time off and non-functional in the reference:

@@ -7,6 +7,7 @@
 !!   modelstate_init -> spd_create + spd_model_create     set_<v> / get_<v> -> spd_model_set / spd_model_get
 !!   init            -> spd_model_init                    step / parallel_step -> spd_model_step
 !!   check           -> spd_model_check                   transform_spectral2grid ... -> spd_model_spectral2grid ...
+!! and, without a counterpart there: time statistics on the device (spd_model_stats_*) and pressure-level fields (spd_model_plev_*)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -169,6 +170,35 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model, dst_device, stream
             character(kind=c_char), intent(in) :: name(*)
             integer(c_int), value :: kind
+            integer(c_size_t), value :: dst_bytes
+        end function
+        ! pressure-level fields and mean sea-level pressure (pyspeedy_amd.h: spd_model_plev_*).  levels_pa: Pa; names as for the
+        ! statistics ("z_plev"//c_null_char, ...; n_names = 0: all six); refresh = 1: spd_model_spectral2grid first
+        integer(c_int) function spd_model_plev_configure(model, levels_pa, n) bind(C, name="spd_model_plev_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model
+            real(c_double), intent(in) :: levels_pa(*)
+            integer(c_int), value :: n
+        end function
+        integer(c_int) function spd_model_plev_levels(model, out, cap) bind(C, name="spd_model_plev_levels")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model
+            real(c_double), intent(out) :: out(*)
+            integer(c_int), value :: cap
+        end function
+        integer(c_int) function spd_model_plev_compute(model, names, n_names, first, count, refresh, stream) &
+                bind(C, name="spd_model_plev_compute")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, stream
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), value :: n_names, first, count, refresh
+        end function
+        integer(c_int) function spd_model_plev_read(model, name, first, count, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_plev_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: first, count
             integer(c_size_t), value :: dst_bytes
         end function
         integer(c_int) function spd_model_current_step(model) bind(C, name="spd_model_current_step")

@@ -25,6 +25,7 @@
 #include "bounded_call.hpp"
 #include "launch_events.hpp"
 #include "sppt_point.hpp"
+#include "plev.hpp"
 #include "stats.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
@@ -224,7 +225,10 @@ struct spd_model {
             size_t offset;  // doubles from `mean` / `m2` to member 0 of the variable
         };
         bool on = false, variance = false, valid = true, uv = false, precip = false;
-        int every = 1, slab_fields = 0, nplanes = 0;
+        // slab_fields: planes of a member in the slab; the first xf_fields of them are written by the export transforms, the
+        // others (pressure-level variables only) by the pressure-level kernel from those
+        int every = 1, slab_fields = 0, xf_fields = 0, nplanes = 0;
+        PlevArgs plev{};  // (plev.mask != 0: a pressure-level variable is sampled)
         long long samples = 0;
         std::string invalid_why;
         std::vector<Var> vars;
@@ -233,6 +237,15 @@ struct spd_model {
         FieldDesc *table[2] = {nullptr, nullptr};
         StatsPlane *planes = nullptr;
     } stats;
+    // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
+    // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
+    struct Plev {
+        int n = 0;
+        double levels[kPlevMaxLevels] = {}, lnp[kPlevMaxLevels] = {};
+        double *out[PLEV_NVARS] = {};
+        int cap[PLEV_NVARS] = {};     // levels the allocation holds
+        bool have[PLEV_NVARS] = {};   // computed since the levels were configured
+    } plev;
 };
 
 namespace spd {
@@ -1949,9 +1962,17 @@ struct StatsCatalogueEntry {
     const char *name;
     int levels, unit;  // unit: as StatsPlane::unit
 };
-// ids 0 ... 5: from the spectral state through the export transforms; 6, 7: the column kernel's precipitation outputs
+// ids 0 ... 5: from the spectral state through the export transforms; 6, 7: the column kernel's precipitation outputs;
+// 8 ... 13: the pressure-level variables (kPlevFirst + PlevVar; levels: the configured target levels, mslp one), written into the
+// slab in export units by the pressure-level kernel
 constexpr StatsCatalogueEntry kStatsCatalogue[] = {{"u_grid", KX, 0},   {"v_grid", KX, 0}, {"t_grid", KX, 0}, {"q_grid", KX, 1},
-                                                   {"phi_grid", KX, 2}, {"ps_grid", 1, 3}, {"precnv", 1, 0}, {"precls", 1, 0}};
+                                                   {"phi_grid", KX, 2}, {"ps_grid", 1, 3}, {"precnv", 1, 0}, {"precls", 1, 0},
+                                                   {"u_plev", 0, 0},    {"v_plev", 0, 0},  {"t_plev", 0, 0}, {"q_plev", 0, 0},
+                                                   {"z_plev", 0, 0},    {"mslp", 1, 0}};
+constexpr int kPlevFirst = 8;
+// sigma-level inputs (catalogue ids 0 ... 5, as bits) of each pressure-level variable: ps always; T with Z (both extrapolations)
+constexpr int kPlevNeeds[PLEV_NVARS] = {1 << 0 | 1 << 5, 1 << 1 | 1 << 5, 1 << 2 | 1 << 5, 1 << 3 | 1 << 5, 1 << 2 | 1 << 4 | 1 << 5,
+                                        1 << 2 | 1 << 5};
 constexpr int kStatsCatalogueSize = sizeof(kStatsCatalogue) / sizeof(kStatsCatalogue[0]);
 static int stats_id(const char *name) {
     for (int v = 0; v < kStatsCatalogueSize; ++v)
@@ -1968,8 +1989,13 @@ static hipError_t stats_sample(spd_model *m, int first, int count, long long n, 
     const size_t S = NSPEC * C, half = static_cast<size_t>(m->M) * 16, off = static_cast<size_t>(first) * 16;
     hipError_t e = hipSuccess;
     if (st.uv) e = run_vort2vel(T, m->P.vor + off * S, m->P.div + off * S, m->P.sv + off * S, m->P.sv + (half + off) * S, count * 16, s);
-    if (e == hipSuccess && st.slab_fields > 0)
-        e = run_spec2grid_table(T, st.table[m->phi_cur] + static_cast<size_t>(first) * st.slab_fields, count * st.slab_fields, s);
+    if (e == hipSuccess && st.xf_fields > 0)
+        e = run_spec2grid_table(T, st.table[m->phi_cur] + static_cast<size_t>(first) * st.xf_fields, count * st.xf_fields, s);
+    if (e == hipSuccess && st.plev.mask) {  // slab -> further slab planes, in export units
+        PlevArgs a = st.plev;
+        a.first = first;
+        e = run_plev(a, count, s);
+    }
     if (e == hipSuccess) e = run_stats_accumulate(st.planes, st.nplanes, st.slab, st.slab_fields, first, count, n, m->stored32 ? 1 : 0, s);
     return e;
 }
@@ -1983,7 +2009,8 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
         const int id = names[k] ? stats_id(names[k]) : -1;
         if (id < 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls)");
+                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
+                                         "q_plev, z_plev, mslp)");
         if (std::find(ids.begin(), ids.end(), id) != ids.end())
             return m_fail(SPD_E_ARG, std::string(who) + ": variable '" + names[k] + "' named twice");
         ids.push_back(id);
@@ -1992,6 +2019,9 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
     if (int rc = usable(m, who)) return rc;
     if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    for (size_t k = 0; k < ids.size(); ++k)
+        if (ids[k] >= kPlevFirst && m->plev.n == 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
     M_HIP(hipSetDevice(m->ctx->device));
     M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
     spd_model::Stats &st = m->stats;
@@ -2003,19 +2033,36 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     next.variance = with_variance != 0;
     const size_t M = static_cast<size_t>(m->M);
     size_t planes = 0;
+    // what the export transforms write into the slab, in slab order: the sigma-level variables asked for, then those only a
+    // pressure-level variable needs; xf_at[id]: first slab plane of variable id (-1: not transformed)
+    std::vector<int> xf;
+    int xf_at[6] = {-1, -1, -1, -1, -1, -1}, needs = 0, plev_planes = 0;
+    auto levels_of = [&](int id) { return id >= kPlevFirst && id != kPlevFirst + PLEV_MSLP ? m->plev.n : kStatsCatalogue[id].levels; };
     for (int id : ids) {
-        next.vars.push_back({id, kStatsCatalogue[id].levels, M * planes * NG});
-        planes += static_cast<size_t>(kStatsCatalogue[id].levels);
-        if (id < 6) next.slab_fields += kStatsCatalogue[id].levels;
-        next.uv = next.uv || id < 2;
-        next.precip = next.precip || id >= 6;
+        next.vars.push_back({id, levels_of(id), M * planes * NG});
+        planes += static_cast<size_t>(levels_of(id));
+        if (id < 6) xf.push_back(id);
+        next.precip = next.precip || id == 6 || id == 7;
+        if (id >= kPlevFirst) {
+            next.plev.mask |= 1 << (id - kPlevFirst);
+            needs |= kPlevNeeds[id - kPlevFirst];
+            plev_planes += levels_of(id);
+        }
     }
+    for (int id = 0; id < 6; ++id)
+        if ((needs >> id & 1) && std::find(xf.begin(), xf.end(), id) == xf.end()) xf.push_back(id);
+    for (int id : xf) {
+        xf_at[id] = next.xf_fields;
+        next.xf_fields += kStatsCatalogue[id].levels;
+        next.uv = next.uv || id < 2;
+    }
+    next.slab_fields = next.xf_fields + plev_planes;
     next.nplanes = static_cast<int>(planes);
     // one allocation: mean | m2 | slab | tables[2] | plane descriptors
     constexpr size_t kAlign = 256;
     auto up = [](size_t b) { return (b + kAlign - 1) / kAlign * kAlign; };
     const size_t acc = up(M * planes * NG * sizeof(double)), slab = up(M * next.slab_fields * NG * sizeof(double)),
-                 table = up(M * next.slab_fields * sizeof(FieldDesc)), desc = up(planes * sizeof(StatsPlane));
+                 table = up(M * next.xf_fields * sizeof(FieldDesc)), desc = up(planes * sizeof(StatsPlane));
     const size_t total = acc * (next.variance ? 2 : 1) + slab + 2 * table + desc;
     void *p = nullptr;
     M_HIP(hipMalloc(&p, total));
@@ -2033,14 +2080,14 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     const size_t half = M * 16;
     std::vector<FieldDesc> host_table[2];
     for (int par = 0; par < 2; ++par) {
-        host_table[par].reserve(M * next.slab_fields);
+        host_table[par].reserve(M * next.xf_fields);
         for (size_t i = 0; i < M; ++i) {
             const size_t w = i * 8, s1 = i * 16;
             size_t j = 0;
-            for (const auto &v : next.vars) {
-                for (int k = 0; k < v.levels && v.id < 6; ++k, ++j) {
+            for (const int id : xf) {
+                for (int k = 0; k < kStatsCatalogue[id].levels; ++k, ++j) {
                     double *dst = next.slab + (i * next.slab_fields + j) * NG;
-                    switch (v.id) {
+                    switch (id) {
                         case 0: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
                         case 1: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
                         case 2: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
@@ -2053,11 +2100,32 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
         }
     }
     std::vector<StatsPlane> host_planes;
-    int slab_plane = 0;
+    int plev_plane = next.xf_fields;
+    if (next.plev.mask) {  // the pressure-level kernel of a sample: from the slab's transformed planes into its further planes
+        PlevArgs &a = next.plev;
+        const long stride = static_cast<long>(next.slab_fields) * NG;
+        for (int x = 0; x < 5; ++x) {
+            a.in[x] = xf_at[x] >= 0 ? next.slab + static_cast<size_t>(xf_at[x]) * NG : nullptr;
+            a.in_stride[x] = stride;
+        }
+        a.ps = next.slab + static_cast<size_t>(xf_at[5]) * NG;
+        a.ps_stride = stride;
+        a.phis0 = m->pa.phis0;
+        a.raw = 1;
+        a.n = m->plev.n;
+        std::copy(m->plev.lnp, m->plev.lnp + kPlevMaxLevels, a.lnp);
+    }
     for (const auto &v : next.vars)
         for (int k = 0; k < v.levels; ++k) {
             StatsPlane d{};
-            d.slab_plane = v.id < 6 ? slab_plane++ : -1;
+            if (v.id < 6) d.slab_plane = xf_at[v.id] + k;
+            else if (v.id >= kPlevFirst) {
+                if (k == 0) {
+                    next.plev.out[v.id - kPlevFirst] = next.slab + static_cast<size_t>(plev_plane) * NG;
+                    next.plev.out_stride[v.id - kPlevFirst] = static_cast<long>(next.slab_fields) * NG;
+                }
+                d.slab_plane = plev_plane++;
+            } else d.slab_plane = -1;
             d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
             d.unit = kStatsCatalogue[v.id].unit;
             d.mean = next.mean + v.offset + static_cast<size_t>(k) * NG;
@@ -2066,7 +2134,7 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
             host_planes.push_back(d);
         }
     hipError_t e = hipSuccess;
-    if (next.slab_fields > 0) {
+    if (next.xf_fields > 0) {
         e = hipMemcpy(next.table[0], host_table[0].data(), host_table[0].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
         if (e == hipSuccess)
             e = hipMemcpy(next.table[1], host_table[1].data(), host_table[1].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
@@ -2156,6 +2224,116 @@ int spd_model_stats_ensemble(spd_model_handle m, const char *name, int kind, voi
     const hipError_t e = run_stats_ensemble(m->stats.mean + v->offset, m->M, static_cast<long>(per), kind == SPD_STATS_STD ? 1 : 0,
                                             static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// pressure-level fields and mean sea-level pressure (spd_model_plev_*; kernel: plev.hip)
+// ---------------------------------------------------------------------------------------------------------------
+static int plev_id(const char *name) {
+    const int id = name ? stats_id(name) : -1;
+    return id >= kPlevFirst ? id - kPlevFirst : -1;
+}
+
+int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n) {
+    const char *who = "spd_model_plev_configure";
+    if (n < 0 || (n > 0 && !levels_pa)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of levels");
+    if (n > kPlevMaxLevels) return m_fail(SPD_E_ARG, std::string(who) + ": at most " + std::to_string(kPlevMaxLevels) + " levels");
+    for (int j = 0; j < n; ++j)
+        if (!(levels_pa[j] > 0.0) || !std::isfinite(levels_pa[j]))
+            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(j) + " is not a positive pressure (Pa)");
+    bool up = true, down = true;
+    for (int j = 1; j < n; ++j) {
+        up = up && levels_pa[j] > levels_pa[j - 1];
+        down = down && levels_pa[j] < levels_pa[j - 1];
+    }
+    if (!up && !down) return m_fail(SPD_E_ARG, std::string(who) + ": the levels must be strictly increasing or strictly decreasing");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->stats.on && m->stats.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": statistics of a pressure-level variable are configured; switch them off first "
+                                                    "(spd_model_stats_configure)");
+    spd_model::Plev &pl = m->plev;
+    pl.n = n;
+    for (int j = 0; j < kPlevMaxLevels; ++j) {
+        pl.levels[j] = j < n ? levels_pa[j] : 0.0;
+        pl.lnp[j] = j < n ? std::log(levels_pa[j]) : 0.0;
+    }
+    for (bool &h : pl.have) h = false;  // (results of the previous levels are not handed out under the new ones)
+    return SPD_OK;
+}
+
+int spd_model_plev_levels(spd_model_handle m, double *out, int cap) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_plev_levels: null model");
+    if (cap < 0 || (cap > 0 && !out)) return m_fail(SPD_E_ARG, "spd_model_plev_levels: bad destination");
+    for (int j = 0; j < m->plev.n && j < cap; ++j) out[j] = m->plev.levels[j];
+    return m->plev.n;
+}
+
+int spd_model_plev_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, int refresh, void *stream) {
+    const char *who = "spd_model_plev_compute";
+    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
+    int mask = n_names == 0 ? (1 << PLEV_NVARS) - 1 : 0;
+    for (int k = 0; k < n_names; ++k) {
+        const int id = plev_id(names[k]);
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
+                                         "' (u_plev, v_plev, t_plev, q_plev, z_plev, mslp)");
+        mask |= 1 << id;
+    }
+    if (int rc = member_range(m, first, count, who)) return rc;
+    spd_model::Plev &pl = m->plev;
+    if (pl.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target levels configured (spd_model_plev_configure)");
+    M_HIP(hipSetDevice(m->ctx->device));
+    const size_t M = static_cast<size_t>(m->M);
+    for (int v = 0; v < PLEV_NVARS; ++v) {
+        const int levels = v == PLEV_MSLP ? 1 : pl.n;
+        if (!(mask >> v & 1) || pl.cap[v] >= levels) continue;
+        if (int rc = dalloc(m, M * levels * NG, &pl.out[v])) return rc;
+        pl.cap[v] = levels;
+    }
+    if (count == 0) return SPD_OK;
+    if (refresh)
+        if (int rc = spd_model_spectral2grid(m, first, count, stream)) return rc;
+    PlevArgs a{};
+    const double *in[5] = {m->u_grid, m->v_grid, m->t_grid, m->q_grid, m->phi_grid};
+    for (int x = 0; x < 5; ++x) {
+        a.in[x] = in[x];
+        a.in_stride[x] = static_cast<long>(KX) * NG;
+    }
+    a.ps = m->ps_grid;
+    a.ps_stride = NG;
+    a.phis0 = m->pa.phis0;
+    for (int v = 0; v < PLEV_NVARS; ++v) {
+        a.out[v] = pl.out[v];
+        a.out_stride[v] = static_cast<long>(v == PLEV_MSLP ? 1 : pl.n) * NG;
+    }
+    a.mask = mask;
+    a.raw = 0;
+    a.n = pl.n;
+    a.first = first;
+    std::copy(pl.lnp, pl.lnp + kPlevMaxLevels, a.lnp);
+    const hipError_t e = run_plev(a, count, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    for (int v = 0; v < PLEV_NVARS; ++v) pl.have[v] = pl.have[v] || (mask >> v & 1);
+    return SPD_OK;
+}
+
+int spd_model_plev_read(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_plev_read";
+    if (!name || !dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    const int v = plev_id(name);
+    if (v < 0) return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + name + "' (u_plev, v_plev, t_plev, q_plev, z_plev, mslp)");
+    if (int rc = member_range(m, first, count, who)) return rc;
+    const spd_model::Plev &pl = m->plev;
+    if (pl.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target levels configured (spd_model_plev_configure)");
+    if (!pl.have[v]) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' has not been computed at these levels (spd_model_plev_compute)");
+    const size_t per = static_cast<size_t>(v == PLEV_MSLP ? 1 : pl.n) * NG, need = static_cast<size_t>(count) * per * sizeof(double);
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (count == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipMemcpyAsync(dst_device, pl.out[v] + static_cast<size_t>(first) * per, need, hipMemcpyDeviceToDevice,
+                         static_cast<hipStream_t>(stream)));
     return SPD_OK;
 }
 

@@ -228,7 +228,7 @@ HostTables::HostTables() {
 // dynamics tables
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-constexpr double kGamma = 6.0f, kHscale = 7.5f, kHshum = 2.5f, kThd = 2.4f, kThdd = 2.4f, kThds = 12.0f, kAlph = 0.5f;
+constexpr double kGamma = phc::gamma_km, kHscale = 7.5f, kHshum = 2.5f, kThd = 2.4f, kThdd = 2.4f, kThds = 12.0f, kAlph = 0.5f;
 
 // LU decomposition with implicit scaling and partial pivoting, then column-by-column back substitution:
 // the algorithm of matrix_inversion.f90 (Numerical Recipes ludcmp/lubksb), n = 8.

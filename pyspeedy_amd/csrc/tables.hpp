@@ -23,6 +23,7 @@ constexpr double rearth = 6.371e+6f, omega = 7.292e-05f, grav = 9.81f, p0 = 1.e+
 constexpr double akap = 2.0f / 7.0f;  // evaluated in fp32
 constexpr double rgas = akap * cp;
 constexpr double alhc = 2501.0f, alhs = 2801.0f, sbc = 5.67e-8f;
+constexpr double gamma_km = 6.0f;  // reference lapse rate, K/km (physical_constants.f90:32; kGamma of tables.cpp)
 }  // namespace phc
 
 struct HostTables {

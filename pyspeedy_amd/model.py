@@ -312,7 +312,8 @@ class EnsembleModel:
         return ms.value, n.value, f.value
 
     # ---- time-mean statistics accumulated on the device (spd_model_stats_*, include/pyspeedy_amd.h) ---------------------
-    STATS_VARIABLES = ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid", "ps_grid", "precnv", "precls")
+    STATS_VARIABLES = ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid", "ps_grid", "precnv", "precls",
+                       "u_plev", "v_plev", "t_plev", "q_plev", "z_plev", "mslp")  # (the last six: after plev_configure)
 
     def stats_configure(self, variables, every, variance=True):
         """Sample `variables` (any of STATS_VARIABLES) after every step that leaves current_step at a multiple of `every`, inside
@@ -335,6 +336,8 @@ class EnsembleModel:
         return int(n)
 
     def _stats_shape(self, name):
+        if name in self.PLEV_VARIABLES[:5]:
+            return (len(self.plev_levels), 48, 96)
         levels = 8 if name in ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid") else 1
         return (levels, 48, 96) if levels > 1 else (48, 96)
 
@@ -364,6 +367,47 @@ class EnsembleModel:
                                                          self._stream()), "spd_model_stats_ensemble(%s)" % name)
             out.append(t)
         return tuple(out)
+
+    # ---- pressure-level fields and mean sea-level pressure (spd_model_plev_*, include/pyspeedy_amd.h) -------------------
+    PLEV_VARIABLES = ("u_plev", "v_plev", "t_plev", "q_plev", "z_plev", "mslp")
+
+    def plev_configure(self, levels_hpa):
+        """Set the target pressure levels, in hPa (the C ABI speaks Pa): at most 32, positive, strictly increasing or strictly
+        decreasing; results keep this order.  An empty list clears them.  Refused while statistics of a pressure-level variable
+        are configured."""
+        pa = [float(p) * 100.0 for p in levels_hpa]
+        arr = (C.c_double * max(len(pa), 1))(*pa)
+        check(self._lib.spd_model_plev_configure(self._m, arr, len(pa)), "spd_model_plev_configure")
+
+    @property
+    def plev_levels(self):
+        """The configured target levels in hPa (a tuple, the caller's order)."""
+        buf = (C.c_double * 32)()
+        n = self._lib.spd_model_plev_levels(self._m, buf, 32)
+        if n < 0:
+            check(n, "spd_model_plev_levels")
+        return tuple(buf[j] / 100.0 for j in range(n))
+
+    def plev(self, names=None, first=0, count=None, refresh=True):
+        """Pressure-level fields of members [first, first + count) at the configured levels: a dict of float64 tensors on the
+        model's device, [count][n][48][96] (u_plev, v_plev: m/s, t_plev: K, q_plev: kg/kg, z_plev: m) and [count][48][96] (mslp:
+        Pa); `names`: any of PLEV_VARIABLES, None = all.  Linear in ln p between the model's full levels, isothermal above the
+        top one, constant lapse rate (6 K/km) below the lowest.  Points under the ground (p > ps) are extrapolated like any other
+        point below the lowest level, not masked: compare with ps_grid to find them.  With `refresh` the grid arrays are first
+        brought up to date (spectral2grid() of those members); without, they are used as they are."""
+        names = list(self.PLEV_VARIABLES) if names is None else [str(v) for v in names]
+        first, count = self._range(first, count)
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        out = {}
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_plev_compute(self._m, arr, len(names), first, count, int(bool(refresh)), self._stream()),
+                  "spd_model_plev_compute")
+            for name in names:
+                t = torch.empty((count,) + self._stats_shape(name), dtype=torch.float64, device=self.sp.device)
+                check(self._lib.spd_model_plev_read(self._m, name.encode(), first, count, C.c_void_p(t.data_ptr()), t.numel() * 8,
+                                                    self._stream()), "spd_model_plev_read(%s)" % name)
+                out[name] = t
+        return out
 
     def set_flags(self, land_coupling_flag=True, sst_anomaly_coupling_flag=True, increase_co2=False):
         check(self._lib.spd_model_set_flags(self._m, int(land_coupling_flag), int(sst_anomaly_coupling_flag),

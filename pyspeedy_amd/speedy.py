@@ -404,11 +404,18 @@ class Speedy:
             raise RuntimeError(ERROR_CODES[code])
 
     # ---- export ----------------------------------------------------------------------------------------------
-    def to_dataframe(self, variables=None, packed=False, slot=0, buffers=None, wait=True):
+    def to_dataframe(self, variables=None, packed=False, slot=0, buffers=None, wait=True, pressure_levels=None):
         """Current model state as a Dataset following the export conventions of the reference (speedy.py:415-477).
         packed=True (extension, what XarrayExporter asks for): the data variables come as they go into a NetCDF-3 file -- float32,
         big-endian, narrowed and ordered on the GPU -- and alias a buffer that the next packed call with the same `slot` (of the same
-        `buffers` dict, when the caller brings its own) overwrites.  wait=False (packed only): see SpeedyEns.to_dataframe."""
+        `buffers` dict, when the caller brings its own) overwrites.  wait=False (packed only): see SpeedyEns.to_dataframe.
+        pressure_levels (extension; a list of hPa values, not with packed=True): see SpeedyEns.to_dataframe."""
+        if pressure_levels is not None:
+            if packed:
+                raise ValueError("pressure_levels cannot be combined with packed=True")
+            frame = self.to_dataframe(variables)
+            members = [self.member_id] if self.is_ensemble_member else None
+            return _add_pressure_levels(frame, [self._state_cnt], pressure_levels, members)
         variables = DEFAULT_OUTPUT_VARS if variables is None else variables
         if packed:
             for var in variables:
@@ -651,6 +658,26 @@ def _build_dataset(model, arrays, members, date, packed=False):
     return Dataset(data, coords)
 
 
+_PLEV_META = {"u_plev": ("eastward wind on pressure levels", "m/s"), "v_plev": ("northward wind on pressure levels", "m/s"),
+              "t_plev": ("air temperature on pressure levels", "K"), "q_plev": ("specific humidity on pressure levels", "kg/kg"),
+              "z_plev": ("geopotential height on pressure levels", "m"), "mslp": ("mean sea-level pressure", "Pa")}
+
+
+def _add_pressure_levels(frame, state_cnts, pressure_levels, members):
+    """`frame` (a Dataset of to_dataframe) with the `plev` coordinate and the six pressure-level variables of the containers"""
+    levels = [float(p) for p in pressure_levels]
+    arrays = _speedy.ensemble_plev_arrays(state_cnts, levels)
+    lead = ("time", "ens") if members is not None else ("time",)
+    for name, values in arrays.items():
+        values = values[None] if members is not None else values  # -> (time, ens, ...) or (time, ...)
+        dims = lead + (("plev",) if name != "mslp" else ()) + ("lat", "lon")
+        long_name, units = _PLEV_META[name]
+        frame.data_vars[name] = Variable(dims, values, {"long_name": long_name, "standard_name": name, "units": units})
+    frame.coords["plev"] = Variable(("plev",), np.array(levels, dtype=np.float32),
+                                    {"long_name": "pressure", "standard_name": "air_pressure", "units": "hPa", "positive": "down"})
+    return frame
+
+
 class PendingFrame:
     """A snapshot of an ensemble that is still on the GPU (SpeedyEns.snapshot_on_device): `resolve()` copies it out and returns the
     Dataset `to_dataframe` would have returned at the time it was taken; `nbytes` is what it holds on the device until then."""
@@ -714,12 +741,21 @@ class SpeedyEns:
             member.spectral2grid()
             member._initialized_bc = True
 
-    def to_dataframe(self, variables=None, packed=False, slot=0, buffers=None, wait=True):
+    def to_dataframe(self, variables=None, packed=False, slot=0, buffers=None, wait=True, pressure_levels=None):
         """All members along the `ens` dimension: one batched spectral -> grid conversion and one device-to-host copy per
         variable (the device layout [member][lev][lat][lon] is already the export order).  packed=True: see Speedy.to_dataframe;
         with wait=False (packed only) the Dataset comes back as soon as the transforms and pack kernels are enqueued and carries
         `ready`: its arrays hold the payload once `synchronize()` of every item of that list has returned -- which is also what
-        copies it out of the device (speedy_driver.ensemble_export_arrays; to be called from the thread that writes the file)."""
+        copies it out of the device (speedy_driver.ensemble_export_arrays; to be called from the thread that writes the file).
+        pressure_levels (extension): a list of pressures in hPa, strictly increasing or decreasing.  The Dataset then also carries
+        a `plev` coordinate (hPa, this order) and float32 u_plev, v_plev, t_plev, q_plev, z_plev on (time, ens, plev, lat, lon) and
+        mslp (Pa) on (time, ens, lat, lon), interpolated on the GPU (EnsembleModel.plev).  Points under the ground are
+        extrapolated, not masked: `ps` tells which they are.  Not with packed=True (ValueError)."""
+        if pressure_levels is not None:
+            if packed:
+                raise ValueError("pressure_levels cannot be combined with packed=True")
+            frame = self.to_dataframe(variables)
+            return _add_pressure_levels(frame, [m._state_cnt for m in self], pressure_levels, [m.member_id for m in self])
         variables = DEFAULT_OUTPUT_VARS if variables is None else variables
         for var in variables:
             _exportable(var)

@@ -397,6 +397,27 @@ def ensemble_grid_arrays(state_cnts, names, narrow=False):
     return out
 
 
+def ensemble_plev_arrays(state_cnts, levels_hpa):
+    """Extension: the pressure-level fields (EnsembleModel.plev: u_plev ... z_plev, mslp) of the given containers at `levels_hpa`,
+    computed per device model after its spectral2grid: dict name -> float32 array [member, (plev,) lat, lon] in the order of
+    `state_cnts` and of `levels_hpa`, narrowed on the GPU.  Sets the models' target levels (plev_configure) where they differ."""
+    import torch
+    levels = tuple(float(p) for p in levels_hpa)
+    order, groups = _group_by_model(state_cnts)
+    out = {}
+    for k in order:
+        model, positions, indices = groups[k]
+        if model.plev_levels != levels:
+            model.plev_configure(levels)
+        fields = model.plev()
+        for name, t in fields.items():
+            part = t.to(torch.float32).cpu().numpy()
+            if name not in out:
+                out[name] = np.empty((len(state_cnts),) + part.shape[1:], dtype=np.float32)
+            out[name][positions] = part[indices]
+    return out
+
+
 _export_stages = {}  # (device, slot) -> uint8 staging tensor on that device (grown on demand)
 _export_copy_streams = {}  # device -> the stream the copies to pinned memory of a packed export run on when the caller does not wait
 

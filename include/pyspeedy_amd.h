@@ -427,6 +427,42 @@ int spd_model_plev_compute(spd_model_handle m, const char *const *names, int n_n
                            void *stream);
 int spd_model_plev_read(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes,
                         void *stream);
+/* The tape: time series of fields recorded on the device inside spd_model_step / spd_model_step_checked_begin calls of any length.
+ * A ring buffer in device memory, per model, holds the last `capacity` samples of the chosen variables for every member; one
+ * sample is taken after every step that leaves the model's absolute step counter at a multiple of `every` (the statistics' rule),
+ * by each member group on its own stream behind its last launch of that step, so an output every few steps no longer ends the
+ * call.  Variables: the fourteen names of the statistics (the six pressure-level ones after spd_model_plev_configure), in export
+ * units.  A sample of u_grid ... ps_grid holds what spd_model_spectral2grid would leave in the grid arrays if the call ended at
+ * that step; of precnv / precls what the column physics stored at that step; of a pressure-level name what spd_model_plev_compute
+ * would give there.  Storage: SPD_TAPE_F64, those values; SPD_TAPE_F32, each rounded to the nearest float (half the memory: what
+ * the export writes).  Recording changes nothing of the run, and statistics and tape are independent: each has its own `every`,
+ * and on a step both sample each runs its own transforms.
+ *   _configure  allocates the ring (capacity x members x planes x 4608 elements, one hipMalloc of its own; synchronises the
+ *               device) and empties it; n_names = 0 switches the tape off and frees it.  SPD_E_ARG for an unknown or repeated name,
+ *               every < 1, capacity < 1, an unknown dtype, a pressure-level name before spd_model_plev_configure, or while a
+ *               checked call is in flight.  SPD_E_DEVICE with the number of bytes asked for when the allocation fails: the tape is
+ *               then off and the model as usable as before.  spd_model_plev_configure is refused while the tape holds a
+ *               pressure-level name.
+ *   _reset      empties the tape (host only, no device work).  spd_model_init does the same.
+ *   _info       taken: samples since the last reset; held = min(taken, capacity); any pointer may be NULL.
+ *   _times      rows[held][6] for the held samples, oldest first: the absolute step counter after the sampled step, then year,
+ *               month, day, hour, minute of the sampled state (host memory; kept on the host when the sample is issued).  Returns
+ *               the number of rows written (at most max_rows).
+ *   _read       members [first, first + count) and samples [t0, t0 + nt) of the held ones, oldest first, of one variable into
+ *               dst_device[count][nt][levels][48][96] ([count][nt][48][96] for ps_grid, precnv, precls, mslp) in the tape's dtype,
+ *               stream-ordered; dst_device must be 16-byte aligned.  SPD_E_SIZE when dst_bytes is too small.
+ * Reads fail (SPD_E_ARG, with the reason) while a checked call is in flight and after a checked call that reported a failed range
+ * check (the message names the member and the step): the tape stays invalid until _reset or spd_model_init.  Samples issued by
+ * unchecked calls on a stream are read behind them on the same stream.  spd_model_copy_member does not carry the tape, and the
+ * outer boundary (spd_parallel_step*) does not keep it across the models it merges and splits. */
+#define SPD_TAPE_F32 0
+#define SPD_TAPE_F64 1
+int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity, int dtype);
+int spd_model_tape_reset(spd_model_handle m);
+int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *dtype);
+int spd_model_tape_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_tape_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
+                        void *stream);
 /* modelstate_init_sst_anom (speedy_driver.f90.j2:225-237): sst_anom(ix, il, 0:n_months+1) per member, zero-filled */
 int spd_model_init_sst_anom(spd_model_handle m, int n_months);
 /* Stochastically perturbed parametrisation tendencies (sppt.f90; compile-time off and non-functional in the reference:

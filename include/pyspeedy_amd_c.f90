@@ -7,13 +7,15 @@
 !!   modelstate_init -> spd_create + spd_model_create     set_<v> / get_<v> -> spd_model_set / spd_model_get
 !!   init            -> spd_model_init                    step / parallel_step -> spd_model_step
 !!   check           -> spd_model_check                   transform_spectral2grid ... -> spd_model_spectral2grid ...
-!! and, without a counterpart there: time statistics on the device (spd_model_stats_*) and pressure-level fields (spd_model_plev_*)
+!! and, without a counterpart there: time statistics on the device (spd_model_stats_*), pressure-level fields (spd_model_plev_*)
+!! and time series recorded on the device (spd_model_tape_*)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
 
     integer(c_int), parameter :: SPD_OK = 0, SPD_E_ARG = -1, SPD_E_DEVICE = -2, SPD_E_SIZE = -3
     integer(c_int), parameter :: SPD_STATS_MEAN = 0, SPD_STATS_VARIANCE = 1, SPD_STATS_STD = 2
+    integer(c_int), parameter :: SPD_TAPE_F32 = 0, SPD_TAPE_F64 = 1
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -199,6 +201,40 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model, dst_device, stream
             character(kind=c_char), intent(in) :: name(*)
             integer(c_int), value :: first, count
+            integer(c_size_t), value :: dst_bytes
+        end function
+        ! the tape: time series of fields recorded on the device inside spd_model_step calls (pyspeedy_amd.h: spd_model_tape_*).
+        ! names as for the statistics; dtype: SPD_TAPE_F32 (0) / SPD_TAPE_F64 (1); rows: (6, held) int32, oldest sample first:
+        ! step counter after the sampled step, year, month, day, hour, minute; _read: (96, 48[, levels], nt, count) in the dtype
+        integer(c_int) function spd_model_tape_configure(model, names, n_names, every, capacity, dtype) &
+                bind(C, name="spd_model_tape_configure")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), value :: n_names, every, capacity, dtype
+        end function
+        integer(c_int) function spd_model_tape_reset(model) bind(C, name="spd_model_tape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_tape_info(model, taken, held, capacity, every, dtype) bind(C, name="spd_model_tape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken
+            integer(c_int), intent(out) :: held, capacity, every, dtype
+        end function
+        integer(c_int) function spd_model_tape_times(model, rows, max_rows) bind(C, name="spd_model_tape_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_tape_read(model, name, first, count, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_tape_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: first, count, t0, nt
             integer(c_size_t), value :: dst_bytes
         end function
         integer(c_int) function spd_model_current_step(model) bind(C, name="spd_model_current_step")

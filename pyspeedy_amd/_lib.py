@@ -17,6 +17,7 @@ NSPEC, NFOUR, NGRID = MX * NX, 2 * MX * IL, IX * IL
 
 SPD_OK, SPD_E_ARG, SPD_E_DEVICE, SPD_E_SIZE = 0, -1, -2, -3
 SPD_STATS_MEAN, SPD_STATS_VARIANCE, SPD_STATS_STD = 0, 1, 2  # kinds of spd_model_stats_read / _ensemble
+SPD_TAPE_F32, SPD_TAPE_F64 = 0, 1  # storage of spd_model_tape_configure
 
 
 class SpeedyHipError(RuntimeError):
@@ -135,6 +136,11 @@ _SIGNATURES = {
     "spd_model_stats_samples": (C.c_int, [C.c_void_p]),
     "spd_model_stats_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spd_model_stats_ensemble": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_tape_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "spd_model_tape_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_tape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 4),
+    "spd_model_tape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_tape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spd_model_plev_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     "spd_model_plev_levels": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     "spd_model_plev_compute": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -27,6 +27,7 @@
 #include "sppt_point.hpp"
 #include "plev.hpp"
 #include "stats.hpp"
+#include "tape.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
 
@@ -214,29 +215,56 @@ struct spd_model {
     // grid-space copies of the prognostic variables in output units (prognostics.f90:125-219) and their transform tables
     double *u_grid = nullptr, *v_grid = nullptr, *t_grid = nullptr, *q_grid = nullptr, *phi_grid = nullptr, *ps_grid = nullptr;
     FieldDesc *exp_inv_table[2] = {nullptr, nullptr}, *exp_fwd_table[2] = {nullptr, nullptr};  // 41 / 40 per member; [phi buffer]
+    // What the front end of a sample (statistics or tape) runs and where it writes: vort2vel when u or v is wanted, the export
+    // transforms over a descriptor table ([phi buffer]) whose destinations are the slab [M][slab_fields][4608], and the
+    // pressure-level kernel (raw = 1) from the slab's transformed planes into its further planes.  The statistics and the tape
+    // each own one, in their own allocation.
+    struct SampleFront {
+        bool uv = false, precip = false;
+        // slab_fields: planes of a member in the slab; the first xf_fields of them are written by the export transforms, the
+        // others (pressure-level variables only) by the pressure-level kernel from those
+        int slab_fields = 0, xf_fields = 0;
+        PlevArgs plev{};  // (plev.mask != 0: a pressure-level variable is sampled)
+        double *slab = nullptr;
+        FieldDesc *table[2] = {nullptr, nullptr};
+    };
     // Running time statistics (spd_model_stats_*): sampled by the step loop after every step that ends on a multiple of `every`,
     // behind each member group's last launch of that step on the group's stream.  One allocation (own hipMalloc, not the arena:
     // a reconfiguration frees it): the accumulators [variable][M][levels][4608] (mean, and M2 with variance), the sample slab
     // [M][slab_fields][4608] the export transforms write instead of the registry's grid arrays, their descriptor tables
     // ([phi buffer]) and the plane descriptors of the accumulate kernel.
-    struct Stats {
+    struct Stats : SampleFront {
         struct Var {
             int id, levels;
             size_t offset;  // doubles from `mean` / `m2` to member 0 of the variable
         };
-        bool on = false, variance = false, valid = true, uv = false, precip = false;
-        // slab_fields: planes of a member in the slab; the first xf_fields of them are written by the export transforms, the
-        // others (pressure-level variables only) by the pressure-level kernel from those
-        int every = 1, slab_fields = 0, xf_fields = 0, nplanes = 0;
-        PlevArgs plev{};  // (plev.mask != 0: a pressure-level variable is sampled)
+        bool on = false, variance = false, valid = true;
+        int every = 1, nplanes = 0;
         long long samples = 0;
         std::string invalid_why;
         std::vector<Var> vars;
         void *alloc = nullptr;
-        double *mean = nullptr, *m2 = nullptr, *slab = nullptr;
-        FieldDesc *table[2] = {nullptr, nullptr};
+        double *mean = nullptr, *m2 = nullptr;
         StatsPlane *planes = nullptr;
     } stats;
+    // The tape (spd_model_tape_*): a ring of the last `capacity` samples of chosen fields, taken where the statistics take theirs
+    // (its own `every`, slab and tables).  One allocation of its own (hipMalloc): the ring, per variable [slot][M][levels][4608] in
+    // `dtype`, then slab, tables and the plane descriptors of the store kernel.  Sample n (1-based since the last reset) lies in
+    // slot (n - 1) % capacity; its step and date are kept on the host in `rows` at issue time.
+    struct Tape : SampleFront {
+        struct Var {
+            int id, levels;
+            size_t offset;  // elements from `data` to slot 0, member 0 of the variable
+        };
+        bool on = false, valid = true;
+        int every = 1, capacity = 0, dtype = 0, nplanes = 0;
+        long long taken = 0;
+        std::string invalid_why;
+        std::vector<Var> vars;
+        std::vector<int32_t> rows;  // [capacity][6]: absolute step after the sampled step, year, month, day, hour, minute
+        void *alloc = nullptr, *data = nullptr;
+        TapePlane *planes = nullptr;
+    } tape;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {
@@ -719,6 +747,7 @@ int spd_model_destroy(spd_model_handle m) {
         if (m->cev[i]) (void)hipEventDestroy(m->cev[i]);
     }
     if (m->stats.alloc) (void)hipFree(m->stats.alloc);
+    if (m->tape.alloc) (void)hipFree(m->tape.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1256,6 +1285,8 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->fail_launch_after = -1;
     m->stats.samples = 0;  // (a new run: a new averaging period)
     m->stats.valid = true;
+    m->tape.taken = 0;  // (... and an empty tape)
+    m->tape.valid = true;
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1361,6 +1392,7 @@ static int ensure_group_streams(spd_model *m, int G) {
 // record: the range check of every step is left in m->h_steps_err[step][member] (spd_model_step_checked_begin) -- the check of step
 // k rides in the spectral -> grid launch of step k + 1 of the same members, the last one is a launch of its own behind the call.
 static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_stats_configure)
+static hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);   // (with spd_model_tape_configure)
 
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
@@ -1449,8 +1481,9 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     bool launched = false, device_failed = false;  // a launch of this call went out / a device call of it failed
     const int tl_check = 1;  // the check looks at time level 2 (do_single_step checks the state the step has just produced)
     const long long samples0 = m->stats.samples;  // (statistics: every round takes the same samples)
+    const long long tape0 = m->tape.taken;        // (... and writes the same slots of the tape, for its own members)
     for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
-        long long taken = 0;
+        long long taken = 0, tape_taken = 0;
         const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
         if (round > 0) {  // the same steps again, for the next members
             m->cal = start.cal;
@@ -1471,7 +1504,9 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             // a step whose state the statistics sample: its diagnostics-only outputs are stored when precnv / precls are sampled
             const bool sample = m->stats.on && (m->current_step + 1) % m->stats.every == 0;
             if (sample) ++taken;
-            const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip)) ? 1 : 0;
+            const bool record_tape = m->tape.on && (m->current_step + 1) % m->tape.every == 0;
+            if (record_tape) ++tape_taken;
+            const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip)) ? 1 : 0;
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
             // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
@@ -1529,6 +1564,14 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                         device_failed = true;
                     }
                 }
+                if (rc == SPD_OK && record_tape) {  // behind the statistics' sample, on the same stream
+                    const hipError_t e = tape_sample(m, first, count, tape0 + tape_taken, gs[g]);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": tape: " + hipGetErrorString(e));
+                        device_failed = true;
+                    }
+                }
                 first += count;
             }
             if (rc != SPD_OK) break;
@@ -1538,6 +1581,11 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             m->surf_cache_valid = true;
             if (round == 0) note_accepted(it + 1);
             if (round == 0 && sample) m->stats.samples = samples0 + taken;
+            if (round == 0 && record_tape) {  // the sample's step and the date of the sampled state, kept beside its slot
+                m->tape.taken = tape0 + tape_taken;
+                int32_t *row = m->tape.rows.data() + 6 * static_cast<size_t>((m->tape.taken - 1) % m->tape.capacity);
+                row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+            }
         }
         round_first += round_count;
     }
@@ -1599,6 +1647,12 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
             m->stats.valid = false;
             m->stats.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
                                    " of a checked call";
+        }
+    for (int i = 0; i < M && m->tape.on && m->tape.valid; ++i)
+        if (first_failed_step[i] >= 0) {  // (the same for the samples on the tape)
+            m->tape.valid = false;
+            m->tape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
+                                  " of a checked call";
         }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)
@@ -1981,30 +2035,14 @@ static int stats_id(const char *name) {
 }
 }  // namespace
 
-// the sample of members [first, first + count) after the step just issued on `s`: what spd_model_spectral2grid would leave in the
-// grid arrays (the same vort2vel into sv, the same transforms, into the slab), then the moments
-static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
-    const spd_model::Stats &st = m->stats;
-    const DeviceTables &T = m->ctx->dev;
-    const size_t S = NSPEC * C, half = static_cast<size_t>(m->M) * 16, off = static_cast<size_t>(first) * 16;
-    hipError_t e = hipSuccess;
-    if (st.uv) e = run_vort2vel(T, m->P.vor + off * S, m->P.div + off * S, m->P.sv + off * S, m->P.sv + (half + off) * S, count * 16, s);
-    if (e == hipSuccess && st.xf_fields > 0)
-        e = run_spec2grid_table(T, st.table[m->phi_cur] + static_cast<size_t>(first) * st.xf_fields, count * st.xf_fields, s);
-    if (e == hipSuccess && st.plev.mask) {  // slab -> further slab planes, in export units
-        PlevArgs a = st.plev;
-        a.first = first;
-        e = run_plev(a, count, s);
-    }
-    if (e == hipSuccess) e = run_stats_accumulate(st.planes, st.nplanes, st.slab, st.slab_fields, first, count, n, m->stored32 ? 1 : 0, s);
-    return e;
-}
+// ---- the layout of a sample's front end, shared by the statistics and the tape (spd_model::SampleFront) ----
+namespace {
+constexpr size_t kSampleAlign = 256;
+size_t sample_up(size_t b) { return (b + kSampleAlign - 1) / kSampleAlign * kSampleAlign; }
 
-int spd_model_stats_configure(spd_model_handle m, const char *const *names, int n_names, int every, int with_variance) {
-    const char *who = "spd_model_stats_configure";
-    // (the arguments first: nothing below needs the device)
+// the list of names of a _configure call -> catalogue ids (the arguments first: nothing here needs the device or a model)
+int sample_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
     if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
-    std::vector<int> ids;
     for (int k = 0; k < n_names; ++k) {
         const int id = names[k] ? stats_id(names[k]) : -1;
         if (id < 0)
@@ -2015,6 +2053,159 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
             return m_fail(SPD_E_ARG, std::string(who) + ": variable '" + names[k] + "' named twice");
         ids.push_back(id);
     }
+    return SPD_OK;
+}
+
+struct SamplePlan {
+    struct Var {
+        int id, levels;
+        size_t first_plane;  // planes of the variables before this one (of one member)
+    };
+    std::vector<Var> vars;
+    // what the export transforms write into the slab, in slab order: the sigma-level variables asked for, then those only a
+    // pressure-level variable needs; xf_at[id]: first slab plane of variable id (-1: not transformed)
+    std::vector<int> xf;
+    int xf_at[6] = {-1, -1, -1, -1, -1, -1};
+    size_t planes = 0;                        // planes of all variables of one member
+    size_t slab_bytes = 0, table_bytes = 0;   // of the slab and of ONE descriptor table, rounded up to kSampleAlign
+};
+
+// the variables `ids` of the model's M members: which planes the slab holds (front.uv, precip, xf_fields, slab_fields, plev.mask)
+// and how large slab and tables are
+void plan_sample(const spd_model *m, const std::vector<int> &ids, spd_model::SampleFront &front, SamplePlan &plan) {
+    int needs = 0, plev_planes = 0;
+    auto levels_of = [&](int id) { return id >= kPlevFirst && id != kPlevFirst + PLEV_MSLP ? m->plev.n : kStatsCatalogue[id].levels; };
+    for (int id : ids) {
+        plan.vars.push_back({id, levels_of(id), plan.planes});
+        plan.planes += static_cast<size_t>(levels_of(id));
+        if (id < 6) plan.xf.push_back(id);
+        front.precip = front.precip || id == 6 || id == 7;
+        if (id >= kPlevFirst) {
+            front.plev.mask |= 1 << (id - kPlevFirst);
+            needs |= kPlevNeeds[id - kPlevFirst];
+            plev_planes += levels_of(id);
+        }
+    }
+    for (int id = 0; id < 6; ++id)
+        if ((needs >> id & 1) && std::find(plan.xf.begin(), plan.xf.end(), id) == plan.xf.end()) plan.xf.push_back(id);
+    for (int id : plan.xf) {
+        plan.xf_at[id] = front.xf_fields;
+        front.xf_fields += kStatsCatalogue[id].levels;
+        front.uv = front.uv || id < 2;
+    }
+    front.slab_fields = front.xf_fields + plev_planes;
+    const size_t M = static_cast<size_t>(m->M);
+    plan.slab_bytes = sample_up(M * front.slab_fields * NG * sizeof(double));
+    plan.table_bytes = sample_up(M * front.xf_fields * sizeof(FieldDesc));
+}
+
+// front.slab and front.table[] point into the caller's allocation: uploads the export descriptors of spd_model_spectral2grid
+// (build_tables) with the slab as destination, for the chosen variables, and sets up the pressure-level kernel of a sample (from
+// the slab's transformed planes into its further planes).  slab_plane: per plane of plan.vars, in their order, the slab plane the
+// value is read from (-1: precnv / precls, read where the column kernel stores them).
+hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_model::SampleFront &front, std::vector<int> &slab_plane) {
+    const size_t M = static_cast<size_t>(m->M);
+    const ModelPtrs &P = m->P;
+    auto spec = [](double *base, size_t field) { return base + field * NSPEC * C; };
+    const size_t half = M * 16;
+    std::vector<FieldDesc> host_table[2];
+    for (int par = 0; par < 2; ++par) {
+        host_table[par].reserve(M * front.xf_fields);
+        for (size_t i = 0; i < M; ++i) {
+            const size_t w = i * 8, s1 = i * 16;
+            size_t j = 0;
+            for (const int id : plan.xf) {
+                for (int k = 0; k < kStatsCatalogue[id].levels; ++k, ++j) {
+                    double *dst = front.slab + (i * front.slab_fields + j) * NG;
+                    switch (id) {
+                        case 0: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
+                        case 1: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
+                        case 2: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
+                        case 3: host_table[par].push_back({spec(P.tr, s1 + k), dst, 1, 0}); break;
+                        case 4: host_table[par].push_back({spec(m->phi_buf[par], w + k), dst, 1, 0}); break;
+                        default: host_table[par].push_back({spec(P.ps, i * 2), dst, 1, 0}); break;
+                    }
+                }
+            }
+        }
+    }
+    int plev_plane = front.xf_fields;
+    if (front.plev.mask) {
+        PlevArgs &a = front.plev;
+        const long stride = static_cast<long>(front.slab_fields) * NG;
+        for (int x = 0; x < 5; ++x) {
+            a.in[x] = plan.xf_at[x] >= 0 ? front.slab + static_cast<size_t>(plan.xf_at[x]) * NG : nullptr;
+            a.in_stride[x] = stride;
+        }
+        a.ps = front.slab + static_cast<size_t>(plan.xf_at[5]) * NG;
+        a.ps_stride = stride;
+        a.phis0 = m->pa.phis0;
+        a.raw = 1;
+        a.n = m->plev.n;
+        std::copy(m->plev.lnp, m->plev.lnp + kPlevMaxLevels, a.lnp);
+    }
+    slab_plane.clear();
+    for (const auto &v : plan.vars)
+        for (int k = 0; k < v.levels; ++k) {
+            if (v.id < 6) slab_plane.push_back(plan.xf_at[v.id] + k);
+            else if (v.id >= kPlevFirst) {
+                if (k == 0) {
+                    front.plev.out[v.id - kPlevFirst] = front.slab + static_cast<size_t>(plev_plane) * NG;
+                    front.plev.out_stride[v.id - kPlevFirst] = static_cast<long>(front.slab_fields) * NG;
+                }
+                slab_plane.push_back(plev_plane++);
+            } else slab_plane.push_back(-1);
+        }
+    hipError_t e = hipSuccess;
+    if (front.xf_fields > 0) {
+        e = hipMemcpy(front.table[0], host_table[0].data(), host_table[0].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(front.table[1], host_table[1].data(), host_table[1].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
+    }
+    return e;
+}
+
+// the front end of a sample of members [first, first + count) after the step just issued on `s`: what spd_model_spectral2grid
+// would leave in the grid arrays (the same vort2vel into sv, the same transforms), into the slab; then the pressure-level planes
+hipError_t sample_front(spd_model *m, const spd_model::SampleFront &f, int first, int count, hipStream_t s) {
+    const DeviceTables &T = m->ctx->dev;
+    const size_t S = NSPEC * C, half = static_cast<size_t>(m->M) * 16, off = static_cast<size_t>(first) * 16;
+    hipError_t e = hipSuccess;
+    if (f.uv) e = run_vort2vel(T, m->P.vor + off * S, m->P.div + off * S, m->P.sv + off * S, m->P.sv + (half + off) * S, count * 16, s);
+    if (e == hipSuccess && f.xf_fields > 0)
+        e = run_spec2grid_table(T, f.table[m->phi_cur] + static_cast<size_t>(first) * f.xf_fields, count * f.xf_fields, s);
+    if (e == hipSuccess && f.plev.mask) {  // slab -> further slab planes, in export units
+        PlevArgs a = f.plev;
+        a.first = first;
+        e = run_plev(a, count, s);
+    }
+    return e;
+}
+}  // namespace
+
+// the sample of members [first, first + count): the front end, then the moments
+static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
+    const spd_model::Stats &st = m->stats;
+    hipError_t e = sample_front(m, st, first, count, s);
+    if (e == hipSuccess) e = run_stats_accumulate(st.planes, st.nplanes, st.slab, st.slab_fields, first, count, n, m->stored32 ? 1 : 0, s);
+    return e;
+}
+
+// ... and of the tape: the front end into the tape's own slab, then the store into ring slot (n - 1) % capacity
+static hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
+    const spd_model::Tape &tp = m->tape;
+    hipError_t e = sample_front(m, tp, first, count, s);
+    if (e == hipSuccess)
+        e = run_tape_store(tp.planes, tp.nplanes, tp.slab, tp.slab_fields, first, count, static_cast<int>((n - 1) % tp.capacity),
+                           m->stored32 ? 1 : 0, tp.dtype == SPD_TAPE_F64 ? 1 : 0, s);
+    return e;
+}
+
+int spd_model_stats_configure(spd_model_handle m, const char *const *names, int n_names, int every, int with_variance) {
+    const char *who = "spd_model_stats_configure";
+    // (the arguments first: nothing below needs the device)
+    std::vector<int> ids;
+    if (int rc = sample_ids(who, names, n_names, ids)) return rc;
     if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
     if (int rc = usable(m, who)) return rc;
@@ -2032,100 +2223,31 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     next.every = every;
     next.variance = with_variance != 0;
     const size_t M = static_cast<size_t>(m->M);
-    size_t planes = 0;
-    // what the export transforms write into the slab, in slab order: the sigma-level variables asked for, then those only a
-    // pressure-level variable needs; xf_at[id]: first slab plane of variable id (-1: not transformed)
-    std::vector<int> xf;
-    int xf_at[6] = {-1, -1, -1, -1, -1, -1}, needs = 0, plev_planes = 0;
-    auto levels_of = [&](int id) { return id >= kPlevFirst && id != kPlevFirst + PLEV_MSLP ? m->plev.n : kStatsCatalogue[id].levels; };
-    for (int id : ids) {
-        next.vars.push_back({id, levels_of(id), M * planes * NG});
-        planes += static_cast<size_t>(levels_of(id));
-        if (id < 6) xf.push_back(id);
-        next.precip = next.precip || id == 6 || id == 7;
-        if (id >= kPlevFirst) {
-            next.plev.mask |= 1 << (id - kPlevFirst);
-            needs |= kPlevNeeds[id - kPlevFirst];
-            plev_planes += levels_of(id);
-        }
-    }
-    for (int id = 0; id < 6; ++id)
-        if ((needs >> id & 1) && std::find(xf.begin(), xf.end(), id) == xf.end()) xf.push_back(id);
-    for (int id : xf) {
-        xf_at[id] = next.xf_fields;
-        next.xf_fields += kStatsCatalogue[id].levels;
-        next.uv = next.uv || id < 2;
-    }
-    next.slab_fields = next.xf_fields + plev_planes;
+    SamplePlan plan;
+    plan_sample(m, ids, next, plan);
+    const size_t planes = plan.planes;
+    for (const auto &v : plan.vars) next.vars.push_back({v.id, v.levels, M * v.first_plane * NG});
     next.nplanes = static_cast<int>(planes);
     // one allocation: mean | m2 | slab | tables[2] | plane descriptors
-    constexpr size_t kAlign = 256;
-    auto up = [](size_t b) { return (b + kAlign - 1) / kAlign * kAlign; };
-    const size_t acc = up(M * planes * NG * sizeof(double)), slab = up(M * next.slab_fields * NG * sizeof(double)),
-                 table = up(M * next.xf_fields * sizeof(FieldDesc)), desc = up(planes * sizeof(StatsPlane));
-    const size_t total = acc * (next.variance ? 2 : 1) + slab + 2 * table + desc;
+    const size_t acc = sample_up(M * planes * NG * sizeof(double)), desc = sample_up(planes * sizeof(StatsPlane));
+    const size_t total = acc * (next.variance ? 2 : 1) + plan.slab_bytes + 2 * plan.table_bytes + desc;
     void *p = nullptr;
     M_HIP(hipMalloc(&p, total));
     char *at = static_cast<char *>(p);
     next.alloc = p;
     next.mean = reinterpret_cast<double *>(at), at += acc;
     if (next.variance) next.m2 = reinterpret_cast<double *>(at), at += acc;
-    next.slab = reinterpret_cast<double *>(at), at += slab;
-    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += table;
-    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += table;
+    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
+    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
+    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
     next.planes = reinterpret_cast<StatsPlane *>(at);
-    // the export descriptors of spd_model_spectral2grid (build_tables), with the slab as destination, for the chosen variables
-    const ModelPtrs &P = m->P;
-    auto spec = [](double *base, size_t field) { return base + field * NSPEC * C; };
-    const size_t half = M * 16;
-    std::vector<FieldDesc> host_table[2];
-    for (int par = 0; par < 2; ++par) {
-        host_table[par].reserve(M * next.xf_fields);
-        for (size_t i = 0; i < M; ++i) {
-            const size_t w = i * 8, s1 = i * 16;
-            size_t j = 0;
-            for (const int id : xf) {
-                for (int k = 0; k < kStatsCatalogue[id].levels; ++k, ++j) {
-                    double *dst = next.slab + (i * next.slab_fields + j) * NG;
-                    switch (id) {
-                        case 0: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
-                        case 1: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
-                        case 2: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
-                        case 3: host_table[par].push_back({spec(P.tr, s1 + k), dst, 1, 0}); break;
-                        case 4: host_table[par].push_back({spec(m->phi_buf[par], w + k), dst, 1, 0}); break;
-                        default: host_table[par].push_back({spec(P.ps, i * 2), dst, 1, 0}); break;
-                    }
-                }
-            }
-        }
-    }
+    std::vector<int> slab_plane;
+    hipError_t e = build_sample_front(m, plan, next, slab_plane);
     std::vector<StatsPlane> host_planes;
-    int plev_plane = next.xf_fields;
-    if (next.plev.mask) {  // the pressure-level kernel of a sample: from the slab's transformed planes into its further planes
-        PlevArgs &a = next.plev;
-        const long stride = static_cast<long>(next.slab_fields) * NG;
-        for (int x = 0; x < 5; ++x) {
-            a.in[x] = xf_at[x] >= 0 ? next.slab + static_cast<size_t>(xf_at[x]) * NG : nullptr;
-            a.in_stride[x] = stride;
-        }
-        a.ps = next.slab + static_cast<size_t>(xf_at[5]) * NG;
-        a.ps_stride = stride;
-        a.phis0 = m->pa.phis0;
-        a.raw = 1;
-        a.n = m->plev.n;
-        std::copy(m->plev.lnp, m->plev.lnp + kPlevMaxLevels, a.lnp);
-    }
     for (const auto &v : next.vars)
         for (int k = 0; k < v.levels; ++k) {
             StatsPlane d{};
-            if (v.id < 6) d.slab_plane = xf_at[v.id] + k;
-            else if (v.id >= kPlevFirst) {
-                if (k == 0) {
-                    next.plev.out[v.id - kPlevFirst] = next.slab + static_cast<size_t>(plev_plane) * NG;
-                    next.plev.out_stride[v.id - kPlevFirst] = static_cast<long>(next.slab_fields) * NG;
-                }
-                d.slab_plane = plev_plane++;
-            } else d.slab_plane = -1;
+            d.slab_plane = slab_plane[host_planes.size()];
             d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
             d.unit = kStatsCatalogue[v.id].unit;
             d.mean = next.mean + v.offset + static_cast<size_t>(k) * NG;
@@ -2133,12 +2255,6 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
             d.member_stride = static_cast<long>(v.levels) * NG;
             host_planes.push_back(d);
         }
-    hipError_t e = hipSuccess;
-    if (next.xf_fields > 0) {
-        e = hipMemcpy(next.table[0], host_table[0].data(), host_table[0].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(next.table[1], host_table[1].data(), host_table[1].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
-    }
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(StatsPlane), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -2228,6 +2344,152 @@ int spd_model_stats_ensemble(spd_model_handle m, const char *name, int kind, voi
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the tape: time series of fields recorded inside multi-step calls (spd_model_tape_*; kernels: tape.hip)
+// ---------------------------------------------------------------------------------------------------------------
+int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity, int dtype) {
+    const char *who = "spd_model_tape_configure";
+    // (the arguments first: nothing below needs the device)
+    std::vector<int> ids;
+    if (int rc = sample_ids(who, names, n_names, ids)) return rc;
+    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+    if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+    if (n_names > 0 && dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64)
+        return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    for (size_t k = 0; k < ids.size(); ++k)
+        if (ids[k] >= kPlevFirst && m->plev.n == 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
+    spd_model::Tape &tp = m->tape;
+    if (tp.alloc) M_HIP(hipFree(tp.alloc));
+    tp = spd_model::Tape{};
+    if (n_names == 0) return SPD_OK;  // off
+    spd_model::Tape next;
+    next.every = every;
+    next.capacity = capacity;
+    next.dtype = dtype;
+    const size_t M = static_cast<size_t>(m->M), elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
+    SamplePlan plan;
+    plan_sample(m, ids, next, plan);
+    const size_t slots = static_cast<size_t>(capacity);
+    for (const auto &v : plan.vars) next.vars.push_back({v.id, v.levels, slots * M * v.first_plane * NG});
+    next.nplanes = static_cast<int>(plan.planes);
+    // one allocation: ring | slab | tables[2] | plane descriptors
+    const size_t per_slot = M * plan.planes * NG * elem;
+    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 2) / per_slot)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the tape's size does not fit size_t");
+    const size_t ring = sample_up(slots * per_slot), desc = sample_up(plan.planes * sizeof(TapePlane));
+    const size_t total = ring + plan.slab_bytes + 2 * plan.table_bytes + desc;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the tape is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the tape (" + std::to_string(total) + " bytes asked for: " +
+                                        std::to_string(capacity) + " samples of " + std::to_string(per_slot) + " bytes); the tape is off");
+    }
+    char *at = static_cast<char *>(p);
+    next.alloc = p;
+    next.data = at, at += ring;
+    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
+    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
+    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
+    next.planes = reinterpret_cast<TapePlane *>(at);
+    std::vector<int> slab_plane;
+    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<TapePlane> host_planes;
+    for (const auto &v : next.vars)
+        for (int k = 0; k < v.levels; ++k) {
+            TapePlane d{};
+            d.slab_plane = slab_plane[host_planes.size()];
+            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
+            d.unit = kStatsCatalogue[v.id].unit;
+            d.dst = static_cast<char *>(next.data) + (v.offset + static_cast<size_t>(k) * NG) * elem;
+            d.member_stride = static_cast<long>(v.levels) * NG;
+            d.slot_stride = static_cast<long>(M) * v.levels * NG;
+            host_planes.push_back(d);
+        }
+    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(TapePlane), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    next.rows.assign(slots * 6, 0);
+    next.on = true;
+    tp = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_tape_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_reset: null model");
+    if (!m->tape.on) return m_fail(SPD_E_ARG, "spd_model_tape_reset: no tape configured (spd_model_tape_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_tape_reset: a checked multi-step call is in flight; end it first");
+    m->tape.taken = 0;  // (the next sample goes into slot 0: no device work)
+    m->tape.valid = true;
+    m->tape.invalid_why.clear();
+    return SPD_OK;
+}
+
+int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *dtype) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_info: null model");
+    const spd_model::Tape &tp = m->tape;
+    if (!tp.on) return m_fail(SPD_E_ARG, "spd_model_tape_info: no tape configured (spd_model_tape_configure)");
+    if (taken) *taken = tp.taken;
+    if (held) *held = static_cast<int>(std::min<long long>(tp.taken, tp.capacity));
+    if (capacity) *capacity = tp.capacity;
+    if (every) *every = tp.every;
+    if (dtype) *dtype = tp.dtype;
+    return SPD_OK;
+}
+
+int spd_model_tape_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_times: null model");
+    const spd_model::Tape &tp = m->tape;
+    if (!tp.on) return m_fail(SPD_E_ARG, "spd_model_tape_times: no tape configured (spd_model_tape_configure)");
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_tape_times: bad destination");
+    const long long held = std::min<long long>(tp.taken, tp.capacity), oldest = tp.taken - held;  // (sample numbers from 0)
+    int n = 0;
+    for (; n < held && n < max_rows; ++n)
+        std::memcpy(rows + 6 * static_cast<size_t>(n), tp.rows.data() + 6 * static_cast<size_t>((oldest + n) % tp.capacity), 6 * sizeof(int32_t));
+    return n;
+}
+
+int spd_model_tape_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
+                        void *stream) {
+    const char *who = "spd_model_tape_read";
+    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::Tape &tp = m->tape;
+    if (!tp.on) return m_fail(SPD_E_ARG, std::string(who) + ": no tape configured (spd_model_tape_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (!tp.valid) return m_fail(SPD_E_ARG, std::string(who) + ": the tape is invalid until spd_model_tape_reset: " + tp.invalid_why);
+    const int id = stats_id(name);
+    const spd_model::Tape::Var *v = nullptr;
+    for (const auto &x : tp.vars)
+        if (x.id == id) v = &x;
+    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    const long long held = std::min<long long>(tp.taken, tp.capacity), oldest = tp.taken - held;
+    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
+        return m_fail(SPD_E_ARG, std::string(who) + ": sample range out of bounds (" + std::to_string(held) + " samples held)");
+    const size_t elem = tp.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->levels) * NG;
+    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (count == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    const char *src = static_cast<const char *>(tp.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
+    const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
+                                         static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % tp.capacity), tp.capacity,
+                                         static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // pressure-level fields and mean sea-level pressure (spd_model_plev_*; kernel: plev.hip)
 // ---------------------------------------------------------------------------------------------------------------
 static int plev_id(const char *name) {
@@ -2253,6 +2515,8 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
     if (m->stats.on && m->stats.plev.mask)
         return m_fail(SPD_E_ARG, std::string(who) + ": statistics of a pressure-level variable are configured; switch them off first "
                                                     "(spd_model_stats_configure)");
+    if (m->tape.on && m->tape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the tape holds a pressure-level variable; switch it off first (spd_model_tape_configure)");
     spd_model::Plev &pl = m->plev;
     pl.n = n;
     for (int j = 0; j < kPlevMaxLevels; ++j) {

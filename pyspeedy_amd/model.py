@@ -368,6 +368,68 @@ class EnsembleModel:
             out.append(t)
         return tuple(out)
 
+    # ---- the tape: time series of fields recorded on the device (spd_model_tape_*, include/pyspeedy_amd.h) ---------------
+    TAPE_DTYPES = {"float32": (_lib.SPD_TAPE_F32, torch.float32), "float64": (_lib.SPD_TAPE_F64, torch.float64)}
+
+    def tape_configure(self, variables, every, capacity, dtype="float32"):
+        """Record `variables` (any of STATS_VARIABLES) after every step that leaves current_step at a multiple of `every`, inside
+        run() / run_checked() calls of any length, into a ring in device memory that keeps the last `capacity` samples of every
+        member; dtype "float32" (the default: what the export writes) or "float64".  Empties the tape; an empty list switches it
+        off and frees it.  Synchronises the device."""
+        key = str(dtype).replace("torch.", "")
+        if key not in self.TAPE_DTYPES:
+            raise ValueError("dtype must be 'float32' or 'float64', got %r" % (dtype,))
+        names = [str(v) for v in variables]
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_tape_configure(self._m, arr, len(names), int(every), int(capacity), self.TAPE_DTYPES[key][0]),
+                  "spd_model_tape_configure")
+
+    def tape_reset(self):
+        """Empty the tape (no device work); the next sample is the first."""
+        check(self._lib.spd_model_tape_reset(self._m), "spd_model_tape_reset")
+
+    @property
+    def tape_info(self):
+        """dict(taken, held, capacity, every, dtype): samples since the last reset, samples the ring holds (min(taken, capacity)),
+        and the configuration."""
+        taken, held, capacity, every, dtype = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.spd_model_tape_info(self._m, C.byref(taken), C.byref(held), C.byref(capacity), C.byref(every), C.byref(dtype)),
+              "spd_model_tape_info")
+        name = [k for k, v in self.TAPE_DTYPES.items() if v[0] == dtype.value][0]
+        return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, dtype=name)
+
+    def _tape_rows(self):
+        held = self.tape_info["held"]
+        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
+        n = self._lib.spd_model_tape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
+        if n < 0:
+            check(n, "spd_model_tape_times")
+        return rows[:n]
+
+    def tape_steps(self):
+        """The model's step counter after each held sample's step, oldest first (numpy int array)."""
+        return self._tape_rows()[:, 0].astype(np.int64)
+
+    def tape_times(self):
+        """The date of each held sample's state, oldest first (a list of datetime)."""
+        from datetime import datetime
+        return [datetime(*(int(v) for v in row[1:6])) for row in self._tape_rows()]
+
+    def tape(self, name, first=0, count=None, t0=0, nt=None):
+        """Members [first, first + count) and samples [t0, t0 + nt) of the held ones (oldest first) of one variable: a tensor
+        [count][nt][levels][48][96] ([count][nt][48][96] for one-level names) on the model's device in the tape's dtype."""
+        first, count = self._range(first, count)
+        info = self.tape_info
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        dtype = self.TAPE_DTYPES[info["dtype"]][1]
+        out = torch.empty((count, max(nt, 0)) + self._stats_shape(name), dtype=dtype, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_tape_read(self._m, name.encode(), first, count, t0, nt, C.c_void_p(out.data_ptr()),
+                                                out.numel() * out.element_size(), self._stream()), "spd_model_tape_read(%s)" % name)
+        return out
+
     # ---- pressure-level fields and mean sea-level pressure (spd_model_plev_*, include/pyspeedy_amd.h) -------------------
     PLEV_VARIABLES = ("u_plev", "v_plev", "t_plev", "q_plev", "z_plev", "mslp")
 

@@ -463,6 +463,47 @@ int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *ca
 int spd_model_tape_times(spd_model_handle m, int32_t *rows, int max_rows);
 int spd_model_tape_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
                         void *stream);
+/* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
+ * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
+ * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],
+ * the total wavenumber of an element is l = m + n, and with w_0 = 1, w_m = 2 otherwise, S_l(f) = sum over m = 0 ... min(l, 30) of
+ * w_m |f_l^m|^2 (m ascending, fp64, one lane: a sample is the same bits whatever the launch plan).  Names, all fp64:
+ *   ke_rot_spectrum [8][32]  1/4 elm2(l) S_l(vorticity), J/kg (elm2: a^2 / (l (l + 1)), 0 at l = 0)
+ *   ke_div_spectrum [8][32]  the same of the divergence
+ *   t_spectrum      [8][32]  1/2 S_l(T), K^2: its sum over l is the global area mean of T^2, bin 0 the squared mean
+ *   q_spectrum      [8][32]  the same of the tracer in its stored unit (g/kg)
+ *   lnps_spectrum   [32]     the same of the stored ln(ps / 1e5 Pa)
+ *   t_mean, q_mean  [8]      the global area mean: Re f_0^0 * sqrt(1/2)
+ *   lnps_mean       [1]      the same
+ * A ring buffer in device memory, per model, holds the last `capacity` samples of the chosen names for every member; one sample is
+ * taken after every step that leaves the model's absolute step counter at a multiple of `every`, by each member group on its own
+ * stream behind its last launch of that step (and behind the statistics' and the tape's samples): one launch, no other launch of
+ * the step changes, and nothing of the run does.
+ *   _configure  allocates the ring (one hipMalloc of its own; synchronises the device) and empties it; n_names = 0 switches the
+ *               spectra off and frees it.  SPD_E_ARG for an unknown or repeated name, every < 1, capacity < 1, a size beyond size_t,
+ *               or while a checked call is in flight.  SPD_E_DEVICE with the number of bytes asked for when the allocation fails:
+ *               the spectra are then off and the model as usable as before.
+ *   _reset      empties the ring (host only, no device work).  spd_model_init does the same.
+ *   _info       taken: samples since the last reset; held = min(taken, capacity); any pointer may be NULL.
+ *   _times      rows[held][6] for the held samples, oldest first: the absolute step counter after the sampled step, then year,
+ *               month, day, hour, minute of the sampled state (host memory).  Returns the number of rows written (<= max_rows).
+ *   _read       members [first, first + count) and samples [t0, t0 + nt) of the held ones, oldest first, of one name into
+ *               dst_device[count][nt][...] doubles, stream-ordered.  SPD_E_SIZE when dst_bytes is too small.
+ *   _compute    the same kernel on the state as it stands, without a ring and without _configure: the members [first, first +
+ *               count) of every name given into dst_device, [count][...] per name, one name after the other in the order given,
+ *               stream-ordered.
+ * Reads fail (SPD_E_ARG, with the reason) while a checked call is in flight and after a checked call that reported a failed range
+ * check (the message names the member and the step): the series stays invalid until _reset or spd_model_init.
+ * spd_model_copy_member does not carry the ring, and the outer boundary (spd_parallel_step*) does not keep it across the models
+ * it merges and splits. */
+int spd_model_spectra_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity);
+int spd_model_spectra_reset(spd_model_handle m);
+int spd_model_spectra_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every);
+int spd_model_spectra_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_spectra_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device,
+                           size_t dst_bytes, void *stream);
+int spd_model_spectra_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, void *dst_device,
+                              size_t dst_bytes, void *stream);
 /* modelstate_init_sst_anom (speedy_driver.f90.j2:225-237): sst_anom(ix, il, 0:n_months+1) per member, zero-filled */
 int spd_model_init_sst_anom(spd_model_handle m, int n_months);
 /* Stochastically perturbed parametrisation tendencies (sppt.f90; compile-time off and non-functional in the reference:

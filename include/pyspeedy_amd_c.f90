@@ -7,8 +7,8 @@
 !!   modelstate_init -> spd_create + spd_model_create     set_<v> / get_<v> -> spd_model_set / spd_model_get
 !!   init            -> spd_model_init                    step / parallel_step -> spd_model_step
 !!   check           -> spd_model_check                   transform_spectral2grid ... -> spd_model_spectral2grid ...
-!! and, without a counterpart there: time statistics on the device (spd_model_stats_*), pressure-level fields (spd_model_plev_*)
-!! and time series recorded on the device (spd_model_tape_*)
+!! and, without a counterpart there: time statistics on the device (spd_model_stats_*), pressure-level fields (spd_model_plev_*),
+!! time series recorded on the device (spd_model_tape_*) and spectra of the spectral state (spd_model_spectra_*)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -235,6 +235,48 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model, dst_device, stream
             character(kind=c_char), intent(in) :: name(*)
             integer(c_int), value :: first, count, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
+        ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for
+        ! a spectrum, ([8, ]nt, count) for a mean; _compute: (..., count) per name, one name after the other
+        integer(c_int) function spd_model_spectra_configure(model, names, n_names, every, capacity) &
+                bind(C, name="spd_model_spectra_configure")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), value :: n_names, every, capacity
+        end function
+        integer(c_int) function spd_model_spectra_reset(model) bind(C, name="spd_model_spectra_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_spectra_info(model, taken, held, capacity, every) bind(C, name="spd_model_spectra_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken
+            integer(c_int), intent(out) :: held, capacity, every
+        end function
+        integer(c_int) function spd_model_spectra_times(model, rows, max_rows) bind(C, name="spd_model_spectra_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_spectra_read(model, name, first, count, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_spectra_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: first, count, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_spectra_compute(model, names, n_names, first, count, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_spectra_compute")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), value :: n_names, first, count
             integer(c_size_t), value :: dst_bytes
         end function
         integer(c_int) function spd_model_current_step(model) bind(C, name="spd_model_current_step")

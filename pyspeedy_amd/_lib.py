@@ -141,6 +141,12 @@ _SIGNATURES = {
     "spd_model_tape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 4),
     "spd_model_tape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "spd_model_tape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
+    "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),
+    "spd_model_spectra_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_spectra_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_spectra_compute": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spd_model_plev_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     "spd_model_plev_levels": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     "spd_model_plev_compute": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

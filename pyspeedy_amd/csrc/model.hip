@@ -27,6 +27,7 @@
 #include "sppt_point.hpp"
 #include "plev.hpp"
 #include "stats.hpp"
+#include "spectra.hpp"
 #include "tape.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
@@ -265,6 +266,20 @@ struct spd_model {
         void *alloc = nullptr, *data = nullptr;
         TapePlane *planes = nullptr;
     } tape;
+    // Spectra and global means of the spectral state (spd_model_spectra_*): a ring of the last `capacity` samples of the chosen
+    // names, fp64, written by one launch per member group and sample behind the tape's (no transform, no slab: spectra.hip).  One
+    // allocation of its own (hipMalloc): per name [slot][M][per] doubles.  Sample n (1-based since the last reset) lies in slot
+    // (n - 1) % capacity; its step and date are kept on the host in `rows` at issue time.
+    struct Spectra {
+        bool on = false, valid = true;
+        int every = 1, capacity = 0;
+        unsigned mask = 0;
+        long long taken = 0;
+        std::string invalid_why;
+        std::vector<int32_t> rows;  // [capacity][6]: absolute step after the sampled step, year, month, day, hour, minute
+        void *alloc = nullptr;
+        size_t offset[SPECTRA_NNAMES] = {};  // doubles from `alloc` to slot 0, member 0 of a name of the mask
+    } spectra;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {
@@ -748,6 +763,7 @@ int spd_model_destroy(spd_model_handle m) {
     }
     if (m->stats.alloc) (void)hipFree(m->stats.alloc);
     if (m->tape.alloc) (void)hipFree(m->tape.alloc);
+    if (m->spectra.alloc) (void)hipFree(m->spectra.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1287,6 +1303,8 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->stats.valid = true;
     m->tape.taken = 0;  // (... and an empty tape)
     m->tape.valid = true;
+    m->spectra.taken = 0;  // (... and an empty series of spectra)
+    m->spectra.valid = true;
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1393,6 +1411,7 @@ static int ensure_group_streams(spd_model *m, int G) {
 // k rides in the spectral -> grid launch of step k + 1 of the same members, the last one is a launch of its own behind the call.
 static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_stats_configure)
 static hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);   // (with spd_model_tape_configure)
+static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_spectra_configure)
 
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
@@ -1482,8 +1501,9 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     const int tl_check = 1;  // the check looks at time level 2 (do_single_step checks the state the step has just produced)
     const long long samples0 = m->stats.samples;  // (statistics: every round takes the same samples)
     const long long tape0 = m->tape.taken;        // (... and writes the same slots of the tape, for its own members)
+    const long long spectra0 = m->spectra.taken;  // (... and of the spectra)
     for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
-        long long taken = 0, tape_taken = 0;
+        long long taken = 0, tape_taken = 0, spectra_taken = 0;
         const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
         if (round > 0) {  // the same steps again, for the next members
             m->cal = start.cal;
@@ -1506,6 +1526,9 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             if (sample) ++taken;
             const bool record_tape = m->tape.on && (m->current_step + 1) % m->tape.every == 0;
             if (record_tape) ++tape_taken;
+            // (the spectra read the spectral state only: they never ask for the diagnostics-only outputs)
+            const bool record_spectra = m->spectra.on && (m->current_step + 1) % m->spectra.every == 0;
+            if (record_spectra) ++spectra_taken;
             const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip)) ? 1 : 0;
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
@@ -1572,6 +1595,14 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                         device_failed = true;
                     }
                 }
+                if (rc == SPD_OK && record_spectra) {  // behind the tape's sample, on the same stream
+                    const hipError_t e = spectra_sample(m, first, count, spectra0 + spectra_taken, gs[g]);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": spectra: " + hipGetErrorString(e));
+                        device_failed = true;
+                    }
+                }
                 first += count;
             }
             if (rc != SPD_OK) break;
@@ -1584,6 +1615,11 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             if (round == 0 && record_tape) {  // the sample's step and the date of the sampled state, kept beside its slot
                 m->tape.taken = tape0 + tape_taken;
                 int32_t *row = m->tape.rows.data() + 6 * static_cast<size_t>((m->tape.taken - 1) % m->tape.capacity);
+                row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+            }
+            if (round == 0 && record_spectra) {  // (the same for the spectra)
+                m->spectra.taken = spectra0 + spectra_taken;
+                int32_t *row = m->spectra.rows.data() + 6 * static_cast<size_t>((m->spectra.taken - 1) % m->spectra.capacity);
                 row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
             }
         }
@@ -1653,6 +1689,12 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
             m->tape.valid = false;
             m->tape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
                                   " of a checked call";
+        }
+    for (int i = 0; i < M && m->spectra.on && m->spectra.valid; ++i)
+        if (first_failed_step[i] >= 0) {  // (... and for the spectra)
+            m->spectra.valid = false;
+            m->spectra.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
+                                     " of a checked call";
         }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)
@@ -2485,6 +2527,194 @@ int spd_model_tape_read(spd_model_handle m, const char *name, int first, int cou
     const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
                                          static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % tp.capacity), tp.capacity,
                                          static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*; kernels: spectra.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr const char *kSpectraNames[SPECTRA_NNAMES] = {"ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum",
+                                                       "lnps_spectrum",   "t_mean",          "q_mean",     "lnps_mean"};
+int spectra_id(const char *name) {
+    for (int v = 0; name && v < SPECTRA_NNAMES; ++v)
+        if (std::strcmp(name, kSpectraNames[v]) == 0) return v;
+    return -1;
+}
+
+// the list of names of a call -> ids, in the order given (the arguments first: nothing here needs the device or a model)
+int spectra_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
+    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of names");
+    for (int k = 0; k < n_names; ++k) {
+        const int id = spectra_id(names[k]);
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown name '" + (names[k] ? names[k] : "(null)") +
+                                         "' (ke_rot_spectrum, ke_div_spectrum, t_spectrum, q_spectrum, lnps_spectrum, t_mean, q_mean, "
+                                         "lnps_mean)");
+        if (std::find(ids.begin(), ids.end(), id) != ids.end())
+            return m_fail(SPD_E_ARG, std::string(who) + ": name '" + names[k] + "' given twice");
+        ids.push_back(id);
+    }
+    return SPD_OK;
+}
+
+// the kernel's arguments but for the destinations: the members [first, first + count) of the state as it stands
+SpectraArgs spectra_args(const spd_model *m, unsigned mask, int first, int out_first) {
+    SpectraArgs a{};
+    a.vor = m->P.vor, a.div = m->P.div, a.t = m->P.t, a.tr = m->P.tr, a.ps = m->P.ps;
+    a.elm2 = m->ctx->dev.elm2;
+    a.mask = mask, a.first = first, a.out_first = out_first;
+    return a;
+}
+}  // namespace
+
+// a sample: one launch for the group's members, straight into ring slot (n - 1) % capacity
+static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
+    const spd_model::Spectra &sp = m->spectra;
+    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>((n - 1) % sp.capacity);
+    SpectraArgs a = spectra_args(m, sp.mask, first, 0);
+    for (int v = 0; v < SPECTRA_NNAMES; ++v)
+        if (sp.mask & (1u << v)) a.out[v] = static_cast<double *>(sp.alloc) + sp.offset[v] + slot * M * spectra_per_member(v);
+    return run_spectra(a, count, s);
+}
+
+int spd_model_spectra_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity) {
+    const char *who = "spd_model_spectra_configure";
+    // (the arguments first: nothing below needs the device)
+    std::vector<int> ids;
+    if (int rc = spectra_ids(who, names, n_names, ids)) return rc;
+    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+    if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
+    spd_model::Spectra &sp = m->spectra;
+    void *old = sp.alloc;
+    sp = spd_model::Spectra{};  // (off before anything below can fail)
+    if (old) M_HIP(hipFree(old));
+    if (n_names == 0) return SPD_OK;  // off
+    spd_model::Spectra next;
+    next.every = every;
+    next.capacity = capacity;
+    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
+    size_t per_slot = 0;  // doubles of a sample
+    for (int id : ids) {
+        next.mask |= 1u << id;
+        per_slot += M * spectra_per_member(id);
+    }
+    if (slots > (static_cast<size_t>(-1) / 2) / (per_slot * sizeof(double)))
+        return m_fail(SPD_E_ARG, std::string(who) + ": the size of the series does not fit size_t");
+    size_t at = 0;
+    for (int v = 0; v < SPECTRA_NNAMES; ++v)
+        if (next.mask & (1u << v)) {
+            next.offset[v] = at;
+            at += slots * M * spectra_per_member(v);
+        }
+    const size_t total = sample_up(at * sizeof(double));
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the spectra are off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the series (" + std::to_string(total) + " bytes asked for: " +
+                                        std::to_string(capacity) + " samples of " + std::to_string(per_slot * sizeof(double)) +
+                                        " bytes); the spectra are off");
+    }
+    next.alloc = p;
+    next.rows.assign(slots * 6, 0);
+    next.on = true;
+    sp = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_spectra_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: null model");
+    if (!m->spectra.on) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: no spectra configured (spd_model_spectra_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: a checked multi-step call is in flight; end it first");
+    m->spectra.taken = 0;  // (the next sample goes into slot 0: no device work)
+    m->spectra.valid = true;
+    m->spectra.invalid_why.clear();
+    return SPD_OK;
+}
+
+int spd_model_spectra_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_info: null model");
+    const spd_model::Spectra &sp = m->spectra;
+    if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_info: no spectra configured (spd_model_spectra_configure)");
+    if (taken) *taken = sp.taken;
+    if (held) *held = static_cast<int>(std::min<long long>(sp.taken, sp.capacity));
+    if (capacity) *capacity = sp.capacity;
+    if (every) *every = sp.every;
+    return SPD_OK;
+}
+
+int spd_model_spectra_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_times: null model");
+    const spd_model::Spectra &sp = m->spectra;
+    if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_times: no spectra configured (spd_model_spectra_configure)");
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_spectra_times: bad destination");
+    const long long held = std::min<long long>(sp.taken, sp.capacity), oldest = sp.taken - held;  // (sample numbers from 0)
+    int n = 0;
+    for (; n < held && n < max_rows; ++n)
+        std::memcpy(rows + 6 * static_cast<size_t>(n), sp.rows.data() + 6 * static_cast<size_t>((oldest + n) % sp.capacity), 6 * sizeof(int32_t));
+    return n;
+}
+
+int spd_model_spectra_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
+                           void *stream) {
+    const char *who = "spd_model_spectra_read";
+    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::Spectra &sp = m->spectra;
+    if (!sp.on) return m_fail(SPD_E_ARG, std::string(who) + ": no spectra configured (spd_model_spectra_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (!sp.valid) return m_fail(SPD_E_ARG, std::string(who) + ": the spectra are invalid until spd_model_spectra_reset: " + sp.invalid_why);
+    const int id = spectra_id(name);
+    if (id < 0 || !(sp.mask & (1u << id))) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured names");
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    const long long held = std::min<long long>(sp.taken, sp.capacity), oldest = sp.taken - held;
+    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
+        return m_fail(SPD_E_ARG, std::string(who) + ": sample range out of bounds (" + std::to_string(held) + " samples held)");
+    const size_t per = static_cast<size_t>(spectra_per_member(id));
+    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    if (count == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    const double *src = static_cast<const double *>(sp.alloc) + sp.offset[id] + static_cast<size_t>(first) * per;
+    const hipError_t e = run_spectra_gather(src, static_cast<double *>(dst_device), static_cast<int>(per),
+                                            static_cast<long>(static_cast<size_t>(m->M) * per), count, nt,
+                                            static_cast<int>((oldest + t0) % sp.capacity), sp.capacity, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+int spd_model_spectra_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, void *dst_device,
+                              size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_spectra_compute";
+    std::vector<int> ids;
+    if (int rc = spectra_ids(who, names, n_names, ids)) return rc;
+    if (int rc = member_range(m, first, count, who)) return rc;
+    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    size_t per = 0;
+    for (int id : ids) per += static_cast<size_t>(spectra_per_member(id));
+    const size_t need = static_cast<size_t>(count) * per * sizeof(double);
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    if (need == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    SpectraArgs a = spectra_args(m, 0, first, first);
+    double *at = static_cast<double *>(dst_device);
+    for (int id : ids) {  // [count][...] per name, one after the other in the order given
+        a.mask |= 1u << id;
+        a.out[id] = at;
+        at += static_cast<size_t>(count) * spectra_per_member(id);
+    }
+    const hipError_t e = run_spectra(a, count, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
 }

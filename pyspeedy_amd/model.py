@@ -430,6 +430,112 @@ class EnsembleModel:
                                                 out.numel() * out.element_size(), self._stream()), "spd_model_tape_read(%s)" % name)
         return out
 
+    # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
+    SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
+                     "lnps_mean")
+    # host arithmetic on what was read: name -> the stored names it needs
+    SPECTRA_DERIVED = {"ke_spectrum": ("ke_rot_spectrum", "ke_div_spectrum"), "ke_mean": ("ke_rot_spectrum", "ke_div_spectrum"),
+                       "ke_column": ("ke_rot_spectrum", "ke_div_spectrum")}
+    _SPECTRA_SHAPES = {"ke_rot_spectrum": (8, 32), "ke_div_spectrum": (8, 32), "t_spectrum": (8, 32), "q_spectrum": (8, 32),
+                       "lnps_spectrum": (32,), "t_mean": (8,), "q_mean": (8,), "lnps_mean": (1,)}
+
+    def spectra_configure(self, variables, every, capacity):
+        """Record `variables` (any of SPECTRA_NAMES, or of SPECTRA_DERIVED: the stored names they need are recorded) after every
+        step that leaves current_step at a multiple of `every`, inside run() / run_checked() calls of any length, into a ring in
+        device memory that keeps the last `capacity` samples of every member (float64).  Sums over the spectral coefficients: no
+        transform, one small launch per sample.  Empties the ring; an empty list switches the spectra off.  Synchronises the device."""
+        names = []
+        for v in variables:
+            for n in self.SPECTRA_DERIVED.get(str(v), (str(v),)):
+                if n not in names:
+                    names.append(n)
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_spectra_configure(self._m, arr, len(names), int(every), int(capacity)),
+                  "spd_model_spectra_configure")
+
+    def spectra_reset(self):
+        """Empty the ring of spectra (no device work); the next sample is the first."""
+        check(self._lib.spd_model_spectra_reset(self._m), "spd_model_spectra_reset")
+
+    def spectra_info(self):
+        """dict(taken, held, capacity, every): samples since the last reset, samples the ring holds (min(taken, capacity)), and
+        the configuration."""
+        taken, held, capacity, every = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.spd_model_spectra_info(self._m, C.byref(taken), C.byref(held), C.byref(capacity), C.byref(every)),
+              "spd_model_spectra_info")
+        return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value)
+
+    def _spectra_rows(self):
+        held = self.spectra_info()["held"]
+        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
+        n = self._lib.spd_model_spectra_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
+        if n < 0:
+            check(n, "spd_model_spectra_times")
+        return rows[:n]
+
+    def spectra_steps(self):
+        """The model's step counter after each held sample's step, oldest first (numpy int array)."""
+        return self._spectra_rows()[:, 0].astype(np.int64)
+
+    def spectra_times(self):
+        """The date of each held sample's state, oldest first (a list of datetime)."""
+        from datetime import datetime
+        return [datetime(*(int(v) for v in row[1:6])) for row in self._spectra_rows()]
+
+    def _spectra_derive(self, name, rot, div):
+        """ke_spectrum = rot + div [..., 8, 32]; ke_mean = its sum over l [..., 8]; ke_column = sum over the levels of dhs[k] *
+        ke_mean[k] [...] (the sigma-thickness weights: NOT weighted by the surface pressure)."""
+        ke = rot + div
+        if name == "ke_spectrum":
+            return ke
+        mean = ke.sum(dim=-1)
+        if name == "ke_mean":
+            return mean
+        dhs = torch.as_tensor(self.sp.table("dhs"), dtype=torch.float64, device=ke.device)
+        return (mean * dhs).sum(dim=-1)
+
+    def spectra(self, name, first=0, count=None, t0=0, nt=None):
+        """Members [first, first + count) and samples [t0, t0 + nt) of the held ones (oldest first) of one name: a float64 tensor
+        [count][nt][8][32] (ke_rot_spectrum, ke_div_spectrum, t_spectrum, q_spectrum, ke_spectrum), [count][nt][32]
+        (lnps_spectrum), [count][nt][8] (t_mean, q_mean, ke_mean), [count][nt][1] (lnps_mean) or [count][nt] (ke_column) on the
+        model's device.  Bin l of a spectrum is total wavenumber l."""
+        name = str(name)
+        if name in self.SPECTRA_DERIVED:
+            return self._spectra_derive(name, *(self.spectra(n, first, count, t0, nt) for n in self.SPECTRA_DERIVED[name]))
+        first, count = self._range(first, count)
+        t0 = int(t0)
+        nt = self.spectra_info()["held"] - t0 if nt is None else int(nt)
+        shape = self._SPECTRA_SHAPES.get(name, (1,))  # (an unknown name: the library says which ones it knows)
+        out = torch.empty((count, max(nt, 0)) + shape, dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_spectra_read(self._m, name.encode(), first, count, t0, nt, C.c_void_p(out.data_ptr()),
+                                                   out.numel() * 8, self._stream()), "spd_model_spectra_read(%s)" % name)
+        return out
+
+    def spectrum(self, names=None, first=0, count=None):
+        """The same quantities of the state as it stands, without a ring: dict name -> float64 tensor [count][...] on the model's
+        device for `names` (default: all of SPECTRA_NAMES; the SPECTRA_DERIVED names are accepted).  One launch."""
+        asked = [str(n) for n in (self.SPECTRA_NAMES if names is None else names)]
+        stored = []
+        for a in asked:
+            for n in self.SPECTRA_DERIVED.get(a, (a,)):
+                if n not in stored:
+                    stored.append(n)
+        first, count = self._range(first, count)
+        sizes = [count * int(np.prod(self._SPECTRA_SHAPES.get(n, (1,)))) for n in stored]
+        buf = torch.empty(sum(sizes), dtype=torch.float64, device=self.sp.device)
+        arr = (C.c_char_p * max(len(stored), 1))(*[n.encode() for n in stored])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_spectra_compute(self._m, arr, len(stored), first, count, C.c_void_p(buf.data_ptr()),
+                                                      buf.numel() * 8, self._stream()), "spd_model_spectra_compute")
+        got, at = {}, 0
+        for n, size in zip(stored, sizes):
+            got[n] = buf[at:at + size].view((count,) + self._SPECTRA_SHAPES[n])
+            at += size
+        return {a: self._spectra_derive(a, *(got[n] for n in self.SPECTRA_DERIVED[a])) if a in self.SPECTRA_DERIVED else got[a]
+                for a in asked}
+
     # ---- pressure-level fields and mean sea-level pressure (spd_model_plev_*, include/pyspeedy_amd.h) -------------------
     PLEV_VARIABLES = ("u_plev", "v_plev", "t_plev", "q_plev", "z_plev", "mslp")
 

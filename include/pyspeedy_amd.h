@@ -463,6 +463,49 @@ int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *ca
 int spd_model_tape_times(spd_model_handle m, int32_t *rows, int max_rows);
 int spd_model_tape_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
                         void *stream);
+/* The ensemble tape: time series of the ensemble mean and spread, recorded on the device inside spd_model_step /
+ * spd_model_step_checked_begin calls of any length.  A third ring in device memory, per model, holds for each of the last `capacity`
+ * samples and each chosen variable the mean over ALL members of the model and the sum of squared deviations from that mean (M2), per
+ * grid point, fp64 -- two planes per sample where the tape holds one per member.  Variables: the fourteen names of the statistics
+ * (the six pressure-level ones after spd_model_plev_configure), in export units.  Sampling rule: the tape's, with the ensemble tape's
+ * own `every`; each member group takes the sample on its own stream behind the spectra's.  The value of member j that enters sample
+ * n is exactly what an fp64 tape would hold for member j at that sample; the reduction (Welford's update over the members of a
+ * launch, in member order) is the only new arithmetic.  Recording changes nothing of the run; statistics, tape, spectra and ensemble
+ * tape are independent (own `every`, slab and tables), and with the ensemble tape off no launch of a step changes.
+ * Members reach a sample in pieces -- member groups on up to 4 streams, rounds of block_members one after the other on them -- so a
+ * slot holds one partial (mean, M2) per group stream, written from that stream only (no atomics, no waits between streams), and a
+ * read merges the partials in the fixed order of the groups with Chan's formula.  For a given launch plan (members, member groups,
+ * block_members, the lengths of the calls) the result is repeatable bit for bit; between plans mean and M2 differ at round-off
+ * level.  Memory: capacity x 4 x planes x 4608 x 16 bytes, whatever the number of members.
+ *   _configure  allocates the ring (one hipMalloc of its own with slab and tables; synchronises the device) and empties it;
+ *               n_names = 0 switches the ensemble tape off and frees it.  SPD_E_ARG, checked in this order before a model or a device
+ *               is needed: an unknown name, a name given twice, every < 1, capacity < 1, a null model; then a pressure-level name
+ *               before spd_model_plev_configure, or a checked call in flight.  SPD_E_DEVICE with the number of bytes asked for when
+ *               the allocation fails: the ensemble tape is then off and the model as usable as before.  spd_model_plev_configure is
+ *               refused while the ensemble tape holds a pressure-level name.
+ *   _reset      empties the ring (host only, no device work).  spd_model_init does the same.
+ *   _info       taken: samples since the last reset; held = min(taken, capacity); members: what a sample reduces over; any pointer
+ *               may be NULL.
+ *   _times      rows[held][6] for the held samples, oldest first: the absolute step counter after the sampled step, then year,
+ *               month, day, hour, minute of the sampled state (host memory).  Returns the number of rows written (<= max_rows).
+ *   _read       samples [t0, t0 + nt) of the held ones, oldest first, of one variable into dst_device[nt][levels][48][96] doubles
+ *               ([nt][48][96] for ps_grid, precnv, precls, mslp), stream-ordered; dst_device must be 16-byte aligned.  kind:
+ *               SPD_ENS_MEAN, SPD_ENS_M2, or SPD_ENS_STD, the unbiased standard deviation sqrt(M2 / (members - 1)) (one member:
+ *               NaN, as spd_model_stats_ensemble).  SPD_E_SIZE when dst_bytes is too small.  (members, mean, M2) of several
+ *               models combine into the moments of all their members by the same formula (pyspeedy_amd.ensemble.merge_moments).
+ * Reads fail (SPD_E_ARG, with the reason) while a checked call is in flight and after a checked call that reported a failed range
+ * check (the message names the member and the step): the ring stays invalid until _reset or spd_model_init.
+ * spd_model_copy_member does not carry the ring, and the outer boundary (spd_parallel_step*) does not keep it across the models
+ * it merges and splits. */
+#define SPD_ENS_MEAN 0
+#define SPD_ENS_STD 1
+#define SPD_ENS_M2 2
+int spd_model_enstape_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity);
+int spd_model_enstape_reset(spd_model_handle m);
+int spd_model_enstape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *members);
+int spd_model_enstape_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t0, int nt, void *dst_device, size_t dst_bytes,
+                           void *stream);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

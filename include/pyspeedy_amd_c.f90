@@ -8,7 +8,8 @@
 !!   init            -> spd_model_init                    step / parallel_step -> spd_model_step
 !!   check           -> spd_model_check                   transform_spectral2grid ... -> spd_model_spectral2grid ...
 !! and, without a counterpart there: time statistics on the device (spd_model_stats_*), pressure-level fields (spd_model_plev_*),
-!! time series recorded on the device (spd_model_tape_*) and spectra of the spectral state (spd_model_spectra_*)
+!! time series recorded on the device (spd_model_tape_*), spectra of the spectral state (spd_model_spectra_*) and the series of
+!! the ensemble mean and spread (spd_model_enstape_*)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -16,6 +17,7 @@ module pyspeedy_amd_c
     integer(c_int), parameter :: SPD_OK = 0, SPD_E_ARG = -1, SPD_E_DEVICE = -2, SPD_E_SIZE = -3
     integer(c_int), parameter :: SPD_STATS_MEAN = 0, SPD_STATS_VARIANCE = 1, SPD_STATS_STD = 2
     integer(c_int), parameter :: SPD_TAPE_F32 = 0, SPD_TAPE_F64 = 1
+    integer(c_int), parameter :: SPD_ENS_MEAN = 0, SPD_ENS_STD = 1, SPD_ENS_M2 = 2
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -235,6 +237,41 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model, dst_device, stream
             character(kind=c_char), intent(in) :: name(*)
             integer(c_int), value :: first, count, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        ! the ensemble tape: mean and spread over all members of a model as a time series recorded on the device inside
+        ! spd_model_step calls (pyspeedy_amd.h: spd_model_enstape_*).  names as for the statistics; rows as the tape's; kind:
+        ! SPD_ENS_MEAN (0) / SPD_ENS_STD (1) / SPD_ENS_M2 (2); _read: (96, 48[, levels], nt) real(c_double)
+        integer(c_int) function spd_model_enstape_configure(model, names, n_names, every, capacity) &
+                bind(C, name="spd_model_enstape_configure")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), value :: n_names, every, capacity
+        end function
+        integer(c_int) function spd_model_enstape_reset(model) bind(C, name="spd_model_enstape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_enstape_info(model, taken, held, capacity, every, members) &
+                bind(C, name="spd_model_enstape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken
+            integer(c_int), intent(out) :: held, capacity, every, members
+        end function
+        integer(c_int) function spd_model_enstape_times(model, rows, max_rows) bind(C, name="spd_model_enstape_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_enstape_read(model, name, kind, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_enstape_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: kind, t0, nt
             integer(c_size_t), value :: dst_bytes
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on

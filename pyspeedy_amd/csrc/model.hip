@@ -29,6 +29,7 @@
 #include "stats.hpp"
 #include "spectra.hpp"
 #include "tape.hpp"
+#include "enstape.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
 
@@ -218,8 +219,8 @@ struct spd_model {
     FieldDesc *exp_inv_table[2] = {nullptr, nullptr}, *exp_fwd_table[2] = {nullptr, nullptr};  // 41 / 40 per member; [phi buffer]
     // What the front end of a sample (statistics or tape) runs and where it writes: vort2vel when u or v is wanted, the export
     // transforms over a descriptor table ([phi buffer]) whose destinations are the slab [M][slab_fields][4608], and the
-    // pressure-level kernel (raw = 1) from the slab's transformed planes into its further planes.  The statistics and the tape
-    // each own one, in their own allocation.
+    // pressure-level kernel (raw = 1) from the slab's transformed planes into its further planes.  The statistics, the tape
+    // and the ensemble tape each own one, in their own allocation.
     struct SampleFront {
         bool uv = false, precip = false;
         // slab_fields: planes of a member in the slab; the first xf_fields of them are written by the export transforms, the
@@ -280,6 +281,28 @@ struct spd_model {
         void *alloc = nullptr;
         size_t offset[SPECTRA_NNAMES] = {};  // doubles from `alloc` to slot 0, member 0 of a name of the mask
     } spectra;
+    // The ensemble tape (spd_model_enstape_*): a ring of the last `capacity` samples of the mean over all members and of the sum of
+    // squared deviations from it (M2), per grid point, fp64, taken by the tape's rule (its own `every`, slab and tables) behind the
+    // spectra's sample.  One allocation of its own (hipMalloc): mean and M2 rings, each [slot][4][planes][4608] -- one partial per
+    // group stream, written only from that stream (enstape.hpp) --, then slab, tables and the plane descriptors of the fold kernel.
+    // Sample n (1-based since the last reset) lies in slot (n - 1) % capacity; its step and date (`rows`) and the members already
+    // folded into each of its partials (`counts`) are kept on the host at issue time.
+    struct EnsTape : SampleFront {
+        struct Var {
+            int id, levels;
+            size_t first_plane;  // planes of the variables before this one
+        };
+        bool on = false, valid = true;
+        int every = 1, capacity = 0, nplanes = 0;
+        long long taken = 0;
+        std::string invalid_why;
+        std::vector<Var> vars;
+        std::vector<int32_t> rows;  // [capacity][6]: absolute step after the sampled step, year, month, day, hour, minute
+        std::vector<int> counts;    // [capacity][4]: members folded into partial (slot, group)
+        void *alloc = nullptr;
+        double *mean = nullptr, *m2 = nullptr;
+        EnsTapePlane *planes = nullptr;
+    } enstape;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {
@@ -764,6 +787,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->stats.alloc) (void)hipFree(m->stats.alloc);
     if (m->tape.alloc) (void)hipFree(m->tape.alloc);
     if (m->spectra.alloc) (void)hipFree(m->spectra.alloc);
+    if (m->enstape.alloc) (void)hipFree(m->enstape.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1305,6 +1329,8 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->tape.valid = true;
     m->spectra.taken = 0;  // (... and an empty series of spectra)
     m->spectra.valid = true;
+    m->enstape.taken = 0;  // (... and an empty ensemble tape)
+    m->enstape.valid = true;
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1412,6 +1438,7 @@ static int ensure_group_streams(spd_model *m, int G) {
 static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_stats_configure)
 static hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);   // (with spd_model_tape_configure)
 static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_spectra_configure)
+static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s);  // (with spd_model_enstape_configure)
 
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
@@ -1502,8 +1529,14 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     const long long samples0 = m->stats.samples;  // (statistics: every round takes the same samples)
     const long long tape0 = m->tape.taken;        // (... and writes the same slots of the tape, for its own members)
     const long long spectra0 = m->spectra.taken;  // (... and of the spectra)
+    const long long enstape0 = m->enstape.taken;  // (... and folds its members into the same slots of the ensemble tape)
+    // the ensemble tape's last sample of this call: a sample whose slot a later sample of the SAME call takes again is not folded at
+    // all -- nobody can read it, and with rounds its members would otherwise land in the partials of the sample that replaced it
+    long long enstape_last = enstape0;
+    if (m->enstape.on)
+        enstape_last += (static_cast<long long>(m->current_step) + nsteps) / m->enstape.every - m->current_step / m->enstape.every;
     for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
-        long long taken = 0, tape_taken = 0, spectra_taken = 0;
+        long long taken = 0, tape_taken = 0, spectra_taken = 0, enstape_taken = 0;
         const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
         if (round > 0) {  // the same steps again, for the next members
             m->cal = start.cal;
@@ -1529,7 +1562,16 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             // (the spectra read the spectral state only: they never ask for the diagnostics-only outputs)
             const bool record_spectra = m->spectra.on && (m->current_step + 1) % m->spectra.every == 0;
             if (record_spectra) ++spectra_taken;
-            const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip)) ? 1 : 0;
+            const bool record_enstape = m->enstape.on && (m->current_step + 1) % m->enstape.every == 0;
+            if (record_enstape) ++enstape_taken;
+            const bool fold_enstape = record_enstape && enstape0 + enstape_taken + m->enstape.capacity > enstape_last;
+            // (round 0 opens the sample: its slot holds no member yet, in any of its partials)
+            if (fold_enstape && round == 0) {
+                int *held = m->enstape.counts.data() + kEnsTapeGroups * static_cast<size_t>((enstape0 + enstape_taken - 1) % m->enstape.capacity);
+                std::fill(held, held + kEnsTapeGroups, 0);
+            }
+            const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip) ||
+                              (fold_enstape && m->enstape.precip)) ? 1 : 0;
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
             // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
@@ -1603,6 +1645,14 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                         device_failed = true;
                     }
                 }
+                if (rc == SPD_OK && fold_enstape) {  // behind the spectra's sample, on the same stream: partial g of the slot
+                    const hipError_t e = enstape_sample(m, first, count, enstape0 + enstape_taken, g, gs[g]);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": ensemble tape: " + hipGetErrorString(e));
+                        device_failed = true;
+                    }
+                }
                 first += count;
             }
             if (rc != SPD_OK) break;
@@ -1620,6 +1670,11 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             if (round == 0 && record_spectra) {  // (the same for the spectra)
                 m->spectra.taken = spectra0 + spectra_taken;
                 int32_t *row = m->spectra.rows.data() + 6 * static_cast<size_t>((m->spectra.taken - 1) % m->spectra.capacity);
+                row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+            }
+            if (round == 0 && record_enstape) {  // (... and for the ensemble tape)
+                m->enstape.taken = enstape0 + enstape_taken;
+                int32_t *row = m->enstape.rows.data() + 6 * static_cast<size_t>((m->enstape.taken - 1) % m->enstape.capacity);
                 row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
             }
         }
@@ -1694,6 +1749,12 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
         if (first_failed_step[i] >= 0) {  // (... and for the spectra)
             m->spectra.valid = false;
             m->spectra.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
+                                     " of a checked call";
+        }
+    for (int i = 0; i < M && m->enstape.on && m->enstape.valid; ++i)
+        if (first_failed_step[i] >= 0) {  // (... and for the ensemble tape)
+            m->enstape.valid = false;
+            m->enstape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
                                      " of a checked call";
         }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
@@ -2243,6 +2304,20 @@ static hipError_t tape_sample(spd_model *m, int first, int count, long long n, h
     return e;
 }
 
+// ... and of the ensemble tape: the front end into its own slab, then the fold of these members into partial `group` of ring slot
+// (n - 1) % capacity, behind the members the partial already holds (rounds: the same stream, one after the other)
+static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s) {
+    spd_model::EnsTape &et = m->enstape;
+    const int slot = static_cast<int>((n - 1) % et.capacity);
+    int &held = et.counts[static_cast<size_t>(slot) * kEnsTapeGroups + group];
+    hipError_t e = sample_front(m, et, first, count, s);
+    if (e == hipSuccess)
+        e = run_enstape_fold(et.planes, et.nplanes, et.slab, et.slab_fields, first, count, slot * kEnsTapeGroups + group, held,
+                             m->stored32 ? 1 : 0, s);
+    if (e == hipSuccess) held += count;
+    return e;
+}
+
 int spd_model_stats_configure(spd_model_handle m, const char *const *names, int n_names, int every, int with_variance) {
     const char *who = "spd_model_stats_configure";
     // (the arguments first: nothing below needs the device)
@@ -2720,6 +2795,156 @@ int spd_model_spectra_compute(spd_model_handle m, const char *const *names, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the ensemble tape: mean and spread over the members as a time series (spd_model_enstape_*; kernels: enstape.hip)
+// ---------------------------------------------------------------------------------------------------------------
+int spd_model_enstape_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity) {
+    const char *who = "spd_model_enstape_configure";
+    // (the arguments first: nothing below needs the device)
+    std::vector<int> ids;
+    if (int rc = sample_ids(who, names, n_names, ids)) return rc;
+    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+    if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    for (size_t k = 0; k < ids.size(); ++k)
+        if (ids[k] >= kPlevFirst && m->plev.n == 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
+    spd_model::EnsTape &et = m->enstape;
+    void *old = et.alloc;
+    et = spd_model::EnsTape{};  // (off before anything below can fail)
+    if (old) M_HIP(hipFree(old));
+    if (n_names == 0) return SPD_OK;  // off
+    spd_model::EnsTape next;
+    next.every = every;
+    next.capacity = capacity;
+    SamplePlan plan;
+    plan_sample(m, ids, next, plan);
+    const size_t slots = static_cast<size_t>(capacity);
+    for (const auto &v : plan.vars) next.vars.push_back({v.id, v.levels, v.first_plane});
+    next.nplanes = static_cast<int>(plan.planes);
+    // one allocation: mean ring | M2 ring | slab | tables[2] | plane descriptors
+    const size_t per_slot = kEnsTapeGroups * plan.planes * NG * sizeof(double);  // of ONE of the two rings
+    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 4) / per_slot)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape's size does not fit size_t");
+    const size_t ring = sample_up(slots * per_slot), desc = sample_up(plan.planes * sizeof(EnsTapePlane));
+    const size_t total = 2 * ring + plan.slab_bytes + 2 * plan.table_bytes + desc;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the ensemble tape is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the ensemble tape (" + std::to_string(total) + " bytes asked for: " +
+                                        std::to_string(capacity) + " samples of " + std::to_string(2 * per_slot) +
+                                        " bytes); the ensemble tape is off");
+    }
+    char *at = static_cast<char *>(p);
+    next.alloc = p;
+    next.mean = reinterpret_cast<double *>(at), at += ring;
+    next.m2 = reinterpret_cast<double *>(at), at += ring;
+    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
+    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
+    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
+    next.planes = reinterpret_cast<EnsTapePlane *>(at);
+    std::vector<int> slab_plane;
+    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<EnsTapePlane> host_planes;
+    for (const auto &v : next.vars)
+        for (int k = 0; k < v.levels; ++k) {
+            EnsTapePlane d{};
+            d.slab_plane = slab_plane[host_planes.size()];
+            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
+            d.unit = kStatsCatalogue[v.id].unit;
+            d.mean = next.mean + (v.first_plane + static_cast<size_t>(k)) * NG;
+            d.m2 = next.m2 + (v.first_plane + static_cast<size_t>(k)) * NG;
+            host_planes.push_back(d);
+        }
+    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(EnsTapePlane), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    next.rows.assign(slots * 6, 0);
+    next.counts.assign(slots * kEnsTapeGroups, 0);
+    next.on = true;
+    et = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_enstape_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: null model");
+    if (!m->enstape.on) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: no ensemble tape configured (spd_model_enstape_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: a checked multi-step call is in flight; end it first");
+    m->enstape.taken = 0;  // (the next sample goes into slot 0 and opens its partials anew: no device work)
+    m->enstape.valid = true;
+    m->enstape.invalid_why.clear();
+    return SPD_OK;
+}
+
+int spd_model_enstape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *members) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_info: null model");
+    const spd_model::EnsTape &et = m->enstape;
+    if (!et.on) return m_fail(SPD_E_ARG, "spd_model_enstape_info: no ensemble tape configured (spd_model_enstape_configure)");
+    if (taken) *taken = et.taken;
+    if (held) *held = static_cast<int>(std::min<long long>(et.taken, et.capacity));
+    if (capacity) *capacity = et.capacity;
+    if (every) *every = et.every;
+    if (members) *members = m->M;
+    return SPD_OK;
+}
+
+int spd_model_enstape_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_times: null model");
+    const spd_model::EnsTape &et = m->enstape;
+    if (!et.on) return m_fail(SPD_E_ARG, "spd_model_enstape_times: no ensemble tape configured (spd_model_enstape_configure)");
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_enstape_times: bad destination");
+    const long long held = std::min<long long>(et.taken, et.capacity), oldest = et.taken - held;  // (sample numbers from 0)
+    int n = 0;
+    for (; n < held && n < max_rows; ++n)
+        std::memcpy(rows + 6 * static_cast<size_t>(n), et.rows.data() + 6 * static_cast<size_t>((oldest + n) % et.capacity), 6 * sizeof(int32_t));
+    return n;
+}
+
+int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_enstape_read";
+    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::EnsTape &et = m->enstape;
+    if (!et.on) return m_fail(SPD_E_ARG, std::string(who) + ": no ensemble tape configured (spd_model_enstape_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (!et.valid)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape is invalid until spd_model_enstape_reset: " + et.invalid_why);
+    const int id = stats_id(name);
+    const spd_model::EnsTape::Var *v = nullptr;
+    for (const auto &x : et.vars)
+        if (x.id == id) v = &x;
+    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
+    if (kind != SPD_ENS_MEAN && kind != SPD_ENS_STD && kind != SPD_ENS_M2)
+        return m_fail(SPD_E_ARG, std::string(who) + ": kind must be SPD_ENS_MEAN, SPD_ENS_STD or SPD_ENS_M2");
+    const long long held = std::min<long long>(et.taken, et.capacity), oldest = et.taken - held;
+    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
+        return m_fail(SPD_E_ARG, std::string(who) + ": sample range out of bounds (" + std::to_string(held) + " samples held)");
+    const size_t per = static_cast<size_t>(v->levels) * NG, need = static_cast<size_t>(nt) * per * sizeof(double);
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    const int slot0 = static_cast<int>((oldest + t0) % et.capacity);
+    std::vector<int> counts(static_cast<size_t>(nt) * kEnsTapeGroups);  // of the samples of the read, in its order
+    for (int t = 0; t < nt; ++t)
+        std::memcpy(counts.data() + static_cast<size_t>(t) * kEnsTapeGroups,
+                    et.counts.data() + static_cast<size_t>((slot0 + static_cast<long long>(t)) % et.capacity) * kEnsTapeGroups,
+                    kEnsTapeGroups * sizeof(int));
+    const size_t var_at = v->first_plane * NG;
+    const hipError_t e = run_enstape_read(et.mean + var_at, et.m2 + var_at, static_cast<long>(per), et.nplanes, kind, nt, slot0, et.capacity,
+                                          counts.data(), static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // pressure-level fields and mean sea-level pressure (spd_model_plev_*; kernel: plev.hip)
 // ---------------------------------------------------------------------------------------------------------------
 static int plev_id(const char *name) {
@@ -2747,6 +2972,9 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
                                                     "(spd_model_stats_configure)");
     if (m->tape.on && m->tape.plev.mask)
         return m_fail(SPD_E_ARG, std::string(who) + ": the tape holds a pressure-level variable; switch it off first (spd_model_tape_configure)");
+    if (m->enstape.on && m->enstape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_enstape_configure)");
     spd_model::Plev &pl = m->plev;
     pl.n = n;
     for (int j = 0; j < kPlevMaxLevels; ++j) {

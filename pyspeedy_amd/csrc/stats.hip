@@ -10,6 +10,7 @@
 
 #include <cmath>
 
+#include "export_unit.hpp"
 #include "stats.hpp"
 #include "tables.hpp"
 
@@ -33,9 +34,7 @@ __global__ __launch_bounds__(kT) void stats_accumulate_kernel(const StatsPlane *
         x = static_cast<double>(static_cast<const float *>(d.src)[i * NG + p]);
     else
         x = static_cast<const double *>(d.src)[i * NG + p];
-    if (d.unit == 1) x = x * static_cast<double>(1.0e-3f);              // q: g/kg -> kg/kg
-    else if (d.unit == 2) x = x / static_cast<double>(9.81f);           // phi: m^2/s^2 -> m
-    else if (d.unit == 3) x = static_cast<double>(1.e+5f) * exp(x);     // ln(ps / 1e5 Pa) -> Pa
+    x = export_unit(x, d.unit);
     double *mean = d.mean + i * d.member_stride + p;
     double *m2 = d.m2 ? d.m2 + i * d.member_stride + p : nullptr;
     if (n == 1) {  // the first sample of a period: nothing is read (reset needs no device work)

@@ -10,6 +10,7 @@
 
 #include <cmath>
 
+#include "export_unit.hpp"
 #include "stream_store.hpp"
 #include "tables.hpp"
 #include "tape.hpp"
@@ -38,13 +39,6 @@ __device__ __forceinline__ T stream_load_global(const T *p) {
 template <typename T>
 __device__ __forceinline__ void stream_store_global(T *p, T v) {
     __builtin_nontemporal_store(v, (__attribute__((address_space(1))) T *)p);
-}
-
-__device__ __forceinline__ double export_unit(double x, int unit) {
-    if (unit == 1) return x * static_cast<double>(1.0e-3f);          // q: g/kg -> kg/kg
-    if (unit == 2) return x / static_cast<double>(9.81f);            // phi: m^2/s^2 -> m
-    if (unit == 3) return static_cast<double>(1.e+5f) * exp(x);      // ln(ps / 1e5 Pa) -> Pa
-    return x;
 }
 
 // blockIdx.x: pairs of points, blockIdx.y: plane, blockIdx.z: member of the group

@@ -127,3 +127,35 @@ def ensemble_mean_spread(values, dist, ddof=1):
         dist.all_reduce(ssq, op=dist.ReduceOp.SUM)
     spread = torch.sqrt(ssq / torch.clamp(n - ddof, min=1.0))
     return mean, spread
+
+
+def merge_moments(parts, ddof=1):
+    """Moments of the union of disjoint groups of members from the moments of each group (Chan's pairwise merge, fp64).
+
+    parts: a list of (n, mean, m2) -- members of the group, their mean and the sum of their squared deviations from it, per
+    point (torch tensors of one shape) -- as EnsembleModel.enstape_moments gives them for one device model, gathered from the
+    models of a process or from the ranks of a job.  Entries with n = 0 are skipped (a rank that owns no member).  Merged in
+    list order: n = na + nb, d = mean_b - mean_a, mean = mean_a + d nb / n, m2 = m2_a + m2_b + d^2 na nb / n.
+    Returns (n, mean, std) with std = sqrt(m2 / (n - ddof)) (NaN where n <= ddof)."""
+    import torch
+    n, mean, m2 = 0, None, None
+    for nb, mean_b, m2_b in parts:
+        nb = int(nb)
+        if nb < 0:
+            raise ValueError("a group of %d members" % nb)
+        if nb == 0:
+            continue
+        mean_b, m2_b = mean_b.to(torch.float64), m2_b.to(torch.float64)
+        if n == 0:
+            n, mean, m2 = nb, mean_b.clone(), m2_b.clone()
+            continue
+        total = n + nb
+        d = mean_b - mean
+        mean = mean + d * (nb / total)
+        m2 = m2 + m2_b + d * d * (n * nb / total)
+        n = total
+    if n == 0:
+        raise ValueError("no members to merge")
+    dof = n - ddof
+    std = torch.sqrt(m2 / dof) if dof > 0 else torch.full_like(m2, float("nan"))
+    return n, mean, std

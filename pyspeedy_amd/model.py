@@ -430,6 +430,70 @@ class EnsembleModel:
                                                 out.numel() * out.element_size(), self._stream()), "spd_model_tape_read(%s)" % name)
         return out
 
+    # ---- the ensemble tape: series of the mean and spread over the members (spd_model_enstape_*, include/pyspeedy_amd.h) ---
+    def enstape_configure(self, variables, every, capacity):
+        """Record the ensemble mean and spread of `variables` (any of STATS_VARIABLES) after every step that leaves current_step
+        at a multiple of `every`, inside run() / run_checked() calls of any length, into a ring in device memory that keeps the last
+        `capacity` samples: per grid point the mean over all members of this model and the sum of squared deviations from it,
+        float64 -- two planes per sample and member group, whatever the number of members.  Empties the ring; an empty list
+        switches it off and frees it.  Synchronises the device."""
+        names = [str(v) for v in variables]
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_enstape_configure(self._m, arr, len(names), int(every), int(capacity)),
+                  "spd_model_enstape_configure")
+
+    def enstape_reset(self):
+        """Empty the ensemble tape (no device work); the next sample is the first."""
+        check(self._lib.spd_model_enstape_reset(self._m), "spd_model_enstape_reset")
+
+    @property
+    def enstape_info(self):
+        """dict(taken, held, capacity, every, members): samples since the last reset, samples the ring holds (min(taken,
+        capacity)), the configuration, and the number of members a sample reduces over."""
+        taken, held, capacity, every, members = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.spd_model_enstape_info(self._m, C.byref(taken), C.byref(held), C.byref(capacity), C.byref(every),
+                                               C.byref(members)), "spd_model_enstape_info")
+        return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, members=members.value)
+
+    def _enstape_rows(self):
+        held = self.enstape_info["held"]
+        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
+        n = self._lib.spd_model_enstape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
+        if n < 0:
+            check(n, "spd_model_enstape_times")
+        return rows[:n]
+
+    def enstape_steps(self):
+        """The model's step counter after each held sample's step, oldest first (numpy int array)."""
+        return self._enstape_rows()[:, 0].astype(np.int64)
+
+    def enstape_times(self):
+        """The date of each held sample's state, oldest first (a list of datetime)."""
+        from datetime import datetime
+        return [datetime(*(int(v) for v in row[1:6])) for row in self._enstape_rows()]
+
+    def _enstape_read(self, name, kind, t0, nt):
+        t0 = int(t0)
+        nt = self.enstape_info["held"] - t0 if nt is None else int(nt)
+        out = torch.empty((max(nt, 0),) + self._stats_shape(name), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_enstape_read(self._m, name.encode(), kind, t0, nt, C.c_void_p(out.data_ptr()), out.numel() * 8,
+                                                   self._stream()), "spd_model_enstape_read(%s)" % name)
+        return out
+
+    def enstape(self, name, t0=0, nt=None):
+        """(mean, std) over the members for the samples [t0, t0 + nt) of the held ones (oldest first) of one variable: float64
+        tensors [nt][levels][48][96] ([nt][48][96] for one-level names) on the model's device; std is the unbiased standard
+        deviation (ddof 1; NaN for a model of one member)."""
+        return (self._enstape_read(name, _lib.SPD_ENS_MEAN, t0, nt), self._enstape_read(name, _lib.SPD_ENS_STD, t0, nt))
+
+    def enstape_moments(self, name, t0=0, nt=None):
+        """(members, mean, m2) of the same samples: m2 is the sum over the members of the squared deviations from the mean.  What
+        pyspeedy_amd.ensemble.merge_moments combines across several models or ranks."""
+        return (self.enstape_info["members"], self._enstape_read(name, _lib.SPD_ENS_MEAN, t0, nt),
+                self._enstape_read(name, _lib.SPD_ENS_M2, t0, nt))
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

@@ -506,6 +506,54 @@ int spd_model_enstape_info(spd_model_handle m, long long *taken, int *held, int 
 int spd_model_enstape_times(spd_model_handle m, int32_t *rows, int max_rows);
 int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t0, int nt, void *dst_device, size_t dst_bytes,
                            void *stream);
+/* The accumulation tape: window sums, means, minima and maxima of the column physics' 2-D outputs, accumulated on the device behind
+ * EVERY step of spd_model_step / spd_model_step_checked_begin calls of any length.  The other recorders sample the state as it
+ * stands on every n-th step; this one keeps what fell or flowed in between: the precipitation of a day, the mean outgoing longwave
+ * of a month, the strongest convective rain of a day.  An entry is a pair (name, op).  Names, one plane each: precnv, precls, cbmf,
+ * olr, tsr, ssr, ssrd, slr, slrd; three planes each (land, sea, weighted by the land fraction, the registry's order): ustr, vstr,
+ * shf, evap, slru.  hfluxn and qcloud_equiv are refused by name: not every plane of them is stored on every step.  Ops: SPD_ACC_SUM,
+ * SPD_ACC_MEAN, SPD_ACC_MIN, SPD_ACC_MAX.  Values are in the registry's own unit (these names carry no export conversion).
+ * A window closes after every step that leaves the model's absolute step counter at a multiple of `every` (the tape's rule) and
+ * holds the values the column physics stored in each step since the previous close; the first window after _configure, _reset or
+ * spd_model_init (or after the step counter was set by spd_model_mark_initialized / spd_model_set_control) starts at the model's
+ * current step and may be shorter than `every`; its number of steps n is kept beside the slot.  Windows run across call boundaries:
+ * the accumulators are device memory.  The arithmetic is fixed, so the result does not depend on the launch plan (members, member
+ * groups, block_members, the lengths of the calls): sum in fp64, the values added in step order starting from the first value
+ * itself; mean, that sum divided by n (one IEEE division at the close); min / max, acc = x < acc ? x : acc and acc = x > acc ? x :
+ * acc starting from the first value; sources stored as fp32 (physics_storage32) are widened to fp64 first.  Window k (from 1 since
+ * the last reset) lies in ring slot (k - 1) % capacity; the ring holds, per entry, [slot][members][planes][4608] elements,
+ * SPD_TAPE_F64 (the fp64 results) or SPD_TAPE_F32 (each rounded to the nearest float).  While the recorder is on every step stores
+ * its diagnostics-only outputs (as the option diag_every_step does), which changes no state; nothing else of a step changes, and
+ * with the recorder off no launch of a step changes.  It is independent of statistics, tape, spectra and ensemble tape.
+ *   _configure  allocates ring, accumulators (only those an entry needs) and tables in one hipMalloc of its own (synchronises the
+ *               device) and empties the ring; n_entries = 0 switches the recorder off and frees it.  SPD_E_ARG, checked in this order
+ *               before a model or a device is needed: an unknown (or refused) name, an unknown op, the same (name, op) twice,
+ *               every < 1, capacity < 1, an unknown dtype, a null model; then a checked call in flight.  SPD_E_DEVICE with the
+ *               number of bytes asked for when the allocation fails: the recorder is then off and the model as usable as before.
+ *   _reset      empties the ring and starts a new window at the model's current step (host only, no device work).
+ *               spd_model_init does the same.
+ *   _info       taken: windows closed since the last reset; held = min(taken, capacity); any pointer may be NULL.
+ *   _times      rows[held][7] for the held windows, oldest first: the absolute step counter after the window's last step, then
+ *               year, month, day, hour, minute of that state, then n, the number of steps in the window (host memory).  Returns the
+ *               number of rows written (at most max_rows).
+ *   _read       members [first, first + count) and windows [t0, t0 + nt) of the held ones, oldest first, of one entry into
+ *               dst_device[count][nt][planes][48][96] ([count][nt][48][96] for a one-plane name) in the ring's dtype, stream-ordered;
+ *               dst_device must be 16-byte aligned.  SPD_E_SIZE when dst_bytes is too small.
+ * Reads fail (SPD_E_ARG, with the reason) while a checked call is in flight and after a checked call that reported a failed range
+ * check (the message names the member and the step): the series stays invalid until _reset or spd_model_init.
+ * spd_model_copy_member does not carry the recorder, and the outer boundary (spd_parallel_step*) does not keep it across the
+ * models it merges and splits. */
+#define SPD_ACC_SUM 0
+#define SPD_ACC_MEAN 1
+#define SPD_ACC_MIN 2
+#define SPD_ACC_MAX 3
+int spd_model_acctape_configure(spd_model_handle m, const char *const *names, const int *ops, int n_entries, int every, int capacity,
+                                int dtype);
+int spd_model_acctape_reset(spd_model_handle m);
+int spd_model_acctape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *dtype);
+int spd_model_acctape_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_acctape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
+                           size_t dst_bytes, void *stream);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

@@ -8,8 +8,8 @@
 !!   init            -> spd_model_init                    step / parallel_step -> spd_model_step
 !!   check           -> spd_model_check                   transform_spectral2grid ... -> spd_model_spectral2grid ...
 !! and, without a counterpart there: time statistics on the device (spd_model_stats_*), pressure-level fields (spd_model_plev_*),
-!! time series recorded on the device (spd_model_tape_*), spectra of the spectral state (spd_model_spectra_*) and the series of
-!! the ensemble mean and spread (spd_model_enstape_*)
+!! time series recorded on the device (spd_model_tape_*), spectra of the spectral state (spd_model_spectra_*), the series of
+!! the ensemble mean and spread (spd_model_enstape_*) and window sums, means and extremes of the physics fluxes (spd_model_acctape_*)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -18,6 +18,7 @@ module pyspeedy_amd_c
     integer(c_int), parameter :: SPD_STATS_MEAN = 0, SPD_STATS_VARIANCE = 1, SPD_STATS_STD = 2
     integer(c_int), parameter :: SPD_TAPE_F32 = 0, SPD_TAPE_F64 = 1
     integer(c_int), parameter :: SPD_ENS_MEAN = 0, SPD_ENS_STD = 1, SPD_ENS_M2 = 2
+    integer(c_int), parameter :: SPD_ACC_SUM = 0, SPD_ACC_MEAN = 1, SPD_ACC_MIN = 2, SPD_ACC_MAX = 3
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -272,6 +273,43 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model, dst_device, stream
             character(kind=c_char), intent(in) :: name(*)
             integer(c_int), value :: kind, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        ! the accumulation tape: window sums, means, minima and maxima of the column physics' 2-D outputs, accumulated on the device
+        ! behind every step (pyspeedy_amd.h: spd_model_acctape_*).  An entry is names(k) with ops(k): SPD_ACC_SUM (0) / _MEAN (1) /
+        ! _MIN (2) / _MAX (3); dtype as the tape's; rows(7, *): the tape's six and the number of steps in the window;
+        ! _read: (96, 48[, 3], nt, count) in the ring's dtype
+        integer(c_int) function spd_model_acctape_configure(model, names, ops, n_entries, every, capacity, dtype) &
+                bind(C, name="spd_model_acctape_configure")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: ops(*)
+            integer(c_int), value :: n_entries, every, capacity, dtype
+        end function
+        integer(c_int) function spd_model_acctape_reset(model) bind(C, name="spd_model_acctape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_acctape_info(model, taken, held, capacity, every, dtype) &
+                bind(C, name="spd_model_acctape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken
+            integer(c_int), intent(out) :: held, capacity, every, dtype
+        end function
+        integer(c_int) function spd_model_acctape_times(model, rows, max_rows) bind(C, name="spd_model_acctape_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(7, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_acctape_read(model, name, op, first, count, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_acctape_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: op, first, count, t0, nt
             integer(c_size_t), value :: dst_bytes
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on

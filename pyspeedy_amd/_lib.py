@@ -19,6 +19,7 @@ SPD_OK, SPD_E_ARG, SPD_E_DEVICE, SPD_E_SIZE = 0, -1, -2, -3
 SPD_STATS_MEAN, SPD_STATS_VARIANCE, SPD_STATS_STD = 0, 1, 2  # kinds of spd_model_stats_read / _ensemble
 SPD_TAPE_F32, SPD_TAPE_F64 = 0, 1  # storage of spd_model_tape_configure
 SPD_ENS_MEAN, SPD_ENS_STD, SPD_ENS_M2 = 0, 1, 2  # kinds of spd_model_enstape_read
+SPD_ACC_SUM, SPD_ACC_MEAN, SPD_ACC_MIN, SPD_ACC_MAX = 0, 1, 2, 3  # ops of spd_model_acctape_configure / _read
 
 
 class SpeedyHipError(RuntimeError):
@@ -147,6 +148,12 @@ _SIGNATURES = {
     "spd_model_enstape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 4),
     "spd_model_enstape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "spd_model_enstape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_acctape_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "spd_model_acctape_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_acctape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 4),
+    "spd_model_acctape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_acctape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),

@@ -30,6 +30,7 @@
 #include "spectra.hpp"
 #include "tape.hpp"
 #include "enstape.hpp"
+#include "acctape.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
 
@@ -303,6 +304,27 @@ struct spd_model {
         double *mean = nullptr, *m2 = nullptr;
         EnsTapePlane *planes = nullptr;
     } enstape;
+    // The accumulation tape (spd_model_acctape_*): window sums, means, minima and maxima of the column physics' 2-D outputs.  An
+    // accumulate launch follows EVERY step while it is on (acctape.hip); a window closes by the tape's rule into ring slot
+    // (k - 1) % capacity, k the number of windows closed since the last reset.  No front end: the values are read where the column
+    // kernel stores them.  One allocation of its own (hipMalloc): ring (per entry [slot][M][planes][4608], float or double), the
+    // fp64 accumulators some entry needs ([M][planes][4608] each), the plane descriptors.  The step the open window started at and
+    // the rows of the closed ones (step, date, number of steps) are host state.
+    struct AccTape {
+        struct Entry {
+            int name, op, planes;
+            size_t offset;  // elements from `data` to slot 0, member 0 of the entry
+        };
+        bool on = false, valid = true;
+        int every = 1, capacity = 0, dtype = SPD_TAPE_F32, nplanes = 0;
+        int window_start = -1;  // absolute step counter the open window began at (-1: at the next step that runs)
+        long long taken = 0;    // windows closed since the last reset
+        std::string invalid_why;
+        std::vector<Entry> entries;
+        std::vector<int32_t> rows;  // [capacity][7]: step after the window, year, month, day, hour, minute of that state, steps in it
+        void *alloc = nullptr, *data = nullptr;
+        AccTapePlane *planes = nullptr;
+    } acctape;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {
@@ -788,6 +810,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->tape.alloc) (void)hipFree(m->tape.alloc);
     if (m->spectra.alloc) (void)hipFree(m->spectra.alloc);
     if (m->enstape.alloc) (void)hipFree(m->enstape.alloc);
+    if (m->acctape.alloc) (void)hipFree(m->acctape.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1331,6 +1354,9 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->spectra.valid = true;
     m->enstape.taken = 0;  // (... and an empty ensemble tape)
     m->enstape.valid = true;
+    m->acctape.taken = 0;  // (... and an accumulation tape whose first window starts at the first step)
+    m->acctape.window_start = -1;
+    m->acctape.valid = true;
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1530,13 +1556,20 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     const long long tape0 = m->tape.taken;        // (... and writes the same slots of the tape, for its own members)
     const long long spectra0 = m->spectra.taken;  // (... and of the spectra)
     const long long enstape0 = m->enstape.taken;  // (... and folds its members into the same slots of the ensemble tape)
+    // the accumulation tape: the open window's first step and the windows closed are put back for every round, whose members
+    // accumulate into their own part of the accumulators and close into their own part of the same slots
+    spd_model::AccTape &ac = m->acctape;
+    if (ac.on && (ac.window_start < 0 || ac.window_start > m->current_step)) ac.window_start = m->current_step;
+    const long long acctape0 = ac.taken;
+    const int acc_start0 = ac.window_start;
     // the ensemble tape's last sample of this call: a sample whose slot a later sample of the SAME call takes again is not folded at
     // all -- nobody can read it, and with rounds its members would otherwise land in the partials of the sample that replaced it
     long long enstape_last = enstape0;
     if (m->enstape.on)
         enstape_last += (static_cast<long long>(m->current_step) + nsteps) / m->enstape.every - m->current_step / m->enstape.every;
     for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
-        long long taken = 0, tape_taken = 0, spectra_taken = 0, enstape_taken = 0;
+        long long taken = 0, tape_taken = 0, spectra_taken = 0, enstape_taken = 0, acctape_taken = 0;
+        int acc_start = acc_start0;
         const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
         if (round > 0) {  // the same steps again, for the next members
             m->cal = start.cal;
@@ -1570,8 +1603,11 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                 int *held = m->enstape.counts.data() + kEnsTapeGroups * static_cast<size_t>((enstape0 + enstape_taken - 1) % m->enstape.capacity);
                 std::fill(held, held + kEnsTapeGroups, 0);
             }
+            // the accumulation tape reads the diagnostics-only outputs of EVERY step; this step is number acc_step of its window
+            const int acc_step = m->current_step + 1 - acc_start;
+            const bool acc_close = ac.on && (m->current_step + 1) % ac.every == 0;
             const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip) ||
-                              (fold_enstape && m->enstape.precip)) ? 1 : 0;
+                              (fold_enstape && m->enstape.precip) || ac.on) ? 1 : 0;
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
             // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
@@ -1653,6 +1689,16 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                         device_failed = true;
                     }
                 }
+                if (rc == SPD_OK && ac.on) {  // behind the ensemble tape's sample, on the same stream, on every step
+                    const hipError_t e = run_acctape_step(ac.planes, ac.nplanes, first, count, acc_step, acc_close ? 1 : 0,
+                                                          static_cast<int>((acctape0 + acctape_taken) % ac.capacity), m->stored32 ? 1 : 0,
+                                                          ac.dtype == SPD_TAPE_F64 ? 1 : 0, gs[g]);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": accumulation tape: " + hipGetErrorString(e));
+                        device_failed = true;
+                    }
+                }
                 first += count;
             }
             if (rc != SPD_OK) break;
@@ -1676,6 +1722,17 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                 m->enstape.taken = enstape0 + enstape_taken;
                 int32_t *row = m->enstape.rows.data() + 6 * static_cast<size_t>((m->enstape.taken - 1) % m->enstape.capacity);
                 row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+            }
+            if (acc_close) {  // the window is closed and the next one starts at the step counter as it stands now
+                ++acctape_taken;
+                acc_start = m->current_step;
+                if (round == 0) {
+                    ac.taken = acctape0 + acctape_taken;
+                    ac.window_start = acc_start;
+                    int32_t *row = ac.rows.data() + 7 * static_cast<size_t>((ac.taken - 1) % ac.capacity);
+                    row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+                    row[6] = acc_step;
+                }
             }
         }
         round_first += round_count;
@@ -1757,6 +1814,12 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
             m->enstape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
                                      " of a checked call";
         }
+    for (int i = 0; i < M && m->acctape.on && m->acctape.valid; ++i)
+        if (first_failed_step[i] >= 0) {  // (... and for the accumulation tape)
+            m->acctape.valid = false;
+            m->acctape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
+                                     " of a checked call";
+        }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)
             std::memcpy(accepted + 7 * static_cast<size_t>(i),
@@ -1826,6 +1889,7 @@ int spd_model_mark_initialized(spd_model_handle m, int current_step, int year, i
     if (int rc = usable(m, "spd_model_mark_initialized")) return rc;
     m->cal.set(year, month, day, hour, minute);
     m->current_step = current_step;
+    m->acctape.window_start = -1;  // (the accumulation tape's open window does not continue across a step counter set by hand)
     m->surf_cache_valid = false;
     m->ablco2_ref = m->air_absortivity_co2;  // set_forcing(imode = 0), forcing.f90:40
     m->initialized = true;
@@ -1866,6 +1930,7 @@ int spd_model_set_control(spd_model_handle m, const spd_model_control *in) {
     m->cal.month_idx = in->month_idx;
     m->surf_cache_valid = false;
     m->current_step = in->current_step;
+    m->acctape.window_start = -1;
     m->land_coupling_flag = in->land_coupling_flag ? 1 : 0;
     m->sst_anomaly_flag = in->sst_anomaly_coupling_flag ? 1 : 0;
     m->increase_co2 = in->increase_co2 ? 1 : 0;
@@ -2940,6 +3005,216 @@ int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t
     const size_t var_at = v->first_plane * NG;
     const hipError_t e = run_enstape_read(et.mean + var_at, et.m2 + var_at, static_cast<long>(per), et.nplanes, kind, nt, slot0, et.capacity,
                                           counts.data(), static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the accumulation tape: window sums, means and extremes of the physics' 2-D outputs (spd_model_acctape_*; kernel: acctape.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// The column physics' 2-D outputs of which every plane is stored on every step that runs with diag = 1 (physics.hip).  hfluxn (its
+// third plane is never written) and qcloud_equiv (written on shortwave steps only, and an input of the next steps rather than a
+// flux) are not confirmed and are refused by name.
+struct AccName {
+    const char *name;
+    int planes;
+};
+constexpr AccName kAccNames[] = {{"precnv", 1}, {"precls", 1}, {"cbmf", 1}, {"olr", 1},  {"tsr", 1},  {"ssr", 1},  {"ssrd", 1},
+                                 {"slr", 1},    {"slrd", 1},   {"ustr", 3}, {"vstr", 3}, {"shf", 3}, {"evap", 3}, {"slru", 3}};
+constexpr int kAccNNames = static_cast<int>(sizeof(kAccNames) / sizeof(kAccNames[0]));
+int acc_name_id(const char *name) {
+    for (int v = 0; name && v < kAccNNames; ++v)
+        if (std::strcmp(name, kAccNames[v].name) == 0) return v;
+    return -1;
+}
+const void *acc_source(const spd_model *m, int id) {
+    const spd_physics_args &pa = m->pa;
+    const double *const src[kAccNNames] = {pa.precnv, pa.precls, pa.cbmf, pa.olr, pa.tsr, pa.ssr, pa.ssrd,
+                                           pa.slr,    pa.slrd,   pa.ustr, pa.vstr, pa.shf, pa.evap, pa.slru};
+    return src[id];
+}
+const char *const kAccOff = "no accumulation tape configured (spd_model_acctape_configure)";
+}  // namespace
+
+int spd_model_acctape_configure(spd_model_handle m, const char *const *names, const int *ops, int n_entries, int every, int capacity,
+                                int dtype) {
+    const char *who = "spd_model_acctape_configure";
+    // (the arguments first: nothing below needs the device)
+    if (n_entries < 0 || (n_entries > 0 && (!names || !ops))) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
+    std::vector<spd_model::AccTape::Entry> entries;
+    for (int k = 0; k < n_entries; ++k) {
+        const int id = acc_name_id(names[k]);
+        if (id < 0) {
+            const std::string name = names[k] ? names[k] : "(null)";
+            if (name == "hfluxn" || name == "qcloud_equiv")
+                return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not stored in every plane on every step and cannot be accumulated");
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + name + "'");
+        }
+        if (ops[k] != SPD_ACC_SUM && ops[k] != SPD_ACC_MEAN && ops[k] != SPD_ACC_MIN && ops[k] != SPD_ACC_MAX)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown op " + std::to_string(ops[k]) + " for '" + names[k] +
+                                         "' (SPD_ACC_SUM, SPD_ACC_MEAN, SPD_ACC_MIN or SPD_ACC_MAX)");
+        for (const auto &e : entries)
+            if (e.name == id && e.op == ops[k])
+                return m_fail(SPD_E_ARG, std::string(who) + ": entry ('" + names[k] + "', " + std::to_string(ops[k]) + ") named twice");
+        entries.push_back({id, ops[k], kAccNames[id].planes, 0});
+    }
+    if (n_entries > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+    if (n_entries > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+    if (n_entries > 0 && dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64)
+        return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still accumulate into the allocation this one replaces)
+    spd_model::AccTape &ac = m->acctape;
+    void *old = ac.alloc;
+    ac = spd_model::AccTape{};  // (off before anything below can fail)
+    if (old) M_HIP(hipFree(old));
+    if (n_entries == 0) return SPD_OK;  // off
+    spd_model::AccTape next;
+    next.every = every;
+    next.capacity = capacity;
+    next.dtype = dtype;
+    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
+    const size_t elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
+    // what each name needs: [0] a running sum (sum or mean), [1] a minimum, [2] a maximum
+    bool need[kAccNNames][3] = {};
+    size_t ring_planes = 0, acc_planes = 0, desc_planes = 0;
+    for (auto &e : entries) {
+        e.offset = slots * M * ring_planes * NG;
+        ring_planes += static_cast<size_t>(e.planes);
+        need[e.name][e.op == SPD_ACC_MIN ? 1 : e.op == SPD_ACC_MAX ? 2 : 0] = true;
+    }
+    for (int v = 0; v < kAccNNames; ++v) {
+        const int kinds = (need[v][0] ? 1 : 0) + (need[v][1] ? 1 : 0) + (need[v][2] ? 1 : 0);
+        acc_planes += static_cast<size_t>(kinds) * kAccNames[v].planes;
+        if (kinds) desc_planes += static_cast<size_t>(kAccNames[v].planes);
+    }
+    // one allocation: ring | accumulators | plane descriptors
+    const size_t per_slot = M * ring_planes * NG * elem;
+    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 2) / per_slot)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the accumulation tape's size does not fit size_t");
+    const size_t ring = sample_up(slots * per_slot), accs = sample_up(M * acc_planes * NG * sizeof(double));
+    const size_t desc = sample_up(desc_planes * sizeof(AccTapePlane));
+    const size_t total = ring + accs + desc;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the accumulation tape is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the accumulation tape (" + std::to_string(total) +
+                                        " bytes asked for: " + std::to_string(capacity) + " windows of " + std::to_string(per_slot) +
+                                        " bytes and " + std::to_string(accs) + " bytes of accumulators); the accumulation tape is off");
+    }
+    char *at = static_cast<char *>(p);
+    next.alloc = p;
+    next.data = at, at += ring;
+    double *acc_at = reinterpret_cast<double *>(at);
+    at += accs;
+    next.planes = reinterpret_cast<AccTapePlane *>(at);
+    std::vector<AccTapePlane> host_planes;
+    for (int v = 0; v < kAccNNames; ++v) {
+        if (!need[v][0] && !need[v][1] && !need[v][2]) continue;
+        const size_t planes = static_cast<size_t>(kAccNames[v].planes), per = planes * NG;
+        double *acc[3] = {nullptr, nullptr, nullptr};
+        for (int a = 0; a < 3; ++a)
+            if (need[v][a]) acc[a] = acc_at, acc_at += M * per;
+        for (size_t k = 0; k < planes; ++k) {
+            AccTapePlane d{};
+            // (plane k in elements: the kernel indexes the source as float or double, as the model stores it at the time of the step)
+            d.src = acc_source(m, v);
+            d.plane = static_cast<int>(k);
+            d.sum = acc[0] ? acc[0] + k * NG : nullptr;
+            d.mn = acc[1] ? acc[1] + k * NG : nullptr;
+            d.mx = acc[2] ? acc[2] + k * NG : nullptr;
+            for (const auto &e : entries)
+                if (e.name == v) d.ring[e.op] = static_cast<char *>(next.data) + (e.offset + k * NG) * elem;
+            d.member_stride = static_cast<long>(per);
+            d.slot_stride = static_cast<long>(M * per);
+            d.narrow = m->reg[kAccNames[v].name].f32 ? 1 : 0;  // (what physics_storage32 keeps as float)
+            host_planes.push_back(d);
+        }
+    }
+    const hipError_t e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(AccTapePlane), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    next.nplanes = static_cast<int>(host_planes.size());
+    next.entries = std::move(entries);
+    next.rows.assign(slots * 7, 0);
+    next.window_start = -1;  // (the first window starts at the model's current step: step_impl reads the counter when it next runs)
+    next.on = true;
+    ac = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_acctape_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: null model");
+    if (!m->acctape.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_reset: ") + kAccOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: a checked multi-step call is in flight; end it first");
+    m->acctape.taken = 0;          // (the next window goes into slot 0 ...
+    m->acctape.window_start = -1;  //  ... and starts at the next step, which overwrites the accumulators: no device work)
+    m->acctape.valid = true;
+    m->acctape.invalid_why.clear();
+    return SPD_OK;
+}
+
+int spd_model_acctape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *dtype) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_info: null model");
+    const spd_model::AccTape &ac = m->acctape;
+    if (!ac.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_info: ") + kAccOff);
+    if (taken) *taken = ac.taken;
+    if (held) *held = static_cast<int>(std::min<long long>(ac.taken, ac.capacity));
+    if (capacity) *capacity = ac.capacity;
+    if (every) *every = ac.every;
+    if (dtype) *dtype = ac.dtype;
+    return SPD_OK;
+}
+
+int spd_model_acctape_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_times: null model");
+    const spd_model::AccTape &ac = m->acctape;
+    if (!ac.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_times: ") + kAccOff);
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_acctape_times: bad destination");
+    const long long held = std::min<long long>(ac.taken, ac.capacity), oldest = ac.taken - held;  // (window numbers from 0)
+    int n = 0;
+    for (; n < held && n < max_rows; ++n)
+        std::memcpy(rows + 7 * static_cast<size_t>(n), ac.rows.data() + 7 * static_cast<size_t>((oldest + n) % ac.capacity), 7 * sizeof(int32_t));
+    return n;
+}
+
+int spd_model_acctape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
+                           size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_acctape_read";
+    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::AccTape &ac = m->acctape;
+    if (!ac.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kAccOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (!ac.valid)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the accumulation tape is invalid until spd_model_acctape_reset: " + ac.invalid_why);
+    const int id = acc_name_id(name);
+    const spd_model::AccTape::Entry *v = nullptr;
+    for (const auto &x : ac.entries)
+        if (x.name == id && x.op == op) v = &x;
+    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": ('" + name + "', " + std::to_string(op) + ") is not among the configured entries");
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    const long long held = std::min<long long>(ac.taken, ac.capacity), oldest = ac.taken - held;
+    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
+        return m_fail(SPD_E_ARG, std::string(who) + ": window range out of bounds (" + std::to_string(held) + " windows held)");
+    const size_t elem = ac.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->planes) * NG;
+    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (count == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    const char *src = static_cast<const char *>(ac.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
+    const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
+                                         static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % ac.capacity), ac.capacity,
+                                         static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
 }

@@ -494,6 +494,85 @@ class EnsembleModel:
         return (self.enstape_info["members"], self._enstape_read(name, _lib.SPD_ENS_MEAN, t0, nt),
                 self._enstape_read(name, _lib.SPD_ENS_M2, t0, nt))
 
+    # ---- the accumulation tape: window sums, means and extremes of the physics fluxes (spd_model_acctape_*, pyspeedy_amd.h) ---
+    ACCTAPE_NAMES = ("precnv", "precls", "cbmf", "olr", "tsr", "ssr", "ssrd", "slr", "slrd", "ustr", "vstr", "shf", "evap", "slru")
+    ACCTAPE_THREE_PLANES = ("ustr", "vstr", "shf", "evap", "slru")  # land, sea, weighted by the land fraction
+    ACCTAPE_OPS = {"sum": _lib.SPD_ACC_SUM, "mean": _lib.SPD_ACC_MEAN, "min": _lib.SPD_ACC_MIN, "max": _lib.SPD_ACC_MAX}
+
+    def _acctape_op(self, op):
+        if op not in self.ACCTAPE_OPS:
+            raise ValueError("op must be one of 'sum', 'mean', 'min', 'max', got %r" % (op,))
+        return self.ACCTAPE_OPS[op]
+
+    def acctape_configure(self, entries, every, capacity, dtype="float32"):
+        """Accumulate over windows of steps, inside run() / run_checked() calls of any length: `entries` is a list of (name, op)
+        pairs, name any of ACCTAPE_NAMES (the column physics' 2-D outputs, in the registry's unit), op "sum", "mean", "min" or
+        "max".  Every step adds to the open window; a window closes after every step that leaves current_step at a multiple of
+        `every` into a ring in device memory that keeps the last `capacity` windows of every member; dtype "float32" (the default)
+        or "float64".  The first window starts at the current step and may be shorter (acctape_counts()).  Empties the ring; an
+        empty list switches the recorder off and frees it.  Synchronises the device."""
+        key = str(dtype).replace("torch.", "")
+        if key not in self.TAPE_DTYPES:
+            raise ValueError("dtype must be 'float32' or 'float64', got %r" % (dtype,))
+        pairs = [(str(n), self._acctape_op(op)) for n, op in entries]
+        names = (C.c_char_p * max(len(pairs), 1))(*[n.encode() for n, _ in pairs])
+        ops = (C.c_int * max(len(pairs), 1))(*[op for _, op in pairs])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_acctape_configure(self._m, names, ops, len(pairs), int(every), int(capacity),
+                                                        self.TAPE_DTYPES[key][0]), "spd_model_acctape_configure")
+
+    def acctape_reset(self):
+        """Empty the ring and start a new window at the current step (no device work)."""
+        check(self._lib.spd_model_acctape_reset(self._m), "spd_model_acctape_reset")
+
+    @property
+    def acctape_info(self):
+        """dict(taken, held, capacity, every, dtype): windows closed since the last reset, windows the ring holds (min(taken,
+        capacity)), and the configuration."""
+        taken, held, capacity, every, dtype = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.spd_model_acctape_info(self._m, C.byref(taken), C.byref(held), C.byref(capacity), C.byref(every),
+                                               C.byref(dtype)), "spd_model_acctape_info")
+        name = [k for k, v in self.TAPE_DTYPES.items() if v[0] == dtype.value][0]
+        return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, dtype=name)
+
+    def _acctape_rows(self):
+        held = self.acctape_info["held"]
+        rows = np.zeros((max(held, 1), 7), dtype=np.int32)
+        n = self._lib.spd_model_acctape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
+        if n < 0:
+            check(n, "spd_model_acctape_times")
+        return rows[:n]
+
+    def acctape_steps(self):
+        """The model's step counter after the last step of each held window, oldest first (numpy int array)."""
+        return self._acctape_rows()[:, 0].astype(np.int64)
+
+    def acctape_times(self):
+        """The date of the state after each held window's last step, oldest first (a list of datetime)."""
+        from datetime import datetime
+        return [datetime(*(int(v) for v in row[1:6])) for row in self._acctape_rows()]
+
+    def acctape_counts(self):
+        """The number of steps in each held window, oldest first (numpy int array)."""
+        return self._acctape_rows()[:, 6].astype(np.int64)
+
+    def acctape(self, name, op, first=0, count=None, t0=0, nt=None):
+        """Members [first, first + count) and windows [t0, t0 + nt) of the held ones (oldest first) of one entry: a tensor
+        [count][nt][48][96] ([count][nt][3][48][96] for the names of ACCTAPE_THREE_PLANES) on the model's device in the ring's
+        dtype."""
+        first, count = self._range(first, count)
+        info = self.acctape_info
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        dtype = self.TAPE_DTYPES[info["dtype"]][1]
+        inner = (3, 48, 96) if name in self.ACCTAPE_THREE_PLANES else (48, 96)
+        out = torch.empty((count, max(nt, 0)) + inner, dtype=dtype, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_acctape_read(self._m, name.encode(), self._acctape_op(op), first, count, t0, nt,
+                                                   C.c_void_p(out.data_ptr()), out.numel() * out.element_size(), self._stream()),
+                  "spd_model_acctape_read(%s, %s)" % (name, op))
+        return out
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

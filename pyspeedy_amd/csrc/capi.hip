@@ -12,6 +12,7 @@
 #include "context.hpp"
 #include "device_tables.hpp"
 #include "surface_host.hpp"
+#include "triangle.hpp"
 #include "vertical_consts.hpp"
 
 namespace spd {
@@ -111,10 +112,33 @@ static std::vector<int> make_dirmeta(const std::vector<DirLane> &lanes, int stri
         const int pr = d.m == 0 ? 0 : 2 * d.m - 1, pi = d.m == 0 ? 61 : 2 * d.m;  // pos_re / pos_im of transforms.hip
         meta[4 * l + 0] = pr | (pi << 8);
         meta[4 * l + 1] = d.par;
-        meta[4 * l + 2] = d.na * MX + d.m;
-        meta[4 * l + 3] = d.nb >= 0 ? d.nb * MX + d.m : -1;
+        // output index: place in the rectangle | place in the packed field << 16 (triangle.hpp)
+        meta[4 * l + 2] = (d.na * MX + d.m) | (tri::packed_index(d.m, d.na) << 16);
+        meta[4 * l + 3] = d.nb >= 0 ? (d.nb * MX + d.m) | (tri::packed_index(d.m, d.nb) << 16) : -1;
     }
     return meta;
+}
+
+// The work list above and the index sets of triangle.hpp describe the same triangle twice: the kernels that skip or pack
+// coefficients by the header are only right while the list fills exactly fwd_filled, each coefficient once, and the packed
+// index is the dense (n, m) order of that set.  Checked where the tables are built, before a single kernel runs.
+static int verify_triangle(const std::vector<DirLane> &lanes) {
+    std::vector<int> hits(NSPEC, 0);
+    for (const DirLane &d : lanes) {
+        ++hits[d.na * MX + d.m];
+        if (d.nb >= 0) ++hits[d.nb * MX + d.m];
+    }
+    int next = 0;
+    for (int n = 0; n < NX; ++n)
+        for (int m = 0; m < MX; ++m) {
+            const bool filled = tri::fwd_filled(m, n);
+            if (hits[n * MX + m] != (filled ? 1 : 0) || (filled && tri::packed_index(m, n) != next++) ||
+                (filled && !tri::inv_needed(m, n)))
+                return fail(SPD_E_ARG, "csrc/triangle.hpp and the direct-Legendre work list (capi.hip: dir_lanes) disagree at m = " +
+                                           std::to_string(m) + ", n = " + std::to_string(n));
+        }
+    if (next != tri::kFilled) return fail(SPD_E_ARG, "csrc/triangle.hpp: kFilled is not the size of the filled set");
+    return SPD_OK;
 }
 
 // The column kernel carries the vertical-structure tables as compile-time constants (vertical_consts.hpp, generated by
@@ -166,6 +190,11 @@ int spd_create(spd_handle *out, int device) {
         if (rc == SPD_OK) rc = upload(c, src, n, dst);
     };
     const std::vector<DirLane> lanes = dir_lanes();
+    rc = verify_triangle(lanes);
+    if (rc != SPD_OK) {
+        delete c;
+        return rc;
+    }
     d.ndir = static_cast<int>(lanes.size());
     d.dir_stride = (d.ndir + 63) / 64 * 64;
     const std::vector<double> pinv = make_pinv(h), pdir = make_pdir(h, lanes, d.dir_stride);
@@ -267,6 +296,20 @@ long spd_get_table_host(spd_handle h, const char *name, double *buf, size_t buf_
     else if (s == "cpol") { tmp = t.cpol(); arr(tmp); }
     else if (s == "nsh2") { tmp.assign(t.nsh2.begin(), t.nsh2.end()); arr(tmp); }
     else if (s == "ifac") { tmp.assign(t.ifac.begin(), t.ifac.end()); arr(tmp); }
+    else if (s == "tri_packed") {  // triangle.hpp: [0] = kPacked, then per k = m + 31 n the packed index (-1: not filled)
+        tmp.assign(1 + NSPEC, -1.0);
+        tmp[0] = tri::kPacked;
+        for (int n = 0; n < NX; ++n)
+            for (int m = 0; m < MX; ++m)
+                if (tri::fwd_filled(m, n)) tmp[1 + n * MX + m] = tri::packed_index(m, n);
+        arr(tmp);
+    }
+    else if (s == "tri_inv_needed") {  // triangle.hpp: per k = m + 31 n, 1 where the inverse transform reads the coefficient
+        tmp.assign(NSPEC, 0.0);
+        for (int n = 0; n < NX; ++n)
+            for (int m = 0; m < MX; ++m) tmp[n * MX + m] = tri::inv_needed(m, n) ? 1.0 : 0.0;
+        arr(tmp);
+    }
     else return fail(SPD_E_ARG, "spd_get_table_host: unknown table '" + s + "'");
     if (buf) {
         if (buf_elems < n) return fail(SPD_E_SIZE, "spd_get_table_host: buffer too small for '" + s + "'");

@@ -9,7 +9,8 @@ struct DeviceTables {
     // inverse-Legendre polynomials  [n=32][m*12+jq][2 lat pairs]      (zero where m + n > 31)
     const double *pinv;
     // direct-Legendre polynomials   [j=24][lane (dir_stride)][2 n]    one lane per two valid coefficients of one
-    // (m, parity); dirmeta[lane] = {pos_re | pos_im << 8, parity, output index a, output index b or -1}
+    // (m, parity); dirmeta[lane] = {pos_re | pos_im << 8, parity, output index a, output index b or -1}; an output index is
+    // k = m + 31 n | packed index << 16 (triangle.hpp)
     const double *pdir;
     const int *dirmeta;
     int ndir, dir_stride;
@@ -33,8 +34,11 @@ struct DeviceTables {
 // arrays in memory: 0 = transform src as it is; 1 / 2 = ucos / vcos of vort2vel(vor = src, div = src2)
 // (spectral.f90:190-214); 3 / 4 = x / y component of gradient(src) (spectral.f90:275-296).
 // flag of a spectral -> grid entry: kcos (1: none, 2: rows times 1 / cos(lat)) [| kGridAsFloat: dst receives the field as
-// fp32, 96 x 48 floats from dst on -- fields that only the fp32 column physics of cfg 5 reads].  grid -> spectral: the prescale.
+// fp32, 96 x 48 floats from dst on -- fields that only the fp32 column physics of cfg 5 reads].  grid -> spectral: the prescale
+// [| kSpecPacked: dst receives the 528 packed coefficients of triangle.hpp, 8448 B, and not the rectangle -- the tendency
+// fields of the model step, which only spectral_step_kernel reads].
 constexpr int kGridAsFloat = 0x100;
+constexpr int kSpecPacked = 0x100;
 struct FieldDesc {
     const double *src;
     double *dst;

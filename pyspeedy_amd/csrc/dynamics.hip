@@ -12,6 +12,8 @@
 // Layouts (member-major, the reference's Fortran order inside a member):
 //   vor, div, t, tr  complex [M][2 time levels][8][32][31] ; ps [M][2][32][31] ; phi [M][8][32][31] ; phis [M][32][31]
 //   grid fields      [M][8][48][96] or [M][48][96]
+//   tendency spectra (forward transforms of the step -> spectral_step_kernel)  complex [3][M][8][528], [M][8][528], [M][528]:
+//                    packed, the 526 coefficients the direct Legendre transform fills and two pad entries (triangle.hpp)
 // One lane per spectral coefficient or grid column (spectral_step_kernel: per coefficient and level); unit-stride accesses.
 #include <hip/hip_runtime.h>
 
@@ -41,15 +43,24 @@ __device__ inline d2 times_i(d2 z) { return d2{-z.y, z.x}; }
 __device__ inline d2 operator_scale(double c, d2 z) { return d2{c * z.x, c * z.y}; }
 
 // vort2vel (MODE 0, tables uvdx/uvdym/uvdyp) or vel2vort (MODE 1, gradx/vddym/vddyp) at coefficient k = m + 31 n of the
-// fields a, b (pointers to the field start), in two halves: all six loads first (neighbour indices clamped into the field,
-// so that the loads need no branch and a lane can have the loads of several stencils in flight at once), the arithmetic
-// afterwards (spectral.f90:190-214 / 275-296: first, last and inner total wavenumbers have different formulas).
+// fields a, b, in two halves: all six loads first (spectral_step_kernel: load_tendencies, so that a lane has the loads of
+// several stencils in flight at once), the arithmetic afterwards (spectral.f90:190-214 / 275-296: first, last and inner
+// total wavenumbers have different formulas).
 struct Stencil {
     d2 ac, bc, ap, bp, an, bn;
 };
-__device__ inline Stencil load_stencil(const d2 *a, const d2 *b, int k, int n) {
-    const int kp = n > 0 ? k - MX : k, kn = n < NX - 1 ? k + MX : k;
-    return Stencil{a[k], b[k], a[kp], b[kp], a[kn], b[kn]};
+
+// Where a lane finds the tendency values of its coefficient (m, n) and of the stencil neighbours (m, n - 1), (m, n + 1) in a
+// PACKED field (triangle.hpp), each with its own predicate: what the direct Legendre transform does not fill is +0.0 by
+// the reference's definition (legendre.f90:187) and is not in memory.  Beyond the field (n - 1 < 0, n + 1 > 31) nothing is
+// filled either; apply_stencil does not use those values.
+struct PackedAt {
+    int c, p, n;
+    bool has_c, has_p, has_n;
+};
+__device__ inline PackedAt packed_at(int m, int n) {
+    return PackedAt{tri::packed_index(m, n), tri::packed_index(m, n > 0 ? n - 1 : 0), tri::packed_index(m, n + 1),
+                    tri::fwd_filled(m, n), n > 0 && tri::fwd_filled(m, n - 1), tri::fwd_filled(m, n + 1)};
 }
 template <int MODE>
 __device__ inline void apply_stencil(const Stencil &s, int k, int m, int n, const DeviceTables &T, d2 &ra, d2 &rb) {
@@ -199,10 +210,16 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
     if (w >= count * kCoefBlocks) return;  // whole wavefronts only: the gathers below need all 64 lanes
     const int l = lane >> 3, kk = lane & 7;
     const int lm = w / kCoefBlocks, mem = first + lm, k = (w - lm * kCoefBlocks) * 8 + kk, n = k / MX, m = k - n * MX;
-    const size_t f8 = static_cast<size_t>(mem) * 8 * NSPEC;        // [M][8] work arrays
-    const size_t pair = static_cast<size_t>(M) * 8 * NSPEC;        // stride between the three (u,v)-pair outputs
+    const size_t f8 = static_cast<size_t>(mem) * 8 * NSPEC;        // [M][8] arrays of whole fields (phi)
     const size_t fo = static_cast<size_t>(l) * NSPEC;
-    const d2 *su = reinterpret_cast<const d2 *>(P.specu) + f8 + fo, *sv = reinterpret_cast<const d2 *>(P.specv) + f8 + fo;
+    // the packed tendency fields of this member and level (triangle.hpp)
+    const size_t tf = (static_cast<size_t>(mem) * 8 + l) * tri::kPacked;
+    const size_t pair = static_cast<size_t>(M) * 8 * tri::kPacked;  // stride between the three (u,v)-pair outputs
+    const d2 *su = reinterpret_cast<const d2 *>(P.specu) + tf, *sv = reinterpret_cast<const d2 *>(P.specv) + tf;
+    const d2 *ske = reinterpret_cast<const d2 *>(P.spec_ke) + tf, *stt_f = reinterpret_cast<const d2 *>(P.spec_tt) + tf;
+    const d2 *str_f = reinterpret_cast<const d2 *>(P.spec_tr) + tf;
+    const d2 *sps = reinterpret_cast<const d2 *>(P.spec_ps) + static_cast<size_t>(mem) * tri::kPacked;
+    const PackedAt at = packed_at(m, n);
     const double el2 = T.el2[k];
     d2 vordt, divdt, tdt, trdt, dump;
     // ---- state at both time levels, this lane's level ----
@@ -216,9 +233,31 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
     // kernel is a chain of short dependent phases; when the ensemble does not fill the GPU its duration is the number of
     // memory round trips on that chain (about 15 in the other form, whose loads sit inside the matrix loops and in front of
     // each use), and registers are free.  The other form keeps 4 wavefronts per SIMD (122 VGPRs).
-    d2 ke, stt, str, psdt, ph, div1, ps1;                                  // first batch
+    d2 ke{0.0, 0.0}, stt{0.0, 0.0}, str{0.0, 0.0}, psdt{0.0, 0.0}, ph, div1, ps1;  // first batch
     d2 vor1, t1, tr1, tcorh, qcorh, phis_k{0.0, 0.0}, vor2{}, div2{}, t2{}, tr2{}, ps2{};  // second batch
     double xc_l[KX], xj_l[KX], xd_l[KX], elz, dmp, dmp1, dmpd, dmp1d, dmps, dmp1s, trf;
+    // The 21 (EARLY: 22) tendency loads of a lane in three predicated groups -- the coefficient itself, its n - 1 and its
+    // n + 1 neighbour -- all issued before the first use; a value that is not in the packed field is the +0.0 it stands for.
+    Stencil s_uv{}, s_ut{}, s_uq{};
+    auto load_tendencies = [&](bool with_ps) {
+        if (at.has_c) {
+            s_uv.ac = su[at.c], s_uv.bc = sv[at.c];
+            s_ut.ac = su[pair + at.c], s_ut.bc = sv[pair + at.c];
+            s_uq.ac = su[2 * pair + at.c], s_uq.bc = sv[2 * pair + at.c];
+            ke = ske[at.c], stt = stt_f[at.c], str = str_f[at.c];
+            if (with_ps) psdt = sps[at.c];
+        }
+        if (at.has_p) {
+            s_uv.ap = su[at.p], s_uv.bp = sv[at.p];
+            s_ut.ap = su[pair + at.p], s_ut.bp = sv[pair + at.p];
+            s_uq.ap = su[2 * pair + at.p], s_uq.bp = sv[2 * pair + at.p];
+        }
+        if (at.has_n) {
+            s_uv.an = su[at.n], s_uv.bn = sv[at.n];
+            s_ut.an = su[pair + at.n], s_ut.bn = sv[pair + at.n];
+            s_uq.an = su[2 * pair + at.n], s_uq.bn = sv[2 * pair + at.n];
+        }
+    };
     auto load_diffusion = [&]() {
         dmp = D.dmp[k], dmp1 = D.dmp1[k], dmpd = D.dmpd[k], dmp1d = D.dmp1d[k], dmps = D.dmps[k], dmp1s = D.dmp1s[k];
         trf = T.trfilt[k];
@@ -226,13 +265,7 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
         qcorh = reinterpret_cast<const d2 *>(P.qcorh)[static_cast<size_t>(mem) * NSPEC + k];
     };
     if constexpr (EARLY) {
-        const Stencil s_uv = load_stencil(su, sv, k, n);
-        const Stencil s_ut = load_stencil(su + pair, sv + pair, k, n);
-        const Stencil s_uq = load_stencil(su + 2 * pair, sv + 2 * pair, k, n);
-        ke = reinterpret_cast<const d2 *>(P.spec_ke)[f8 + fo + k];
-        stt = reinterpret_cast<const d2 *>(P.spec_tt)[f8 + fo + k];
-        str = reinterpret_cast<const d2 *>(P.spec_tr)[f8 + fo + k];
-        psdt = reinterpret_cast<const d2 *>(P.spec_ps)[static_cast<size_t>(mem) * NSPEC + k];
+        load_tendencies(true);
         ph = reinterpret_cast<const d2 *>(P.phi)[f8 + fo + k];
         div1 = divS[0];
         ps1 = psS[0];
@@ -252,12 +285,7 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
         apply_stencil<1>(s_uq, k, m, n, T, dump, trdt);                                  // div of (-uq, -vq)
         trdt = d2{trdt.x + str.x, trdt.y + str.y};
     } else {  // the stencils' 18 loads in one batch (their branches would each wait for their own), the rest where it is used
-        const Stencil s_uv = load_stencil(su, sv, k, n);
-        const Stencil s_ut = load_stencil(su + pair, sv + pair, k, n);
-        const Stencil s_uq = load_stencil(su + 2 * pair, sv + 2 * pair, k, n);
-        ke = reinterpret_cast<const d2 *>(P.spec_ke)[f8 + fo + k];
-        stt = reinterpret_cast<const d2 *>(P.spec_tt)[f8 + fo + k];
-        str = reinterpret_cast<const d2 *>(P.spec_tr)[f8 + fo + k];
+        load_tendencies(false);
         apply_stencil<1>(s_uv, k, m, n, T, vordt, divdt);
         const d2 lap = d2{-ke.x * el2, -ke.y * el2};
         divdt = d2{divdt.x - lap.x, divdt.y - lap.y};
@@ -265,7 +293,7 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
         tdt = d2{tdt.x + stt.x, tdt.y + stt.y};
         apply_stencil<1>(s_uq, k, m, n, T, dump, trdt);
         trdt = d2{trdt.x + str.x, trdt.y + str.y};
-        psdt = reinterpret_cast<const d2 *>(P.spec_ps)[static_cast<size_t>(mem) * NSPEC + k];
+        if (at.has_c) psdt = sps[at.c];
         div1 = divS[0];
         ps1 = psS[0];
     }

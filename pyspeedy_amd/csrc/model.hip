@@ -515,6 +515,9 @@ static int build_tables(spd_model *m) {
     auto grid = [](double *base, size_t field) { return base + field * NG; };
     TableBatch batch;
     build_inverse_tables(m, false, false, m->inv_table, batch);
+    // the step's forward transforms write packed tendency fields (triangle.hpp): only this table sets kSpecPacked
+    auto pspec = [](double *base, size_t field) { return base + field * tri::kPacked * C; };
+    constexpr int pk = kSpecPacked;
     std::vector<FieldDesc> t;
     t.reserve(static_cast<size_t>(M) * 73);
     const size_t pair = static_cast<size_t>(M) * 8;
@@ -522,17 +525,17 @@ static int build_tables(spd_model *m) {
         const size_t w = static_cast<size_t>(i) * 8;
         for (int k = 0; k < 8; ++k) {
             // grid_vel2vort(..., kcos = 2): rows pre-multiplied by cosgr (spectral.f90:229-235) -> flag 1
-            t.push_back({grid(P.utend, w + k), spec(P.specu, w + k), 1, 0});
-            t.push_back({grid(P.vtend, w + k), spec(P.specv, w + k), 1, 0});
-            t.push_back({grid(P.utg, w + k), spec(P.specu, pair + w + k), 1, 0});
-            t.push_back({grid(P.vtg, w + k), spec(P.specv, pair + w + k), 1, 0});
-            t.push_back({grid(P.uqg, w + k), spec(P.specu, 2 * pair + w + k), 1, 0});
-            t.push_back({grid(P.vqg, w + k), spec(P.specv, 2 * pair + w + k), 1, 0});
-            t.push_back({grid(P.ttend, w + k), spec(P.spec_tt, w + k), 0, 0});
-            t.push_back({grid(P.trtend, w + k), spec(P.spec_tr, w + k), 0, 0});
-            t.push_back({grid(P.keg, w + k), spec(P.spec_ke, w + k), 0, 0});
+            t.push_back({grid(P.utend, w + k), pspec(P.specu, w + k), 1 | pk, 0});
+            t.push_back({grid(P.vtend, w + k), pspec(P.specv, w + k), 1 | pk, 0});
+            t.push_back({grid(P.utg, w + k), pspec(P.specu, pair + w + k), 1 | pk, 0});
+            t.push_back({grid(P.vtg, w + k), pspec(P.specv, pair + w + k), 1 | pk, 0});
+            t.push_back({grid(P.uqg, w + k), pspec(P.specu, 2 * pair + w + k), 1 | pk, 0});
+            t.push_back({grid(P.vqg, w + k), pspec(P.specv, 2 * pair + w + k), 1 | pk, 0});
+            t.push_back({grid(P.ttend, w + k), pspec(P.spec_tt, w + k), pk, 0});
+            t.push_back({grid(P.trtend, w + k), pspec(P.spec_tr, w + k), pk, 0});
+            t.push_back({grid(P.keg, w + k), pspec(P.spec_ke, w + k), pk, 0});
         }
-        t.push_back({grid(P.psdtg, i), spec(P.spec_ps, i), 0, 0});
+        t.push_back({grid(P.psdtg, i), pspec(P.spec_ps, i), pk, 0});
     }
     batch.add(std::move(t), &m->fwd_table);
     // export tables (prognostics.f90:125-219), time level 1.  sv holds ucos | vcos in the [M][2][8] layout of vor / div.
@@ -700,9 +703,10 @@ int spd_model_create(spd_handle h, int nmembers, spd_model_handle *out) {
     A(P.trtend, M * G3, nullptr, 0); A(P.keg, M * G3, nullptr, 0); A(P.utg, M * G3, nullptr, 0);
     A(P.vtg, M * G3, nullptr, 0); A(P.uqg, M * G3, nullptr, 0); A(P.vqg, M * G3, nullptr, 0);
     A(P.psdtg, M * NG, nullptr, 0);
-    A(P.specu, 3 * M * 8 * S, nullptr, 0); A(P.specv, 3 * M * 8 * S, nullptr, 0);
-    A(P.spec_tt, M * 8 * S, nullptr, 0); A(P.spec_tr, M * 8 * S, nullptr, 0); A(P.spec_ke, M * 8 * S, nullptr, 0);
-    A(P.spec_ps, M * S, nullptr, 0);
+    const size_t SP = static_cast<size_t>(tri::kPacked) * C;  // a packed tendency field (triangle.hpp)
+    A(P.specu, 3 * M * 8 * SP, nullptr, 0); A(P.specv, 3 * M * 8 * SP, nullptr, 0);
+    A(P.spec_tt, M * 8 * SP, nullptr, 0); A(P.spec_tr, M * 8 * SP, nullptr, 0); A(P.spec_ke, M * 8 * SP, nullptr, 0);
+    A(P.spec_ps, M * SP, nullptr, 0);
     // physics: grid-point inputs (work) ...
     double *tmp = nullptr;
 #define PA_IN(field, doubles, name, per)                            \

@@ -1,6 +1,7 @@
 // Device-resident model state of an ensemble and the per-step work buffers (model.hip owns the memory).
 #pragma once
 #include "device_tables.hpp"
+#include "triangle.hpp"
 
 namespace spd {
 
@@ -21,10 +22,11 @@ struct ModelPtrs {
     // tendencies (dynamics writes, physics accumulates) and the other forward-transform inputs
     double *utend, *vtend, *ttend, *trtend, *keg, *utg, *vtg, *uqg, *vqg;  // [M][8][NG]
     double *psdtg;                                                          // [M][NG]
-    // forward-transform outputs
-    double *specu, *specv;                 // [3][M][8][992]: (utend,vtend), (-uT',-vT'), (-uq,-vq)
-    double *spec_tt, *spec_tr, *spec_ke;   // [M][8][992]
-    double *spec_ps;                       // [M][992]
+    // forward-transform outputs of the step, read by spectral_step_kernel alone: PACKED fields of 528 complex (triangle.hpp:
+    // the 526 coefficients the direct Legendre transform fills, in (n, m) order, and two zero pad entries)
+    double *specu, *specv;                 // [3][M][8][528]: (utend,vtend), (-uT',-vT'), (-uq,-vq)
+    double *spec_tt, *spec_tr, *spec_ke;   // [M][8][528]
+    double *spec_ps;                       // [M][528]
 };
 
 struct DynDeviceTables {

@@ -35,6 +35,7 @@
 #include "diagnostics_block.hpp"
 #include "launch_events.hpp"
 #include "fft96.hpp"
+#include "triangle.hpp"
 
 namespace spd {
 
@@ -137,15 +138,26 @@ __device__ __forceinline__ void spec2grid_body(const double *__restrict__ src, d
         // ---- stage spectral coefficients: 16 B per lane, fully coalesced ----
         // (all loads of a lane are issued before the first LDS store: a rolled loop would wait for each one in turn)
         gd2_in g = (gd2_in)src;
+        // Only the triangle the inverse transform reads (m + n <= 31, triangle.hpp) is fetched; the rest of the staging area
+        // is zero: the Legendre loop of a wavefront runs to the count of its SMALLEST m, so lanes with a larger m do read
+        // positions beyond their own triangle, where the table's zero must meet a finite value.  A staged operator is
+        // evaluated inside the triangle only; its n +- 1 neighbours then reach m + n = 32 at most, and are not masked.
         d2 sv[kSpecPerLane];
+        bool need[kSpecPerLane];
+#pragma unroll
+        for (int it = 0; it < kSpecPerLane; ++it) {
+            const int k = tid + it * kThreads, n = k / MX;
+            need[it] = k < NSPEC && tri::inv_needed(k - n * MX, n);
+            sv[it] = d2{0.0, 0.0};
+        }
         if (mode == 0) {
 #pragma unroll
             for (int it = 0; it < kSpecPerLane; ++it)
-                if (tid + it * kThreads < NSPEC) sv[it] = g[tid + it * kThreads];
+                if (need[it]) sv[it] = g[tid + it * kThreads];
         } else {  // the spectral operator in front of the transform, applied on the fly (FieldDesc::mode)
 #pragma unroll
             for (int it = 0; it < kSpecPerLane; ++it)
-                if (tid + it * kThreads < NSPEC) sv[it] = staged_coefficient(mode, g, (gd2_in)src2, tid + it * kThreads, T);
+                if (need[it]) sv[it] = staged_coefficient(mode, g, (gd2_in)src2, tid + it * kThreads, T);
         }
 #pragma unroll
         for (int it = 0; it < kSpecPerLane; ++it)
@@ -295,6 +307,7 @@ __device__ __forceinline__ void spec2grid_body(const double *__restrict__ src, d
 
 // ------------------------------------------------------------------------------------------------
 // grid -> spec.  prescale: 0 none, 1 multiply rows by cosgr, 2 by cosgr2 (spectral.f90:229-243)
+// [| kSpecPacked, fused form: dst receives the tri::kPacked filled coefficients only (triangle.hpp), not the rectangle]
 // ------------------------------------------------------------------------------------------------
 template <Stage ST>
 __device__ __forceinline__ void grid2spec_body(const double *__restrict__ src, double *__restrict__ dst,
@@ -305,6 +318,8 @@ __device__ __forceinline__ void grid2spec_body(const double *__restrict__ src, d
     d2 *s = reinterpret_cast<d2 *>(lds + kCBufDoubles);    // output staging, 992 complex (aliases the tail of R)
     const int tid = threadIdx.x;
     const int wave = wave_id(), lane = tid & 63;
+    const bool packed = ST == Stage::Fused && (prescale & kSpecPacked) != 0;
+    prescale &= ~kSpecPacked;
 
     TRACE_BEGIN();
     if (ST == Stage::Fused) {
@@ -502,13 +517,17 @@ __device__ __forceinline__ void grid2spec_body(const double *__restrict__ src, d
             acc[0][0] += p.x * xr;  acc[0][1] += p.x * xi;
             acc[1][0] += p.y * xr;  acc[1][1] += p.y * xi;
         }
-        s[meta.z] = d2{acc[0][0], acc[0][1]};
-        if (meta.w >= 0) s[meta.w] = d2{acc[1][0], acc[1][1]};
+        // an output index holds the coefficient's place in the rectangle (low half) and in the packed field (high half)
+        const int sh = packed ? 16 : 0;
+        s[(meta.z >> sh) & 0xffff] = d2{acc[0][0], acc[0][1]};
+        if (meta.w >= 0) s[(meta.w >> sh) & 0xffff] = d2{acc[1][0], acc[1][1]};
     }
     __syncthreads();
     TRACE_MARK(1, 4);
     gd2_out g = (gd2_out)dst;
-    for (int idx = tid; idx < NSPEC; idx += kThreads) __builtin_nontemporal_store(s[idx], &g[idx]);
+    // packed: the staging area holds the filled coefficients in packed order, the cleared pad entries behind them
+    const int nout = packed ? tri::kPacked : NSPEC;
+    for (int idx = tid; idx < nout; idx += kThreads) __builtin_nontemporal_store(s[idx], &g[idx]);
     TRACE_MARK(1, 5);
     TRACE_END(1);
 }
@@ -529,7 +548,7 @@ __global__ __launch_bounds__(kThreads) void grid2spec_kernel(const double *__res
                                                              DeviceTables T, int prescale) {
     const size_t f = blockIdx.x;
     constexpr size_t in = (ST == Stage::LegendreOnly) ? NFOUR : NGRID, out = (ST == Stage::FourierOnly) ? NFOUR : 2 * NSPEC;
-    grid2spec_body<ST>(src + f * in, dst + f * out, T, prescale);
+    grid2spec_body<ST>(src + f * in, dst + f * out, T, prescale & ~kSpecPacked);  // contiguous batches are rectangles
 }
 
 __global__ __launch_bounds__(kThreads) void spec2grid_table_kernel(const FieldDesc *__restrict__ table, DeviceTables T) {

@@ -333,7 +333,11 @@ int spd_model_group_streams(spd_model_handle m, int32_t *created, int32_t *apart
  * Returns SPD_E_ARG for an unknown name or a value outside the list.  What is fixed at creation (the pruned transform
  * table, the geopotential fold) is read from the environment only. */
 int spd_model_set_option(spd_model_handle m, const char *name, int32_t value);
-/* ... and read back, by the same names */
+/* ... and read back, by the same names.  One name is read-only:
+ *   "quiet_rim_members"    the number of members whose coefficients beyond the truncation's halo (m + n >= 33) the last call of
+ *                          spd_model_step / spd_model_step_checked_begin found to be all-zero bits at its first step, and whose
+ *                          dead coefficient blocks its later steps therefore left alone; -1 when that call did not look (a call of
+ *                          one step, or launches that fold the geopotential: ensembles of up to 8 members).  Waits for the device. */
 int spd_model_get_option(spd_model_handle m, const char *name, int32_t *value);
 /* BASELINE cfg 5: fp32 != 0 runs the arithmetic of the column physics (physics.f90:107-256 and the schemes it calls) in
  * single precision; the model state, the grid-point dynamics and the tendencies handed to the transforms stay fp64 (the

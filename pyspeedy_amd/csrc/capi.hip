@@ -310,6 +310,11 @@ long spd_get_table_host(spd_handle h, const char *name, double *buf, size_t buf_
             for (int m = 0; m < MX; ++m) tmp[n * MX + m] = tri::inv_needed(m, n) ? 1.0 : 0.0;
         arr(tmp);
     }
+    else if (s == "tri_dead_blocks") {  // triangle.hpp: per block of 8 coefficients k = m + 31 n, 1 where the block is dead
+        tmp.assign(tri::kBlocks, 0.0);
+        for (int b = 0; b < tri::kBlocks; ++b) tmp[b] = tri::dead_block(b) ? 1.0 : 0.0;
+        arr(tmp);
+    }
     else return fail(SPD_E_ARG, "spd_get_table_host: unknown table '" + s + "'");
     if (buf) {
         if (buf_elems < n) return fail(SPD_E_SIZE, "spd_get_table_host: buffer too small for '" + s + "'");

@@ -99,11 +99,23 @@ __device__ __forceinline__ d2 geo_corr(d2 ph, d2 t_below, d2 t_above, double cor
 }
 }  // namespace
 
+// The quiet rim (model.hip: step_impl chooses the mode and says why it is sound).  kRimDetect: a step that does what the plain
+// one does and, for every dead block of coefficients (triangle.hpp), clears the member's flag unless every bit the block loaded
+// and every bit it is about to store is zero.  kRimSkip: the dead blocks of a member whose flag still stands do nothing.
+// A template parameter and not a run-time switch, as FOLD below; the plain form takes an empty struct where the others take the
+// flags.
+struct NoRim {};
+template <int RIM>
+using RimArg = std::conditional_t<RIM == kRimPlain, NoRim, int *>;
+
 // geopotential from temperature at time level `tl`.  SPPT: the blocks behind the geopotential ones advance the AR(1) pattern
 // of the stochastic physics (sppt_point.hpp) -- both are the small launches that open a step of an ensemble with SPPT, neither
 // depends on the other, so they share one (tendencies.f90:229 and physics.f90:234-236 in one launch).
-template <bool SPPT>
-__global__ __launch_bounds__(kT) void geopotential_kernel(ModelPtrs P, DynDeviceTables D, int first, int count, int tl, SpptArgs sp) {
+// RIM == kRimSkip: a lane whose coefficient is in a dead block of a quiet member leaves the +0.0 that is there (8 lanes = one line).
+template <bool SPPT, int RIM = kRimPlain>
+__global__ __launch_bounds__(kT) void geopotential_kernel(ModelPtrs P, DynDeviceTables D, int first, int count, int tl, SpptArgs sp,
+                                                          RimArg<RIM> rim) {
+    static_assert(RIM == kRimPlain || RIM == kRimSkip, "the geopotential launch has nothing to detect");
     // (writes P.phi: the geopotential the current step uses)
     const int ngeo = (count * NSPEC + kT - 1) / kT;
     if (SPPT && static_cast<int>(blockIdx.x) >= ngeo) {
@@ -113,6 +125,9 @@ __global__ __launch_bounds__(kT) void geopotential_kernel(ModelPtrs P, DynDevice
     const int gid = blockIdx.x * kT + threadIdx.x;
     if (gid >= count * NSPEC) return;
     const int lm = gid / NSPEC, mem = first + lm, k = gid - lm * NSPEC, m = k % MX;
+    if constexpr (RIM == kRimSkip) {
+        if (tri::dead_block(k / tri::kBlock) && rim[mem] != 0) return;
+    }
     const d2 *t = reinterpret_cast<const d2 *>(P.t) + (static_cast<size_t>(mem) * 2 + tl) * 8 * NSPEC + k;
     d2 *phi = reinterpret_cast<d2 *>(P.phi) + static_cast<size_t>(mem) * 8 * NSPEC + k;
     d2 tt[KX], ph[KX];
@@ -183,10 +198,15 @@ __device__ inline d2 pick(const d2 (&a)[N], int l) {
 // column kernel only, as this kernel's spectral work depends on the transforms only: the blocks behind the spectral ones
 // do the coupling for 256 grid points each, in the same launch -- one kernel boundary less and, for ensembles that do not
 // fill the GPU, the coupling runs beside the spectral step instead of after it.  CA = NoCoupler (empty): spectral work only.
+//
+// RIM: the quiet rim (above), for launches without FOLD.  In kRimSkip the wavefront of a dead block of a quiet member returns
+// before its first load; the test is wave-uniform (a wavefront is one member and one block), so gather_levels never sees a
+// partial wavefront.
 struct NoCoupler {};
-template <bool FOLD, bool EARLY, typename CA>
+template <bool FOLD, bool EARLY, typename CA, int RIM = kRimPlain>
 __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTables T, DynDeviceTables D, int M, int first,
-                                                           int count, int j1, double dt, double eps, CA cpl) {
+                                                           int count, int j1, double dt, double eps, CA cpl, RimArg<RIM> rim) {
+    static_assert(!FOLD || RIM == kRimPlain, "the folded form (small, latency-bound launches) has no rim modes");
     int nblocks = gridDim.x;  // blocks of spectral work
     if constexpr (std::is_same<CA, CouplerArgs>::value) {
         nblocks = (count * NSPEC * KX + kT - 1) / kT;
@@ -210,6 +230,18 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
     if (w >= count * kCoefBlocks) return;  // whole wavefronts only: the gathers below need all 64 lanes
     const int l = lane >> 3, kk = lane & 7;
     const int lm = w / kCoefBlocks, mem = first + lm, k = (w - lm * kCoefBlocks) * 8 + kk, n = k / MX, m = k - n * MX;
+    if constexpr (RIM == kRimSkip) {
+        if (tri::dead_block(w - lm * kCoefBlocks) && rim[mem] != 0) return;
+    }
+    // kRimDetect: the OR of the bit patterns of everything this lane loads from the state and stores to it ("quiet" is a
+    // statement about bits: -0.0, NaN and junk are not quiet).  The tendencies of a dead block are the +0.0 of the packed fields.
+    unsigned seen = 0;
+    auto note = [&](d2 v) {
+        if constexpr (RIM == kRimDetect) {
+            const unsigned long long x = __double_as_longlong(v.x) | __double_as_longlong(v.y);
+            seen |= static_cast<unsigned>(x) | static_cast<unsigned>(x >> 32);
+        }
+    };
     const size_t f8 = static_cast<size_t>(mem) * 8 * NSPEC;        // [M][8] arrays of whole fields (phi)
     const size_t fo = static_cast<size_t>(l) * NSPEC;
     // the packed tendency fields of this member and level (triangle.hpp)
@@ -263,6 +295,7 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
         trf = T.trfilt[k];
         tcorh = reinterpret_cast<const d2 *>(P.tcorh)[static_cast<size_t>(mem) * NSPEC + k];
         qcorh = reinterpret_cast<const d2 *>(P.qcorh)[static_cast<size_t>(mem) * NSPEC + k];
+        note(tcorh), note(qcorh);
     };
     if constexpr (EARLY) {
         load_tendencies(true);
@@ -336,6 +369,7 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
     {   // geopotential (valid for time level 1: formed before the physics) and its Laplacian
         if constexpr (!EARLY) ph = reinterpret_cast<const d2 *>(P.phi)[f8 + fo + k];
         const double c = RGASd * tref_l;
+        note(ph), note(ps1);
         const d2 x = d2{ph.x + c * ps1.x, ph.y + c * ps1.y};
         const d2 lap = d2{-x.x * el2, -x.y * el2};
         divdt = d2{divdt.x - lap.x, divdt.y - lap.y};
@@ -382,6 +416,7 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
     // step_field_2d, time_stepping.f90:164-188, on the two time levels o1, o2 of a field (loaded above); returns level 1
     auto advance = [&](d2 *base, size_t stride, d2 o1, d2 o2, d2 fdt) -> d2 {
         if (!EARLY) o1 = base[0], o2 = base[stride];
+        note(o1), note(o2);
         fdt = d2{fdt.x * trf, fdt.y * trf};
         const d2 oj = (j1 == 0) ? o1 : o2;
         const d2 fnew = d2{o1.x + dt * fdt.x, o1.y + dt * fdt.y};
@@ -390,6 +425,7 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
         const d2 oja = (j1 == 0) ? n1 : oj;
         const double we2 = (1.0f - WILd) * eps;
         const d2 n2 = d2{fnew.x - we2 * (n1.x - 2.0f * oja.x + fnew.x), fnew.y - we2 * (n1.y - 2.0f * oja.y + fnew.y)};
+        note(n1), note(n2);
         stream_store(&base[0], n1);
         stream_store(&base[stride], n2);
         return n1;
@@ -441,6 +477,9 @@ __global__ __launch_bounds__(kT) void spectral_step_kernel(ModelPtrs P, DeviceTa
         }
     }
     if (l == 0) advance(psS, NSPEC, ps1, ps2, psdt);  // ln ps has no vertical index: the two time levels are NSPEC apart
+    if constexpr (RIM == kRimDetect) {  // (every lane arrives here: ps level 2 is in the lanes of level 0, ps level 1 in all)
+        if (tri::dead_block(w - lm * kCoefBlocks) && __any(seen != 0) && lane == 0) rim[mem] = 0;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -458,15 +497,19 @@ __global__ __launch_bounds__(64 * KX) void diagnostics_kernel(CheckArgs c, Devic
 // ---------------------------------------------------------------------------------------------------------
 // (first, count): the members the launch works on; M: members in the arrays (strides between the blocks of specu / specv)
 // sppt != nullptr: the launch also advances the SPPT pattern (all members of the model) in its tail blocks
+// rim != nullptr: kRimSkip with the members' quiet-rim flags (model.hip: step_impl)
 hipError_t run_geopotential(const ModelPtrs &P, const DynDeviceTables &D, int first, int count, int tl, const SpptArgs *sppt,
-                            hipStream_t s) {
+                            int *rim, hipStream_t s) {
     const int ngeo = (count * NSPEC + kT - 1) / kT;
     if (sppt) {
         const long n = static_cast<long>(sppt->M) * KX * NSPEC;
-        launch(geopotential_kernel<true>, dim3(ngeo + static_cast<unsigned>((n + kT - 1) / kT)), dim3(kT), 0, s, P, D,
-                           first, count, tl, *sppt);
+        const dim3 grid(ngeo + static_cast<unsigned>((n + kT - 1) / kT));
+        if (rim) launch(geopotential_kernel<true, kRimSkip>, grid, dim3(kT), 0, s, P, D, first, count, tl, *sppt, rim);
+        else launch(geopotential_kernel<true>, grid, dim3(kT), 0, s, P, D, first, count, tl, *sppt, NoRim{});
+    } else if (rim) {
+        launch(geopotential_kernel<false, kRimSkip>, dim3(ngeo), dim3(kT), 0, s, P, D, first, count, tl, SpptArgs{}, rim);
     } else {
-        launch(geopotential_kernel<false>, dim3(ngeo), dim3(kT), 0, s, P, D, first, count, tl, SpptArgs{});
+        launch(geopotential_kernel<false>, dim3(ngeo), dim3(kT), 0, s, P, D, first, count, tl, SpptArgs{}, NoRim{});
     }
     return hipGetLastError();
 }
@@ -477,29 +520,37 @@ hipError_t run_dyn_grid(const ModelPtrs &P, const DynDeviceTables &D, int M, hip
 // cpl != nullptr: the coupling of the step rides in the same launch (tail blocks).  Small launches use the form of the kernel
 // with all loads up front (EARLY): same arithmetic, 2 instead of 4 wavefronts per SIMD, a fraction of the memory round trips.
 namespace {
-template <bool FOLD, bool EARLY, typename CA>
+template <bool FOLD, bool EARLY, typename CA, int RIM = kRimPlain>
 void launch_spectral_step(dim3 grid, hipStream_t s, const ModelPtrs &P, const DeviceTables &T, const DynDeviceTables &D, int M,
-                          int first, int count, int j1, double dt, double eps, const CA &cpl) {
-    launch(spectral_step_kernel<FOLD, EARLY, CA>, grid, dim3(kT), 0, s, P, T, D, M, first, count, j1, dt, eps, cpl);
+                          int first, int count, int j1, double dt, double eps, const CA &cpl, RimArg<RIM> rim = {}) {
+    launch(spectral_step_kernel<FOLD, EARLY, CA, RIM>, grid, dim3(kT), 0, s, P, T, D, M, first, count, j1, dt, eps, cpl, rim);
 }
 template <typename CA>
-void dispatch_spectral_step(bool fold, bool early, dim3 grid, hipStream_t s, const ModelPtrs &P, const DeviceTables &T,
-                            const DynDeviceTables &D, int M, int first, int count, int j1, double dt, double eps, const CA &cpl) {
+void dispatch_spectral_step(bool fold, bool early, int rim_mode, int *rim, dim3 grid, hipStream_t s, const ModelPtrs &P,
+                            const DeviceTables &T, const DynDeviceTables &D, int M, int first, int count, int j1, double dt, double eps,
+                            const CA &cpl) {
     if (fold && early) launch_spectral_step<true, true, CA>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl);
     else if (fold) launch_spectral_step<true, false, CA>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl);
+    else if (rim_mode == kRimDetect && early) launch_spectral_step<false, true, CA, kRimDetect>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl, rim);
+    else if (rim_mode == kRimDetect) launch_spectral_step<false, false, CA, kRimDetect>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl, rim);
+    else if (rim_mode == kRimSkip && early) launch_spectral_step<false, true, CA, kRimSkip>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl, rim);
+    else if (rim_mode == kRimSkip) launch_spectral_step<false, false, CA, kRimSkip>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl, rim);
     else if (early) launch_spectral_step<false, true, CA>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl);
     else launch_spectral_step<false, false, CA>(grid, s, P, T, D, M, first, count, j1, dt, eps, cpl);
 }
 }  // namespace
+// rim_mode: kRimPlain, or kRimDetect / kRimSkip with the members' quiet-rim flags in `rim` (launches without the folded
+// geopotential only: P.phi_next == nullptr)
 hipError_t run_spectral_step(const ModelPtrs &P, const DeviceTables &T, const DynDeviceTables &D, int M, int first, int count,
-                             int j1, double dt, double eps, const CouplerArgs *cpl, bool early, hipStream_t s) {
+                             int j1, double dt, double eps, const CouplerArgs *cpl, bool early, int rim_mode, int *rim, hipStream_t s) {
     const int nspec = (count * NSPEC * KX + kT - 1) / kT;
     const bool fold = P.phi_next != nullptr;
+    if (fold && rim_mode != kRimPlain) return hipErrorInvalidValue;
     if (cpl)
-        dispatch_spectral_step(fold, early, dim3(nspec + (cpl->count * NG + kT - 1) / kT), s, P, T, D, M, first, count, j1, dt, eps,
-                               *cpl);
+        dispatch_spectral_step(fold, early, rim_mode, rim, dim3(nspec + (cpl->count * NG + kT - 1) / kT), s, P, T, D, M, first, count,
+                               j1, dt, eps, *cpl);
     else
-        dispatch_spectral_step(fold, early, dim3(nspec), s, P, T, D, M, first, count, j1, dt, eps, NoCoupler{});
+        dispatch_spectral_step(fold, early, rim_mode, rim, dim3(nspec), s, P, T, D, M, first, count, j1, dt, eps, NoCoupler{});
     return hipGetLastError();
 }
 hipError_t run_diagnostics(const ModelPtrs &P, const DeviceTables &T, int M, int tl, int *err, double *diag, int ticket,

@@ -41,10 +41,10 @@ hipError_t run_physics(const DeviceTables &T, const spd_physics_args &a, int nme
 hipError_t run_dyn_physics(const ModelPtrs &P, const DynDeviceTables &D, const DeviceTables &T, const spd_physics_args &a,
                            int first, int nmembers, int fp32, int store32, int diag, hipStream_t s);
 hipError_t run_geopotential(const ModelPtrs &P, const DynDeviceTables &D, int first, int count, int tl, const SpptArgs *sppt,
-                            hipStream_t s);
+                            int *rim, hipStream_t s);
 hipError_t run_dyn_grid(const ModelPtrs &P, const DynDeviceTables &D, int M, hipStream_t s);
 hipError_t run_spectral_step(const ModelPtrs &P, const DeviceTables &T, const DynDeviceTables &D, int M, int first, int count,
-                             int j1, double dt, double eps, const CouplerArgs *cpl, bool early, hipStream_t s);
+                             int j1, double dt, double eps, const CouplerArgs *cpl, bool early, int rim_mode, int *rim, hipStream_t s);
 hipError_t run_diagnostics(const ModelPtrs &P, const DeviceTables &T, int M, int tl, int *err, double *diag, int ticket,
                            hipStream_t s);
 hipError_t run_diagnostics_range(const ModelPtrs &P, const DeviceTables &T, int first, int count, int tl, int *err, double *diag,
@@ -129,6 +129,10 @@ struct spd_model {
     bool groups_apart = true;  // every group stream created so far was measured to run side by side with the others
     int *d_err = nullptr;
     double *d_diag = nullptr;
+    // The quiet rim: one flag per member, armed and established by the device inside a multi-step call (step_impl) and valid in
+    // that call only.  rim_call: the last call of spd_model_step / _step_checked_begin used the flags (option "quiet_rim_members").
+    int *d_rim = nullptr;
+    bool rim_call = false;
     // asynchronous range check (spd_model_check_begin / _end): two pinned result slots with their events
     int *h_err[2] = {nullptr, nullptr}, *h_err_sync = nullptr;  // (h_err_sync: pinned staging of the synchronous check)
     hipEvent_t err_event[2] = {nullptr, nullptr};
@@ -780,6 +784,8 @@ int spd_model_create(spd_handle h, int nmembers, spd_model_handle *out) {
         m->d_err = static_cast<int *>(p);
         if (rc == SPD_OK) rc = arena_alloc(m, sizeof(double) * M * 24, &p);
         m->d_diag = static_cast<double *>(p);
+        if (rc == SPD_OK) rc = arena_alloc(m, sizeof(int) * M, &p);
+        m->d_rim = static_cast<int *>(p);
     }
     if (rc == SPD_OK) rc = build_tables(m);
     if (rc != SPD_OK) {
@@ -1029,7 +1035,7 @@ static void sppt_advance(spd_model *m) {
 // ride != nullptr: the range check of the PREVIOUS step of these members rides in this step's spectral -> grid launch
 static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int compute_shortwave, int first, int count, int diag,
                              bool run_geo, const CouplerArgs *cpl, hipStream_t s, hipEvent_t after_grid2spec = nullptr,
-                             const CheckArgs *ride = nullptr) {
+                             const CheckArgs *ride = nullptr, int rim_mode = kRimPlain) {
     const DeviceTables &T = m->ctx->dev;
     const int M = m->M;
     hipError_t e = hipSuccess;
@@ -1044,7 +1050,8 @@ static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int comput
                        m->sppt_step, m->sppt_first ? 1 : 0);
     if (run_geo) {
         ProfScope ps(m, SPD_K_GEOPOTENTIAL, count, s);
-        e = run_geopotential(m->P, m->D, first, count, 0, m->sppt_on ? &sp : nullptr, s);  // tendencies.f90:229
+        e = run_geopotential(m->P, m->D, first, count, 0, m->sppt_on ? &sp : nullptr, rim_mode == kRimSkip ? m->d_rim : nullptr,
+                             s);  // tendencies.f90:229
     } else if (m->sppt_on) {
         ProfScope ps(m, SPD_K_SPPT, 8 * count, s);
         e = run_sppt_update(sp, s);
@@ -1098,7 +1105,7 @@ static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int comput
     if (e == hipSuccess) {
         ProfScope ps(m, SPD_K_SPECTRAL_STEP, count, s);
         const bool early = m->spectral_early < 0 ? count <= 8 : m->spectral_early != 0;
-        e = run_spectral_step(m->P, T, m->D, M, first, count, j1 - 1, dt, eps, cpl, early, s);
+        e = run_spectral_step(m->P, T, m->D, M, first, count, j1 - 1, dt, eps, cpl, early, rim_mode, m->d_rim, s);
     }
     return e;
 }
@@ -1527,6 +1534,23 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     const bool may_round = G > 1 || (m->nchunks == 1 && m->profile == 0 && !m->split_dyn_physics);
     if (may_round && nsteps > 1 && m->block_members > 0 && m->M >= 4 * m->block_members)
         rounds = (m->M + G * m->block_members - 1) / (G * m->block_members);
+    // The quiet rim.  A coefficient beyond the truncation's halo (m + n >= 33, triangle.hpp) feeds nothing but itself, and a member
+    // whose state is all +0.0 bits there stays so: its tendencies there are the +0.0 of the packed fields, and the spectral step
+    // makes +0.0 of +0.0 (diffuse: (+-0 - a (+0)) b = +-0; advance: +0 + dt (+-0) = +0, and the two filter lines keep +0; the
+    // semi-implicit sums are sums of zeros added to +0).  Such a member moves 563 KB of zeros per step to reproduce zeros.  A call
+    // of two steps or more whose launches do not fold the geopotential therefore issues its FIRST step (of each round, for that
+    // round's members) in the detect mode: the flags of the step's members are armed in front of it, the step does what the plain
+    // one does, and every wavefront of a dead block clears its member's flag unless everything it loaded (vor, div, t, tr, ps at
+    // both levels, phi, tcorh, qcorh) and everything it stored was zero, bit for bit.  Every later step runs in the skip mode:
+    // the dead blocks of a member whose flag stands are left alone by the spectral step and by the geopotential launch.
+    // The flag stays true through the call: the skipped blocks are not written by anybody; phis does not change inside a call;
+    // tcorh and qcorh change only where the first step of a day rewrites them (forcing_range: a direct transform, which stores
+    // +0.0 beyond the triangle -- so what detect saw as zero is zero afterwards, and a member that detect found loud stays loud
+    // for the rest of the call, which is merely slower); phi is recomputed every step from t and phis, and detect saw the +0.0
+    // that this t and phis give.  Nothing is carried from call to call -- a host may write the state between calls, through
+    // device views as well -- and calls of one step never skip.
+    const bool rim = nsteps >= 2 && !m->fold_geo;
+    m->rim_call = rim;
     struct HostState {  // what a step changes on the host side of the model
         Calendar cal;
         int current_step, phi_cur;
@@ -1640,12 +1664,15 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                 if (rc == SPD_OK) {
                     hipError_t e = hipSuccess;
                     if (offset && first_of_call && g == 1) e = hipStreamWaitEvent(gs[1], m->ev_offset, 0);
+                    if (rim && it == 0 && e == hipSuccess)  // arm the flags of this group's members, on its stream
+                        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_rim + first), 1, static_cast<size_t>(count), gs[g]);
                     // (the check of the step before this one, for these members: written to that step's row)
                     const CheckArgs chk{m->P.vor, m->P.div, m->P.t, tl_check, record && it > 0 ? m->h_steps_err + static_cast<size_t>(it - 1) * m->M : nullptr,
                                         nullptr, m->steps_ticket, first};
                     if (e == hipSuccess)
                         e = step_range(m, 2, 2, 2 * delt, sw, first, count, diag, run_geo, &cpl, gs[g],
-                                       (offset && first_of_call && g == 0) ? m->ev_offset : nullptr, record && it > 0 ? &chk : nullptr);
+                                       (offset && first_of_call && g == 0) ? m->ev_offset : nullptr, record && it > 0 ? &chk : nullptr,
+                                       rim ? (it == 0 ? kRimDetect : kRimSkip) : kRimPlain);
                     if (e != hipSuccess) {
                         (void)hipGetLastError();
                         rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
@@ -1986,6 +2013,18 @@ int spd_model_get_option(spd_model_handle m, const char *name, int32_t *value) {
     else if (key == "member_groups") *value = m->nchunks;
     else if (key == "block_members") *value = m->block_members;
     else if (key == "physics_storage32") *value = m->phys_store32 ? 1 : 0;
+    else if (key == "quiet_rim_members") {
+        // members whose rim the last multi-step call found quiet (step_impl); -1 when the last call did not look (one step, or
+        // launches that fold the geopotential).  Waits for the device: the call's streams were joined into the caller's.
+        *value = -1;
+        if (m->rim_call) {
+            std::vector<int> flags(static_cast<size_t>(m->M));
+            M_HIP(hipDeviceSynchronize());
+            M_HIP(hipMemcpy(flags.data(), m->d_rim, sizeof(int) * flags.size(), hipMemcpyDeviceToHost));
+            *value = 0;
+            for (int f : flags) *value += f != 0 ? 1 : 0;
+        }
+    }
     else return m_fail(SPD_E_ARG, "spd_model_get_option: unknown option: " + key);
     return SPD_OK;
 }

@@ -29,6 +29,10 @@ struct ModelPtrs {
     double *spec_ps;                       // [M][528]
 };
 
+// How a launch of the spectral step (and of the geopotential) treats the coefficient blocks beyond the truncation's halo
+// (triangle.hpp: dead_block; dynamics.hip; model.hip: step_impl)
+enum RimMode : int { kRimPlain = 0, kRimDetect = 1, kRimSkip = 2 };
+
 struct DynDeviceTables {
     const double *dmp, *dmpd, *dmps, *dmp1, *dmp1d, *dmp1s, *elz;  // (31,32)
     const double *xj, *xc, *xd;                                    // (8,8,64), (8,8), (8,8)

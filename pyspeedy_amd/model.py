@@ -291,6 +291,18 @@ class EnsembleModel:
             raise ValueError("unknown option or value out of range: %s = %r" % (name, value))
         check(rc, "spd_model_set_option")
 
+    def get_option(self, name):
+        """The value of a switch of set_option, or of a read-only figure (spd_model_get_option): quiet_rim_members is the number
+        of members whose coefficients beyond the truncation's halo the last multi-step call found to be all-zero bits and left
+        alone, -1 when that call did not look (a call of one step, or an ensemble of up to 8 members).  ValueError for an
+        unknown name."""
+        value = C.c_int32(0)
+        rc = self._lib.spd_model_get_option(self._m, name.encode(), C.byref(value))
+        if rc == _lib.SPD_E_ARG:
+            raise ValueError("unknown option: %s" % name)
+        check(rc, "spd_model_get_option")
+        return value.value
+
     def profile(self, level=1):
         """HIP-event brackets on the launch stream: 0 off, 1 the spectral->grid launch of every step, 2 every kernel."""
         check(self._lib.spd_model_profile(self._m, int(level)), "spd_model_profile")

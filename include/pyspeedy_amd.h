@@ -558,6 +558,77 @@ int spd_model_acctape_info(spd_model_handle m, long long *taken, int *held, int 
 int spd_model_acctape_times(spd_model_handle m, int32_t *rows, int max_rows);
 int spd_model_acctape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
                            size_t dst_bytes, void *stream);
+/* The window tape: window sums, means, minima, maxima and threshold counts of the STATE's grid-space fields, accumulated on the
+ * device inside spd_model_step / spd_model_step_checked_begin calls of any length: the monthly mean of z_plev at 500 hPa, the day's
+ * lowest t_grid, the month's strongest wind, the samples of a month below 273.15 K.  A sixth recorder, independent of statistics,
+ * tape, spectra, ensemble tape and accumulation tape (its own front end, slab, tables and allocation); with it off no launch of a
+ * step changes, and recording changes nothing of the run.
+ * An entry is (name, op[, threshold]).  Names: the fourteen of the tape (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv,
+ * precls, u_plev, v_plev, t_plev, q_plev, z_plev, mslp; the pressure-level ones after spd_model_plev_configure) and two of this
+ * recorder only: wspd_grid (8 levels) and wspd_plev (the configured levels), sqrt(u * u + v * v) of u_grid, v_grid and of u_plev,
+ * v_plev.  Ops: SPD_WIN_SUM, SPD_WIN_MEAN, SPD_WIN_MIN, SPD_WIN_MAX (the numbers of SPD_ACC_*), SPD_WIN_COUNT_ABOVE (samples with
+ * x > threshold) and SPD_WIN_COUNT_BELOW (x < threshold); thresholds[k] is read for the two count ops only, must be finite, and is
+ * in the entry's own unit.  The value sampled is exactly what an fp64 tape of the same name holds (export units); a wind speed is
+ * formed from those fp64 values of u and v by four correctly rounded IEEE operations (two products, their sum, the square root; no
+ * fused multiply-add).
+ * Sampling: after every step that leaves the model's absolute step counter at a multiple of `sample_every` (the tape's rule).
+ * Windows, one kind for the whole recorder: SPD_WINDOW_STEPS closes after a step that leaves the counter at a multiple of `every`;
+ * SPD_WINDOW_DAY after a step whose resulting date is 00:00; SPD_WINDOW_MONTH after a step whose resulting date is 00:00 on day 1
+ * (the model's own calendar); `every` is 0 for the two calendar kinds.  Closing and sampling are separate decisions: a closing step
+ * that is not sampled closes what was accumulated, and a window without a sample closes with 0 samples: sum and counts 0, mean,
+ * minimum and maximum quiet NaN.  The first window after _configure, _reset or spd_model_init (or after the step counter was set by
+ * spd_model_mark_initialized / spd_model_set_control) starts at the model's current step and may be short; windows run across call
+ * boundaries.  The arithmetic is fixed, so the result does not depend on the launch plan: sum in fp64 in sample order starting from
+ * the first sample itself; mean, that sum divided by the number of samples (one IEEE division at the close); min / max, acc = x <
+ * acc ? x : acc and acc = x > acc ? x : acc from the first sample; counts as fp64 integers.  Window k (from 1 since the last reset)
+ * lies in ring slot (k - 1) % capacity; the ring holds, per entry, [slot][members][levels][4608] elements, SPD_TAPE_F64 (the fp64
+ * results) or SPD_TAPE_F32 (each rounded to the nearest float).  On a sampled step the diagnostics-only outputs are stored when
+ * precnv or precls is an entry (the tape's rule).
+ *   _configure  allocates ring, accumulators (only those an entry needs), slab and tables in one hipMalloc of its own (synchronises
+ *               the device) and empties the ring; n_entries = 0 switches the recorder off and frees it.  SPD_E_ARG, checked in this
+ *               order before a model or a device is needed: a bad list; an unknown name; an unknown op; a count op without a finite
+ *               threshold (thresholds may be NULL when no entry counts); the same (name, op) twice; an unknown window kind; `every`
+ *               (at least 1 for SPD_WINDOW_STEPS, 0 otherwise); sample_every < 1; capacity < 1; an unknown dtype; a null model; then
+ *               a pressure-level name (wspd_plev included) before spd_model_plev_configure, or a checked call in flight.
+ *               SPD_E_DEVICE with the number of bytes asked for when the allocation fails: the recorder is then off and the model
+ *               as usable as before.  spd_model_plev_configure is refused while the recorder holds a pressure-level name.
+ *   _reset      empties the ring and starts a new window at the model's current step (host only, no device work).
+ *               spd_model_init does the same.
+ *   _info       taken: windows closed since the last reset; held = min(taken, capacity); any pointer may be NULL.
+ *   _times      rows[held][8] for the held windows, oldest first: the absolute step counter after the window's last step, then
+ *               year, month, day, hour, minute of that state, then the number of samples and the number of steps in the window
+ *               (host memory).  Returns the number of rows written (at most max_rows).
+ *   _read       members [first, first + count) and windows [t0, t0 + nt) of the held ones, oldest first, of one entry into
+ *               dst_device[count][nt][levels][48][96] ([count][nt][48][96] for ps_grid, precnv, precls, mslp) in the ring's dtype,
+ *               stream-ordered; dst_device must be 16-byte aligned.  SPD_E_SIZE when dst_bytes is too small.
+ * Reads fail (SPD_E_ARG, with the reason) while a checked call is in flight and after a checked call that reported a failed range
+ * check (the message names the member and the step): the series stays invalid until _reset or spd_model_init.
+ * spd_model_copy_member does not carry the recorder, and the outer boundary (spd_parallel_step*) does not keep it across the
+ * models it merges and splits.
+ * spd_wintape_plan is the recorder's schedule, the same code the step loop takes its decisions from, for hosts that want to know
+ * the windows ahead: from the date y-m-d h:min and the step counter step0, over nsteps steps of 40 minutes, it returns the number
+ * of windows that close and fills rows[min(that number, max_rows)][8] as _times does (the first window starts at step0).  It needs
+ * no model and no device; SPD_E_ARG for a bad date, step0 < 0, nsteps < 0, a bad destination, or the window kind, `every` and
+ * sample_every that _configure refuses. */
+#define SPD_WIN_SUM 0
+#define SPD_WIN_MEAN 1
+#define SPD_WIN_MIN 2
+#define SPD_WIN_MAX 3
+#define SPD_WIN_COUNT_ABOVE 4
+#define SPD_WIN_COUNT_BELOW 5
+#define SPD_WINDOW_STEPS 0
+#define SPD_WINDOW_DAY 1
+#define SPD_WINDOW_MONTH 2
+int spd_model_wintape_configure(spd_model_handle m, const char *const *names, const int *ops, const double *thresholds, int n_entries,
+                                int window, int every, int sample_every, int capacity, int dtype);
+int spd_model_wintape_reset(spd_model_handle m);
+int spd_model_wintape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *window, int *every, int *sample_every,
+                           int *dtype);
+int spd_model_wintape_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
+                           size_t dst_bytes, void *stream);
+int spd_wintape_plan(int year, int month, int day, int hour, int minute, int step0, int nsteps, int window, int every,
+                     int sample_every, int32_t *rows, int max_rows);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

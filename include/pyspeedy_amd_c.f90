@@ -9,7 +9,8 @@
 !!   check           -> spd_model_check                   transform_spectral2grid ... -> spd_model_spectral2grid ...
 !! and, without a counterpart there: time statistics on the device (spd_model_stats_*), pressure-level fields (spd_model_plev_*),
 !! time series recorded on the device (spd_model_tape_*), spectra of the spectral state (spd_model_spectra_*), the series of
-!! the ensemble mean and spread (spd_model_enstape_*) and window sums, means and extremes of the physics fluxes (spd_model_acctape_*)
+!! the ensemble mean and spread (spd_model_enstape_*), window sums, means and extremes of the physics fluxes (spd_model_acctape_*)
+!! and window means, extremes and threshold counts of the state's fields (spd_model_wintape_*, spd_wintape_plan)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -19,6 +20,9 @@ module pyspeedy_amd_c
     integer(c_int), parameter :: SPD_TAPE_F32 = 0, SPD_TAPE_F64 = 1
     integer(c_int), parameter :: SPD_ENS_MEAN = 0, SPD_ENS_STD = 1, SPD_ENS_M2 = 2
     integer(c_int), parameter :: SPD_ACC_SUM = 0, SPD_ACC_MEAN = 1, SPD_ACC_MIN = 2, SPD_ACC_MAX = 3
+    integer(c_int), parameter :: SPD_WIN_SUM = 0, SPD_WIN_MEAN = 1, SPD_WIN_MIN = 2, SPD_WIN_MAX = 3
+    integer(c_int), parameter :: SPD_WIN_COUNT_ABOVE = 4, SPD_WIN_COUNT_BELOW = 5
+    integer(c_int), parameter :: SPD_WINDOW_STEPS = 0, SPD_WINDOW_DAY = 1, SPD_WINDOW_MONTH = 2
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -311,6 +315,51 @@ module pyspeedy_amd_c
             character(kind=c_char), intent(in) :: name(*)
             integer(c_int), value :: op, first, count, t0, nt
             integer(c_size_t), value :: dst_bytes
+        end function
+        ! the window tape: window sums, means, minima, maxima and threshold counts of the state's grid-space fields, accumulated on
+        ! the device behind the sampled steps; windows close every `every` steps, at midnight or at month ends (pyspeedy_amd.h:
+        ! spd_model_wintape_*).  An entry is names(k) with ops(k): SPD_WIN_SUM (0) ... _COUNT_BELOW (5); thresholds: c_loc of a
+        ! real(c_double) array of n_entries values, read for the count ops only (c_null_ptr without count ops); dtype as the tape's;
+        ! rows(8, *): the tape's six, the samples and the steps in the window; _read: (96, 48[, levels], nt, count) in the ring's
+        ! dtype.  spd_wintape_plan: the windows that close within nsteps steps from a date and a step counter (no model needed)
+        integer(c_int) function spd_model_wintape_configure(model, names, ops, thresholds, n_entries, window, every, sample_every, &
+                capacity, dtype) bind(C, name="spd_model_wintape_configure")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, thresholds
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: ops(*)
+            integer(c_int), value :: n_entries, window, every, sample_every, capacity, dtype
+        end function
+        integer(c_int) function spd_model_wintape_reset(model) bind(C, name="spd_model_wintape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_wintape_info(model, taken, held, capacity, window, every, sample_every, dtype) &
+                bind(C, name="spd_model_wintape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken
+            integer(c_int), intent(out) :: held, capacity, window, every, sample_every, dtype
+        end function
+        integer(c_int) function spd_model_wintape_times(model, rows, max_rows) bind(C, name="spd_model_wintape_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(8, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_wintape_read(model, name, op, first, count, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_wintape_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: op, first, count, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_wintape_plan(year, month, day, hour, minute, step0, nsteps, window, every, sample_every, rows, &
+                max_rows) bind(C, name="spd_wintape_plan")
+            import :: c_int, c_int32_t
+            integer(c_int), value :: year, month, day, hour, minute, step0, nsteps, window, every, sample_every, max_rows
+            integer(c_int32_t), intent(out) :: rows(8, *)
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
         ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for

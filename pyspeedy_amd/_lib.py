@@ -20,6 +20,8 @@ SPD_STATS_MEAN, SPD_STATS_VARIANCE, SPD_STATS_STD = 0, 1, 2  # kinds of spd_mode
 SPD_TAPE_F32, SPD_TAPE_F64 = 0, 1  # storage of spd_model_tape_configure
 SPD_ENS_MEAN, SPD_ENS_STD, SPD_ENS_M2 = 0, 1, 2  # kinds of spd_model_enstape_read
 SPD_ACC_SUM, SPD_ACC_MEAN, SPD_ACC_MIN, SPD_ACC_MAX = 0, 1, 2, 3  # ops of spd_model_acctape_configure / _read
+SPD_WIN_SUM, SPD_WIN_MEAN, SPD_WIN_MIN, SPD_WIN_MAX, SPD_WIN_COUNT_ABOVE, SPD_WIN_COUNT_BELOW = 0, 1, 2, 3, 4, 5  # ops of spd_model_wintape_*
+SPD_WINDOW_STEPS, SPD_WINDOW_DAY, SPD_WINDOW_MONTH = 0, 1, 2  # window kinds of spd_model_wintape_configure / spd_wintape_plan
 
 
 class SpeedyHipError(RuntimeError):
@@ -154,6 +156,14 @@ _SIGNATURES = {
     "spd_model_acctape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "spd_model_acctape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
+    "spd_model_wintape_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_int]),
+    "spd_model_wintape_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_wintape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 6),
+    "spd_model_wintape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_wintape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
+    "spd_wintape_plan": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int32), C.c_int]),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),
@@ -257,3 +267,28 @@ def check(rc, what):
     if rc != SPD_OK:
         msg = lib().spd_last_error()
         raise SpeedyHipError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
+
+
+def wintape_plan(start, step0, nsteps, window, sample_every=1):
+    """The windows the window tape (EnsembleModel.wintape_configure) closes within `nsteps` steps from the date `start` (a
+    datetime or (year, month, day, hour, minute)) and the step counter `step0`: an int32 array [windows][8] of the step counter
+    after the window, year, month, day, hour, minute of that state, the samples and the steps in the window.  `window` is a number
+    of steps, "day" or "month".  The library's own schedule (spd_wintape_plan): no model and no device are needed."""
+    import numpy as np
+    kinds = {"day": SPD_WINDOW_DAY, "month": SPD_WINDOW_MONTH}
+    if isinstance(window, str):
+        if window not in kinds:
+            raise ValueError("window must be a number of steps, 'day' or 'month', got %r" % (window,))
+        kind, every = kinds[window], 0
+    else:
+        kind, every = SPD_WINDOW_STEPS, int(window)
+    date = tuple(start) if isinstance(start, (tuple, list)) else (start.year, start.month, start.day, start.hour, start.minute)
+    args = [int(v) for v in date] + [int(step0), int(nsteps), kind, every, int(sample_every)]
+    n = lib().spd_wintape_plan(*args, None, 0)
+    if n < 0:
+        check(n, "spd_wintape_plan")
+    rows = np.zeros((max(n, 1), 8), dtype=np.int32)
+    n = lib().spd_wintape_plan(*args, rows.ctypes.data_as(C.POINTER(C.c_int32)), n)
+    if n < 0:
+        check(n, "spd_wintape_plan")
+    return rows[:n]

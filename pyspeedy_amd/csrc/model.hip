@@ -31,6 +31,7 @@
 #include "tape.hpp"
 #include "enstape.hpp"
 #include "acctape.hpp"
+#include "wintape.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
 
@@ -329,6 +330,30 @@ struct spd_model {
         void *alloc = nullptr, *data = nullptr;
         AccTapePlane *planes = nullptr;
     } acctape;
+    // The window tape (spd_model_wintape_*): window sums, means, extremes and threshold counts of the state's grid-space fields.
+    // The tape's front end (its own slab and tables) and an accumulate launch follow every step that samples (the tape's rule
+    // with `sample_every`); a window closes every `every` steps, at midnight or at month ends (wintape_advance) into ring slot
+    // (k - 1) % capacity, k the number of windows closed since the last reset; a closing step that does not sample launches the
+    // kernel alone.  One allocation of its own (hipMalloc): ring (per entry [slot][M][levels][4608], float or double), the fp64
+    // accumulators some entry needs ([M][levels][4608] each), slab, tables, plane descriptors.  The step the open window started
+    // at, its samples so far and the rows of the closed ones are host state.
+    struct WinTape : SampleFront {
+        struct Entry {
+            int name, op, levels;  // name: catalogue id, 14 wspd_grid, 15 wspd_plev
+            double threshold;
+            size_t offset;  // elements from `data` to slot 0, member 0 of the entry
+        };
+        bool on = false, valid = true;
+        int window = SPD_WINDOW_STEPS, every = 1, sample_every = 1, capacity = 0, dtype = SPD_TAPE_F32, nplanes = 0;
+        int window_start = -1;  // absolute step counter the open window began at (-1: at the next step that runs)
+        int samples = 0;        // samples the open window holds
+        long long taken = 0;    // windows closed since the last reset
+        std::string invalid_why;
+        std::vector<Entry> entries;
+        std::vector<int32_t> rows;  // [capacity][8]: step after the window, year, month, day, hour, minute, samples, steps
+        void *alloc = nullptr, *data = nullptr;
+        WinTapePlane *planes = nullptr;
+    } wintape;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {
@@ -339,6 +364,37 @@ struct spd_model {
         bool have[PLEV_NVARS] = {};   // computed since the levels were configured
     } plev;
 };
+
+// The window tape's schedule: the ONE place that decides whether a step samples and whether it closes the open window, for the step
+// loop (step_impl) and for spd_wintape_plan alike.
+namespace {
+struct WinSchedule {
+    int window, every, sample_every;
+};
+struct WinOpen {
+    int start, samples;  // the step counter the open window began at; the samples it holds
+};
+struct WinDecision {
+    bool sample, close;
+};
+// The step that leaves the counter at `step_after` and the date at `next`: a sample goes into the open window first; a closing
+// step then fills row[8] (spd_model_wintape_times) and opens the next window at step_after.
+WinDecision wintape_advance(const WinSchedule &s, WinOpen &w, int step_after, const spd::Calendar &next, int32_t *row) {
+    WinDecision d;
+    d.sample = step_after % s.sample_every == 0;
+    const bool midnight = next.hour == 0 && next.minute == 0;
+    d.close = s.window == SPD_WINDOW_STEPS ? step_after % s.every == 0 : s.window == SPD_WINDOW_DAY ? midnight : midnight && next.day == 1;
+    if (d.sample) ++w.samples;
+    if (d.close) {
+        row[0] = step_after; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+        row[6] = w.samples;
+        row[7] = step_after - w.start;
+        w.start = step_after;
+        w.samples = 0;
+    }
+    return d;
+}
+}  // namespace
 
 namespace spd {
 LaunchEvents &pending_launch_events() {
@@ -821,6 +877,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->spectra.alloc) (void)hipFree(m->spectra.alloc);
     if (m->enstape.alloc) (void)hipFree(m->enstape.alloc);
     if (m->acctape.alloc) (void)hipFree(m->acctape.alloc);
+    if (m->wintape.alloc) (void)hipFree(m->wintape.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1368,6 +1425,10 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->acctape.taken = 0;  // (... and an accumulation tape whose first window starts at the first step)
     m->acctape.window_start = -1;
     m->acctape.valid = true;
+    m->wintape.taken = 0;  // (... and a window tape whose first window starts at the first step)
+    m->wintape.window_start = -1;
+    m->wintape.samples = 0;
+    m->wintape.valid = true;
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1476,6 +1537,7 @@ static hipError_t stats_sample(spd_model *m, int first, int count, long long n, 
 static hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);   // (with spd_model_tape_configure)
 static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_spectra_configure)
 static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s);  // (with spd_model_enstape_configure)
+static hipError_t wintape_step(spd_model *m, int first, int count, int k, int close, int n, int slot, hipStream_t s);  // (with spd_model_wintape_configure)
 
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
@@ -1590,6 +1652,15 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     if (ac.on && (ac.window_start < 0 || ac.window_start > m->current_step)) ac.window_start = m->current_step;
     const long long acctape0 = ac.taken;
     const int acc_start0 = ac.window_start;
+    // the window tape: the open window (its first step, its samples so far) and the windows closed, put back for every round likewise
+    spd_model::WinTape &wt = m->wintape;
+    if (wt.on && (wt.window_start < 0 || wt.window_start > m->current_step)) {
+        wt.window_start = m->current_step;
+        wt.samples = 0;
+    }
+    const long long wintape0 = wt.taken;
+    const WinOpen win_open0{wt.window_start, wt.samples};
+    const WinSchedule win_schedule{wt.window, wt.every, wt.sample_every};
     // the ensemble tape's last sample of this call: a sample whose slot a later sample of the SAME call takes again is not folded at
     // all -- nobody can read it, and with rounds its members would otherwise land in the partials of the sample that replaced it
     long long enstape_last = enstape0;
@@ -1598,6 +1669,8 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
         long long taken = 0, tape_taken = 0, spectra_taken = 0, enstape_taken = 0, acctape_taken = 0;
         int acc_start = acc_start0;
+        long long wintape_taken = 0;
+        WinOpen win_open = win_open0;
         const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
         if (round > 0) {  // the same steps again, for the next members
             m->cal = start.cal;
@@ -1634,15 +1707,21 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             // the accumulation tape reads the diagnostics-only outputs of EVERY step; this step is number acc_step of its window
             const int acc_step = m->current_step + 1 - acc_start;
             const bool acc_close = ac.on && (m->current_step + 1) % ac.every == 0;
+            // the window tape: what this step does to the open window (sample number win_k of it, 0: none; win_n samples at a close)
+            Calendar next = m->cal;
+            next.advance();
+            WinDecision win{false, false};
+            WinOpen win_after = win_open;
+            int32_t win_row[8] = {};
+            if (wt.on) win = wintape_advance(win_schedule, win_after, m->current_step + 1, next, win_row);
+            const int win_k = win.sample ? win_open.samples + 1 : 0, win_n = win_open.samples + (win.sample ? 1 : 0);
             const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip) ||
-                              (fold_enstape && m->enstape.precip) || ac.on) ? 1 : 0;
+                              (fold_enstape && m->enstape.precip) || ac.on || (win.sample && wt.precip)) ? 1 : 0;
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
             // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
             // It rides as tail blocks in the step's spectral_step_kernel launch (dynamics.hip; as a launch of its own the step
             // was 2 ... 7 % slower).
-            Calendar next = m->cal;
-            next.advance();
             const TimeInterp w = time_interp(next);
             const int fresh = (!m->surf_cache_valid || (next.hour == 0 && next.minute == 0)) ? 1 : 0;
             if (m->sst_anomaly_flag && (w.a0 < 0 || w.a1 < 0 || w.a0 >= m->anom_planes || w.a1 >= m->anom_planes)) {
@@ -1730,6 +1809,15 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                         device_failed = true;
                     }
                 }
+                if (rc == SPD_OK && (win.sample || win.close)) {  // behind the accumulation tape's launch, on the same stream
+                    const hipError_t e = wintape_step(m, first, count, win_k, win.close ? 1 : 0, win_n,
+                                                      static_cast<int>((wintape0 + wintape_taken) % wt.capacity), gs[g]);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": window tape: " + hipGetErrorString(e));
+                        device_failed = true;
+                    }
+                }
                 first += count;
             }
             if (rc != SPD_OK) break;
@@ -1763,6 +1851,16 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                     int32_t *row = ac.rows.data() + 7 * static_cast<size_t>((ac.taken - 1) % ac.capacity);
                     row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
                     row[6] = acc_step;
+                }
+            }
+            win_open = win_after;  // (the window tape's open window with this step's sample, or the next one after a close)
+            if (win.close) ++wintape_taken;
+            if (wt.on && round == 0) {
+                wt.window_start = win_open.start;
+                wt.samples = win_open.samples;
+                if (win.close) {
+                    wt.taken = wintape0 + wintape_taken;
+                    std::memcpy(wt.rows.data() + 8 * static_cast<size_t>((wt.taken - 1) % wt.capacity), win_row, sizeof(win_row));
                 }
             }
         }
@@ -1851,6 +1949,12 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
             m->acctape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
                                      " of a checked call";
         }
+    for (int i = 0; i < M && m->wintape.on && m->wintape.valid; ++i)
+        if (first_failed_step[i] >= 0) {  // (... and for the window tape)
+            m->wintape.valid = false;
+            m->wintape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
+                                     " of a checked call";
+        }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)
             std::memcpy(accepted + 7 * static_cast<size_t>(i),
@@ -1921,6 +2025,7 @@ int spd_model_mark_initialized(spd_model_handle m, int current_step, int year, i
     m->cal.set(year, month, day, hour, minute);
     m->current_step = current_step;
     m->acctape.window_start = -1;  // (the accumulation tape's open window does not continue across a step counter set by hand)
+    m->wintape.window_start = -1;  // (... nor does the window tape's)
     m->surf_cache_valid = false;
     m->ablco2_ref = m->air_absortivity_co2;  // set_forcing(imode = 0), forcing.f90:40
     m->initialized = true;
@@ -1962,6 +2067,7 @@ int spd_model_set_control(spd_model_handle m, const spd_model_control *in) {
     m->surf_cache_valid = false;
     m->current_step = in->current_step;
     m->acctape.window_start = -1;
+    m->wintape.window_start = -1;
     m->land_coupling_flag = in->land_coupling_flag ? 1 : 0;
     m->sst_anomaly_flag = in->sst_anomaly_coupling_flag ? 1 : 0;
     m->increase_co2 = in->increase_co2 ? 1 : 0;
@@ -3263,6 +3369,306 @@ int spd_model_acctape_read(spd_model_handle m, const char *name, int op, int fir
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the window tape: window sums, means, extremes and threshold counts of the state's fields (spd_model_wintape_*; kernel: wintape.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// names: the catalogue's fourteen, then the two wind speeds of this recorder only (u and v: the catalogue ids they are formed from)
+constexpr int kWinWspdGrid = kStatsCatalogueSize, kWinWspdPlev = kStatsCatalogueSize + 1, kWinNNames = kStatsCatalogueSize + 2;
+constexpr int kWinNOps = 6;
+int win_name_id(const char *name) {
+    if (!name) return -1;
+    if (std::strcmp(name, "wspd_grid") == 0) return kWinWspdGrid;
+    if (std::strcmp(name, "wspd_plev") == 0) return kWinWspdPlev;
+    return stats_id(name);
+}
+bool win_needs_levels(int id) { return id == kWinWspdPlev || (id >= kPlevFirst && id < kStatsCatalogueSize); }
+int win_u_id(int id) { return id == kWinWspdGrid ? 0 : kPlevFirst + PLEV_U; }
+const char *const kWinOff = "no window tape configured (spd_model_wintape_configure)";
+const char *const kWinOpNames[kWinNOps] = {"SPD_WIN_SUM", "SPD_WIN_MEAN", "SPD_WIN_MIN", "SPD_WIN_MAX", "SPD_WIN_COUNT_ABOVE", "SPD_WIN_COUNT_BELOW"};
+
+// window kind, `every` and sample_every, as _configure and spd_wintape_plan refuse them
+int win_schedule_check(const char *who, int window, int every, int sample_every) {
+    if (window != SPD_WINDOW_STEPS && window != SPD_WINDOW_DAY && window != SPD_WINDOW_MONTH)
+        return m_fail(SPD_E_ARG, std::string(who) + ": unknown window kind " + std::to_string(window) +
+                                     " (SPD_WINDOW_STEPS, SPD_WINDOW_DAY or SPD_WINDOW_MONTH)");
+    if (window == SPD_WINDOW_STEPS && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1 for SPD_WINDOW_STEPS");
+    if (window != SPD_WINDOW_STEPS && every != 0)
+        return m_fail(SPD_E_ARG, std::string(who) + ": every must be 0 for SPD_WINDOW_DAY and SPD_WINDOW_MONTH");
+    if (sample_every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": sample_every must be at least 1");
+    return SPD_OK;
+}
+}  // namespace
+
+int spd_wintape_plan(int year, int month, int day, int hour, int minute, int step0, int nsteps, int window, int every, int sample_every,
+                     int32_t *rows, int max_rows) {
+    const char *who = "spd_wintape_plan";
+    if (month < 1 || month > 12 || day < 1 || day > 31 || hour < 0 || hour > 23 || minute < 0 || minute > 59)
+        return m_fail(SPD_E_ARG, std::string(who) + ": bad date");
+    if (step0 < 0 || nsteps < 0) return m_fail(SPD_E_ARG, std::string(who) + ": step0 and nsteps must not be negative");
+    if (static_cast<long long>(step0) + nsteps > 2147483647LL) return m_fail(SPD_E_ARG, std::string(who) + ": step0 + nsteps does not fit an int");
+    if (int rc = win_schedule_check(who, window, every, sample_every)) return rc;
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, std::string(who) + ": bad destination");
+    Calendar cal;
+    cal.set(year, month, day, hour, minute);
+    const WinSchedule schedule{window, every, sample_every};
+    WinOpen open{step0, 0};
+    int closed = 0;
+    for (int it = 0; it < nsteps; ++it) {
+        cal.advance();
+        int32_t row[8];
+        if (wintape_advance(schedule, open, step0 + it + 1, cal, row).close) {
+            if (closed < max_rows) std::memcpy(rows + 8 * static_cast<size_t>(closed), row, sizeof(row));
+            ++closed;
+        }
+    }
+    return closed;
+}
+
+// the launches of the members [first, first + count) for a step that samples (k >= 1: the front end into the recorder's own slab,
+// then the kernel) or only closes (k = 0: the kernel alone)
+static hipError_t wintape_step(spd_model *m, int first, int count, int k, int close, int n, int slot, hipStream_t s) {
+    const spd_model::WinTape &wt = m->wintape;
+    hipError_t e = hipSuccess;
+    if (k > 0) e = sample_front(m, wt, first, count, s);
+    if (e == hipSuccess)
+        e = run_wintape_step(wt.planes, wt.nplanes, wt.slab, wt.slab_fields, first, count, k, close, n, slot, m->stored32 ? 1 : 0,
+                             wt.dtype == SPD_TAPE_F64 ? 1 : 0, s);
+    return e;
+}
+
+int spd_model_wintape_configure(spd_model_handle m, const char *const *names, const int *ops, const double *thresholds, int n_entries,
+                                int window, int every, int sample_every, int capacity, int dtype) {
+    const char *who = "spd_model_wintape_configure";
+    // (the arguments first, in the header's order: nothing below needs the device)
+    if (n_entries < 0 || (n_entries > 0 && (!names || !ops))) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
+    std::vector<spd_model::WinTape::Entry> entries;
+    for (int k = 0; k < n_entries; ++k) {
+        const int id = win_name_id(names[k]);
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
+                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
+                                         "q_plev, z_plev, mslp, wspd_grid, wspd_plev)");
+        entries.push_back({id, ops[k], 0, 0.0, 0});
+    }
+    for (int k = 0; k < n_entries; ++k)
+        if (ops[k] < 0 || ops[k] >= kWinNOps)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown op " + std::to_string(ops[k]) + " for '" + names[k] +
+                                         "' (SPD_WIN_SUM, SPD_WIN_MEAN, SPD_WIN_MIN, SPD_WIN_MAX, SPD_WIN_COUNT_ABOVE or SPD_WIN_COUNT_BELOW)");
+    for (int k = 0; k < n_entries; ++k)
+        if (ops[k] == SPD_WIN_COUNT_ABOVE || ops[k] == SPD_WIN_COUNT_BELOW) {
+            if (!thresholds || !std::isfinite(thresholds[k]))
+                return m_fail(SPD_E_ARG, std::string(who) + ": " + kWinOpNames[ops[k]] + " of '" + names[k] + "' needs a finite threshold");
+            entries[k].threshold = thresholds[k];
+        }
+    for (int k = 0; k < n_entries; ++k)
+        for (int j = 0; j < k; ++j)
+            if (entries[j].name == entries[k].name && entries[j].op == entries[k].op)
+                return m_fail(SPD_E_ARG, std::string(who) + ": entry ('" + names[k] + "', " + std::to_string(ops[k]) + ") named twice");
+    if (n_entries > 0) {
+        if (int rc = win_schedule_check(who, window, every, sample_every)) return rc;
+        if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+        if (dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64) return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
+    }
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    for (int k = 0; k < n_entries; ++k)
+        if (win_needs_levels(entries[k].name) && m->plev.n == 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still accumulate into the allocation this one replaces)
+    spd_model::WinTape &wt = m->wintape;
+    void *old = wt.alloc;
+    wt = spd_model::WinTape{};  // (off before anything below can fail)
+    if (old) M_HIP(hipFree(old));
+    if (n_entries == 0) return SPD_OK;  // off
+    spd_model::WinTape next;
+    next.window = window;
+    next.every = every;
+    next.sample_every = sample_every;
+    next.capacity = capacity;
+    next.dtype = dtype;
+    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
+    const size_t elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
+    // The sample plan: the catalogue names among the entries in the order they first appear, then the u and v a wind speed is
+    // formed from where no entry names them -- planes of the slab without accumulators of their own.
+    std::vector<int> ids;
+    auto want = [&](int id) {
+        if (std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
+    };
+    for (const auto &e : entries)
+        if (e.name < kStatsCatalogueSize) want(e.name);
+    for (const auto &e : entries)
+        if (e.name >= kStatsCatalogueSize) want(win_u_id(e.name)), want(win_u_id(e.name) + 1);
+    SamplePlan plan;
+    plan_sample(m, ids, next, plan);
+    auto plan_var = [&](int id) -> const SamplePlan::Var & {
+        return *std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
+    };
+    // what each name needs: [0] a running sum (sum or mean), [1] a minimum, [2] a maximum, [3] / [4] a count above / below
+    bool need[kWinNNames][5] = {};
+    int levels[kWinNNames] = {};
+    size_t ring_planes = 0, acc_planes = 0, desc_planes = 0;
+    for (auto &e : entries) {
+        e.levels = plan_var(e.name < kStatsCatalogueSize ? e.name : win_u_id(e.name)).levels;
+        levels[e.name] = e.levels;
+        e.offset = slots * M * ring_planes * NG;
+        ring_planes += static_cast<size_t>(e.levels);
+        need[e.name][e.op <= SPD_WIN_MEAN ? 0 : e.op - 1] = true;
+    }
+    for (int v = 0; v < kWinNNames; ++v) {
+        int kinds = 0;
+        for (int a = 0; a < 5; ++a) kinds += need[v][a] ? 1 : 0;
+        acc_planes += static_cast<size_t>(kinds) * levels[v];
+        if (kinds) desc_planes += static_cast<size_t>(levels[v]);
+    }
+    // one allocation: ring | accumulators | slab | tables[2] | plane descriptors
+    const size_t per_slot = M * ring_planes * NG * elem;
+    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 2) / per_slot)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the window tape's size does not fit size_t");
+    const size_t ring = sample_up(slots * per_slot), accs = sample_up(M * acc_planes * NG * sizeof(double));
+    const size_t desc = sample_up(desc_planes * sizeof(WinTapePlane));
+    const size_t total = ring + accs + plan.slab_bytes + 2 * plan.table_bytes + desc;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the window tape is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the window tape (" + std::to_string(total) +
+                                        " bytes asked for: " + std::to_string(capacity) + " windows of " + std::to_string(per_slot) +
+                                        " bytes and " + std::to_string(accs) + " bytes of accumulators); the window tape is off");
+    }
+    char *at = static_cast<char *>(p);
+    next.alloc = p;
+    next.data = at, at += ring;
+    double *acc_at = reinterpret_cast<double *>(at);
+    at += accs;
+    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
+    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
+    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
+    next.planes = reinterpret_cast<WinTapePlane *>(at);
+    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
+    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<WinTapePlane> host_planes;
+    for (int v = 0; v < kWinNNames; ++v) {
+        bool any = false;
+        for (int a = 0; a < 5; ++a) any = any || need[v][a];
+        if (!any) continue;
+        const bool wspd = v >= kStatsCatalogueSize;
+        const size_t nlev = static_cast<size_t>(levels[v]), per = nlev * NG;
+        double *acc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        for (int a = 0; a < 5; ++a)
+            if (need[v][a]) acc[a] = acc_at, acc_at += M * per;
+        const size_t plane_a = plan_var(wspd ? win_u_id(v) : v).first_plane;
+        const size_t plane_b = wspd ? plan_var(win_u_id(v) + 1).first_plane : 0;
+        for (size_t k = 0; k < nlev; ++k) {
+            WinTapePlane d{};
+            d.slab_a = slab_plane[plane_a + k];
+            d.slab_b = wspd ? slab_plane[plane_b + k] : -1;
+            d.src = v == 6 ? static_cast<const void *>(m->pa.precnv) : v == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
+            d.narrow = (v == 6 || v == 7) && m->reg[kStatsCatalogue[v].name].f32 ? 1 : 0;  // (what physics_storage32 keeps as float)
+            d.unit = wspd ? 0 : kStatsCatalogue[v].unit;
+            d.sum = acc[0] ? acc[0] + k * NG : nullptr;
+            d.mn = acc[1] ? acc[1] + k * NG : nullptr;
+            d.mx = acc[2] ? acc[2] + k * NG : nullptr;
+            d.cnt[0] = acc[3] ? acc[3] + k * NG : nullptr;
+            d.cnt[1] = acc[4] ? acc[4] + k * NG : nullptr;
+            for (const auto &x : entries)
+                if (x.name == v) {
+                    d.ring[x.op] = static_cast<char *>(next.data) + (x.offset + k * NG) * elem;
+                    if (x.op >= SPD_WIN_COUNT_ABOVE) d.thr[x.op - SPD_WIN_COUNT_ABOVE] = x.threshold;
+                }
+            d.member_stride = static_cast<long>(per);
+            d.slot_stride = static_cast<long>(M * per);
+            host_planes.push_back(d);
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(WinTapePlane), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    next.nplanes = static_cast<int>(host_planes.size());
+    next.entries = std::move(entries);
+    next.rows.assign(slots * 8, 0);
+    next.window_start = -1;  // (the first window starts at the model's current step: step_impl reads the counter when it next runs)
+    next.on = true;
+    wt = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_wintape_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: null model");
+    if (!m->wintape.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_reset: ") + kWinOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: a checked multi-step call is in flight; end it first");
+    m->wintape.taken = 0;          // (the next window goes into slot 0 ...
+    m->wintape.window_start = -1;  //  ... and starts at the next step; its first sample overwrites the accumulators: no device work)
+    m->wintape.samples = 0;
+    m->wintape.valid = true;
+    m->wintape.invalid_why.clear();
+    return SPD_OK;
+}
+
+int spd_model_wintape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *window, int *every, int *sample_every,
+                           int *dtype) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_info: null model");
+    const spd_model::WinTape &wt = m->wintape;
+    if (!wt.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_info: ") + kWinOff);
+    if (taken) *taken = wt.taken;
+    if (held) *held = static_cast<int>(std::min<long long>(wt.taken, wt.capacity));
+    if (capacity) *capacity = wt.capacity;
+    if (window) *window = wt.window;
+    if (every) *every = wt.every;
+    if (sample_every) *sample_every = wt.sample_every;
+    if (dtype) *dtype = wt.dtype;
+    return SPD_OK;
+}
+
+int spd_model_wintape_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_times: null model");
+    const spd_model::WinTape &wt = m->wintape;
+    if (!wt.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_times: ") + kWinOff);
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_wintape_times: bad destination");
+    const long long held = std::min<long long>(wt.taken, wt.capacity), oldest = wt.taken - held;  // (window numbers from 0)
+    int n = 0;
+    for (; n < held && n < max_rows; ++n)
+        std::memcpy(rows + 8 * static_cast<size_t>(n), wt.rows.data() + 8 * static_cast<size_t>((oldest + n) % wt.capacity), 8 * sizeof(int32_t));
+    return n;
+}
+
+int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
+                           size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_wintape_read";
+    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::WinTape &wt = m->wintape;
+    if (!wt.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kWinOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (!wt.valid) return m_fail(SPD_E_ARG, std::string(who) + ": the window tape is invalid until spd_model_wintape_reset: " + wt.invalid_why);
+    const int id = win_name_id(name);
+    const spd_model::WinTape::Entry *v = nullptr;
+    for (const auto &x : wt.entries)
+        if (x.name == id && x.op == op) v = &x;
+    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": ('" + name + "', " + std::to_string(op) + ") is not among the configured entries");
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    const long long held = std::min<long long>(wt.taken, wt.capacity), oldest = wt.taken - held;
+    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
+        return m_fail(SPD_E_ARG, std::string(who) + ": window range out of bounds (" + std::to_string(held) + " windows held)");
+    const size_t elem = wt.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->levels) * NG;
+    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (count == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    const char *src = static_cast<const char *>(wt.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
+    const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
+                                         static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % wt.capacity), wt.capacity,
+                                         static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // pressure-level fields and mean sea-level pressure (spd_model_plev_*; kernel: plev.hip)
 // ---------------------------------------------------------------------------------------------------------------
 static int plev_id(const char *name) {
@@ -3293,6 +3699,9 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
     if (m->enstape.on && m->enstape.plev.mask)
         return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_enstape_configure)");
+    if (m->wintape.on && m->wintape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the window tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_wintape_configure)");
     spd_model::Plev &pl = m->plev;
     pl.n = n;
     for (int j = 0; j < kPlevMaxLevels; ++j) {

@@ -585,6 +585,111 @@ class EnsembleModel:
                   "spd_model_acctape_read(%s, %s)" % (name, op))
         return out
 
+    # ---- the window tape: window means, extremes and threshold counts of the state's fields (spd_model_wintape_*) ----------
+    WINTAPE_NAMES = STATS_VARIABLES + ("wspd_grid", "wspd_plev")  # (the wind speeds: sqrt(u * u + v * v), this recorder only)
+    WINTAPE_OPS = {"sum": _lib.SPD_WIN_SUM, "mean": _lib.SPD_WIN_MEAN, "min": _lib.SPD_WIN_MIN, "max": _lib.SPD_WIN_MAX,
+                   "count_above": _lib.SPD_WIN_COUNT_ABOVE, "count_below": _lib.SPD_WIN_COUNT_BELOW}
+    WINTAPE_WINDOWS = {"day": _lib.SPD_WINDOW_DAY, "month": _lib.SPD_WINDOW_MONTH}
+
+    wintape_plan = staticmethod(_lib.wintape_plan)  # (the windows ahead, from the library's own schedule: no device needed)
+
+    def _wintape_op(self, op):
+        if op not in self.WINTAPE_OPS:
+            raise ValueError("op must be one of 'sum', 'mean', 'min', 'max', 'count_above', 'count_below', got %r" % (op,))
+        return self.WINTAPE_OPS[op]
+
+    def wintape_configure(self, entries, window, capacity, sample_every=1, dtype="float32"):
+        """Accumulate the state's fields over windows, inside run() / run_checked() calls of any length.  `entries` is a list of
+        (name, op) or (name, op, threshold): name any of WINTAPE_NAMES (the tape's fourteen, the pressure-level ones after
+        plev_configure with its levels in hPa, and the wind speeds wspd_grid / wspd_plev), op "sum", "mean", "min", "max",
+        "count_above" (samples with x > threshold) or "count_below" (x < threshold); a threshold is in the unit tape() returns the
+        name in (t_grid in K, winds in m/s, ps_grid and mslp in Pa).  A sample is taken after every step that leaves current_step
+        at a multiple of `sample_every` and is what a float64 tape holds.  `window` is a number of steps (a window closes after
+        every step that leaves current_step at a multiple of it), "day" (at 00:00) or "month" (at 00:00 on day 1 of the model's
+        calendar); the ring in device memory keeps the last `capacity` windows of every member; dtype "float32" (the default) or
+        "float64".  The first window starts at the current step and may be short (wintape_counts()); a window without a sample
+        holds 0 for sums and counts and NaN otherwise.  Empties the ring; an empty list switches the recorder off and frees it.
+        Synchronises the device."""
+        key = str(dtype).replace("torch.", "")
+        if key not in self.TAPE_DTYPES:
+            raise ValueError("dtype must be 'float32' or 'float64', got %r" % (dtype,))
+        if isinstance(window, str):
+            if window not in self.WINTAPE_WINDOWS:
+                raise ValueError("window must be a number of steps, 'day' or 'month', got %r" % (window,))
+            kind, every = self.WINTAPE_WINDOWS[window], 0
+        else:
+            kind, every = _lib.SPD_WINDOW_STEPS, int(window)
+        rows = []
+        for entry in entries:
+            if len(entry) not in (2, 3):
+                raise ValueError("an entry is (name, op) or (name, op, threshold), got %r" % (entry,))
+            op = self._wintape_op(entry[1])
+            counts = op in (_lib.SPD_WIN_COUNT_ABOVE, _lib.SPD_WIN_COUNT_BELOW)
+            if counts and len(entry) != 3:
+                raise ValueError("op %r needs a threshold: (name, op, threshold)" % (entry[1],))
+            rows.append((str(entry[0]), op, float(entry[2]) if counts else 0.0))
+        names = (C.c_char_p * max(len(rows), 1))(*[n.encode() for n, _, _ in rows])
+        ops = (C.c_int * max(len(rows), 1))(*[op for _, op, _ in rows])
+        thresholds = (C.c_double * max(len(rows), 1))(*[t for _, _, t in rows])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_wintape_configure(self._m, names, ops, thresholds, len(rows), kind, every, int(sample_every),
+                                                        int(capacity), self.TAPE_DTYPES[key][0]), "spd_model_wintape_configure")
+
+    def wintape_reset(self):
+        """Empty the ring and start a new window at the current step (no device work)."""
+        check(self._lib.spd_model_wintape_reset(self._m), "spd_model_wintape_reset")
+
+    @property
+    def wintape_info(self):
+        """dict(taken, held, capacity, window, sample_every, dtype): windows closed since the last reset, windows the ring holds
+        (min(taken, capacity)), and the configuration (window: the number of steps, "day" or "month")."""
+        taken, held, capacity, kind, every, sample_every, dtype = (C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0),
+                                                                   C.c_int(0), C.c_int(0))
+        check(self._lib.spd_model_wintape_info(self._m, C.byref(taken), C.byref(held), C.byref(capacity), C.byref(kind), C.byref(every),
+                                               C.byref(sample_every), C.byref(dtype)), "spd_model_wintape_info")
+        name = [k for k, v in self.TAPE_DTYPES.items() if v[0] == dtype.value][0]
+        window = every.value if kind.value == _lib.SPD_WINDOW_STEPS else [k for k, v in self.WINTAPE_WINDOWS.items() if v == kind.value][0]
+        return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, window=window, sample_every=sample_every.value,
+                    dtype=name)
+
+    def _wintape_rows(self):
+        held = self.wintape_info["held"]
+        rows = np.zeros((max(held, 1), 8), dtype=np.int32)
+        n = self._lib.spd_model_wintape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
+        if n < 0:
+            check(n, "spd_model_wintape_times")
+        return rows[:n]
+
+    def wintape_steps(self):
+        """The model's step counter after the last step of each held window, oldest first (numpy int array)."""
+        return self._wintape_rows()[:, 0].astype(np.int64)
+
+    def wintape_times(self):
+        """The date of the state after each held window's last step, oldest first (a list of datetime)."""
+        from datetime import datetime
+        return [datetime(*(int(v) for v in row[1:6])) for row in self._wintape_rows()]
+
+    def wintape_counts(self):
+        """(samples, steps) in each held window, oldest first (two numpy int arrays)."""
+        rows = self._wintape_rows()
+        return rows[:, 6].astype(np.int64), rows[:, 7].astype(np.int64)
+
+    def wintape(self, name, op, first=0, count=None, t0=0, nt=None):
+        """Members [first, first + count) and windows [t0, t0 + nt) of the held ones (oldest first) of one entry: a tensor
+        [count][nt][levels][48][96] ([count][nt][48][96] for one-level names) on the model's device in the ring's dtype."""
+        first, count = self._range(first, count)
+        info = self.wintape_info
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        dtype = self.TAPE_DTYPES[info["dtype"]][1]
+        shape = self._stats_shape({"wspd_grid": "u_grid", "wspd_plev": "u_plev"}.get(name, name))
+        out = torch.empty((count, max(nt, 0)) + shape, dtype=dtype, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_wintape_read(self._m, name.encode(), self._wintape_op(op), first, count, t0, nt,
+                                                   C.c_void_p(out.data_ptr()), out.numel() * out.element_size(), self._stream()),
+                  "spd_model_wintape_read(%s, %s)" % (name, op))
+        return out
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

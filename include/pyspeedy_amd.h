@@ -629,6 +629,54 @@ int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int fir
                            size_t dst_bytes, void *stream);
 int spd_wintape_plan(int year, int month, int day, int hour, int minute, int step0, int nsteps, int window, int every,
                      int sample_every, int32_t *rows, int max_rows);
+/* Nudging: operator-split Newtonian relaxation of the spectral state toward target fields, on the device inside spd_model_step /
+ * spd_model_step_checked_begin calls of any length (in-loop mode) or once on the state as it stands (_apply): replay experiments,
+ * spectral nudging of the large scales, the cheapest form of data assimilation.  The only thing in the device loop that WRITES the
+ * state; off unless configured, and a model that never configures it issues the launches it always issued.
+ * Definition.  After a model step that leaves the absolute step counter at n, for every nudged variable X of vor, div, t, tr, ps,
+ * every level k, BOTH time levels, every coefficient (m, nn) with total wavenumber l = m + nn <= 31 and every member whose mask
+ * entry is 1:
+ *     T  = T0 + a * (T1 - T0)          real and imaginary part separately
+ *     X' = X + g[X][k][l] * (T - X)
+ * Every operation is an IEEE fp64 operation rounded on its own (no fused multiply-add), so that a host restatement -- numpy's
+ * x + g * ((t0 + a * (t1 - t0)) - x) on the real and imaginary parts -- gives the same bits.  Both time levels move alike, so the
+ * leapfrog's computational mode is not excited.  Coefficients with m + nn >= 32 are neither loaded nor stored.
+ * Targets are `capacity` slots of spectral fields shared by all members, complex128 in the registry's layout without the
+ * time-level axis: (31, 32, 8) in Fortran order for vor, div, t, tr and (31, 32) for ps, in the state's stored units.  The first
+ * in_use slots carry strictly ascending absolute step stamps (_set_times).  T0 and T1 are the slots whose stamps s0 < n < s1
+ * bracket n and a = (n - s0) / (s1 - s0), computed on the host in fp64 and handed to the launch by value.  Before the first stamp
+ * T is the first slot, at or after the last stamp the last slot, at a slot's own stamp that slot: T = T0 then, without the
+ * interpolation line.  Gains are gains[n_names][8][32] fp64 in [0, 1], by name in the order given, level and total wavenumber
+ * (ps reads the first of its eight rows); a plane whose 32 gains are all zero is not part of the launch, and a table that is zero
+ * everywhere launches nothing at all.
+ * In-loop mode: one launch per member group and step directly behind the group's step on its stream, in front of the range checks
+ * of a checked call and of every recorder's sample, which therefore see the nudged state -- the state a host that nudged between
+ * one-step calls would see, bit for bit, whatever the launch plan (groups, rounds, checked calls).  While in-loop nudging with a
+ * non-zero gain is configured the spectral step does not compute the next step's geopotential ahead (spd_model_get_config reports
+ * the fold as off): it would be that of the temperature before the nudge.  The quiet rim keeps working: nothing beyond m + nn = 31
+ * is touched.  spd_model_step_dynamics is never nudged.
+ *   _configure  n_names = 0 switches nudging off and frees it.  Otherwise allocates the slots (zero-filled), gain rows and the mask
+ *               in one hipMalloc of its own (synchronises the device), with no slot in use and `applied` 0; member_mask is
+ *               int32[members] of 0 / 1 or NULL for all members; in_loop = 0 keeps gains and targets for _apply only.  SPD_E_ARG,
+ *               checked in this order before a model or a device is needed: a bad list (n_names > 5 too); an unknown name; a name
+ *               twice; null gains; a gain that is not finite or outside [0, 1] (the message names variable, level and wavenumber);
+ *               capacity < 1; in_loop neither 0 nor 1; a null model; then a mask entry other than 0 / 1, or a checked call in flight.
+ *   _set_times  declares the first n <= capacity slots in use with the stamps steps[n] (host state; n = 0: none in use).
+ *   _set_target copies one slot of one configured name from host memory (bytes must be 16 * 992 * levels; synchronises the device).
+ *   _apply      the same kernel once for the members [first, first + count) on the state as it stands, with n the current step
+ *               counter, stream-ordered; drops the look-ahead geopotential as spd_model_set does (phi itself is recomputed by the
+ *               next step, not here).
+ *   _info       names configured (0: off), capacity, slots in use, the mode, and `applied`: the steps nudged so far (in-loop steps
+ *               and _apply calls that launched) since _configure; any pointer may be NULL.
+ * _apply, and spd_model_step / spd_model_step_checked_begin in the in-loop mode, fail (SPD_E_ARG) while no slot is in use.
+ * spd_model_copy_member does not carry the configuration, and the outer boundary (spd_parallel_step*) does not keep it across the
+ * models it merges and splits. */
+int spd_model_nudge_configure(spd_model_handle m, const char *const *names, int n_names, const double *gains, const int32_t *member_mask,
+                              int capacity, int in_loop);
+int spd_model_nudge_set_times(spd_model_handle m, const int32_t *steps, int n);
+int spd_model_nudge_set_target(spd_model_handle m, int slot, const char *name, const void *host, size_t bytes);
+int spd_model_nudge_apply(spd_model_handle m, int first, int count, void *stream);
+int spd_model_nudge_info(spd_model_handle m, int *n_names, int *capacity, int *in_use, int *in_loop, long long *applied);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

@@ -10,7 +10,8 @@
 !! and, without a counterpart there: time statistics on the device (spd_model_stats_*), pressure-level fields (spd_model_plev_*),
 !! time series recorded on the device (spd_model_tape_*), spectra of the spectral state (spd_model_spectra_*), the series of
 !! the ensemble mean and spread (spd_model_enstape_*), window sums, means and extremes of the physics fluxes (spd_model_acctape_*)
-!! and window means, extremes and threshold counts of the state's fields (spd_model_wintape_*, spd_wintape_plan)
+!! window means, extremes and threshold counts of the state's fields (spd_model_wintape_*, spd_wintape_plan), and nudging of the
+!! spectral state toward target fields inside the device loop (spd_model_nudge_*)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -360,6 +361,44 @@ module pyspeedy_amd_c
             import :: c_int, c_int32_t
             integer(c_int), value :: year, month, day, hour, minute, step0, nsteps, window, every, sample_every, max_rows
             integer(c_int32_t), intent(out) :: rows(8, *)
+        end function
+        ! nudging: relaxation of the spectral state toward target fields behind every step of spd_model_step (in_loop = 1) or once on
+        ! the state as it stands (_apply) (pyspeedy_amd.h: spd_model_nudge_*).  names: any of vor, div, t, tr, ps; gains(32, 8,
+        ! n_names) in [0, 1] by total wavenumber, level and name (ps reads its first row); member_mask: c_loc of an
+        ! integer(c_int32_t) array of 0 / 1 per member, or c_null_ptr for all; a target is complex(c_double_complex) (31, 32, 8),
+        ! (31, 32) for ps, passed by c_loc with its size in bytes; steps(n): strictly ascending absolute step stamps
+        integer(c_int) function spd_model_nudge_configure(model, names, n_names, gains, member_mask, capacity, in_loop) &
+                bind(C, name="spd_model_nudge_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model, member_mask
+            type(c_ptr), intent(in) :: names(*)
+            real(c_double), intent(in) :: gains(32, 8, *)
+            integer(c_int), value :: n_names, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_nudge_set_times(model, steps, n) bind(C, name="spd_model_nudge_set_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(in) :: steps(*)
+            integer(c_int), value :: n
+        end function
+        integer(c_int) function spd_model_nudge_set_target(model, slot, name, host, bytes) bind(C, name="spd_model_nudge_set_target")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, host
+            integer(c_int), value :: slot
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_size_t), value :: bytes
+        end function
+        integer(c_int) function spd_model_nudge_apply(model, first, count, stream) bind(C, name="spd_model_nudge_apply")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, stream
+            integer(c_int), value :: first, count
+        end function
+        integer(c_int) function spd_model_nudge_info(model, n_names, capacity, in_use, in_loop, applied) &
+                bind(C, name="spd_model_nudge_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_int), intent(out) :: n_names, capacity, in_use, in_loop
+            integer(c_long_long), intent(out) :: applied
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
         ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for

@@ -164,6 +164,12 @@ _SIGNATURES = {
     "spd_model_wintape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
     "spd_wintape_plan": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_nudge_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int,
+                                            C.c_int]),
+    "spd_model_nudge_set_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_nudge_set_target": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "spd_model_nudge_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "spd_model_nudge_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)]),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),
@@ -292,3 +298,35 @@ def wintape_plan(start, step0, nsteps, window, sample_every=1):
     if n < 0:
         check(n, "spd_wintape_plan")
     return rows[:n]
+
+
+def nudge_gains(tau_hours, levels=None, l_max=31, taper=0):
+    """A gain table for EnsembleModel.nudge_configure from a relaxation time scale: an array (levels, 32) of
+    g = (2400 / (3600 tau)) * w(l), the fraction of the distance to the target that one 40-minute step removes, by level and total
+    wavenumber l.  w = 1 for l <= l_max - taper, a linear ramp (l_max + 1 - l) / (taper + 1) from there to 0 at l_max + 1, and 0
+    beyond; the table ends at l = 31, the largest wavenumber that is nudged.  `tau_hours`: one value or one per level.  `levels`:
+    None for the 8 model levels, a number of rows (1 for ps), or the 0-based indices of the levels to nudge (8 rows, the others
+    zero).  Raises ValueError if a gain exceeds 1 (tau shorter than a step) or tau is not positive."""
+    import numpy as np
+    rows, chosen = 8, None
+    if levels is not None:
+        if np.ndim(levels) == 0:
+            rows = int(levels)
+        else:
+            chosen = [int(k) for k in levels]
+    tau = np.broadcast_to(np.asarray(tau_hours, dtype=np.float64), (rows,))
+    if not np.all(tau > 0):
+        raise ValueError("tau_hours must be positive")
+    taper = int(taper)
+    if taper < 0:
+        raise ValueError("taper must not be negative")
+    l = np.arange(32)
+    w = np.clip((int(l_max) + 1 - l) / (taper + 1.0), 0.0, 1.0)
+    g = (2400.0 / (3600.0 * tau))[:, None] * w[None, :]
+    if chosen is not None:
+        keep = np.zeros(rows, dtype=bool)
+        keep[chosen] = True
+        g[~keep] = 0.0
+    if np.any(g > 1.0):
+        raise ValueError("a gain exceeds 1: tau_hours must be at least one 40-minute step (2/3 h)")
+    return g

@@ -31,6 +31,7 @@
 #include "tape.hpp"
 #include "enstape.hpp"
 #include "acctape.hpp"
+#include "nudge.hpp"
 #include "wintape.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
@@ -354,6 +355,26 @@ struct spd_model {
         void *alloc = nullptr, *data = nullptr;
         WinTapePlane *planes = nullptr;
     } wintape;
+    // Nudging (spd_model_nudge_*): relaxation of the spectral state toward target fields, the one thing in the device loop that
+    // WRITES the state.  In the in-loop mode a launch follows the step_range of every member group on the group's stream, in front
+    // of the last step's range check and of every recorder (nudge.hip); spd_model_nudge_apply is the same launch once, on the state
+    // as it stands.  One allocation of its own (hipMalloc): the target slots (per name [capacity][levels][992] complex128, shared by
+    // all members, zero-filled), the gain rows and descriptors of the planes some gain of which is not zero, and the member mask.
+    // The slots in use and their absolute step stamps are host state: the bracketing slots and the interpolation weight of a
+    // step travel by value.
+    struct Nudge {
+        bool on = false, in_loop = false;
+        int capacity = 0, in_use = 0, nplanes = 0;
+        long long applied = 0;       // steps nudged so far: in-loop steps and calls of _apply that launched
+        std::vector<int> names;      // 0 vor, 1 div, 2 t, 3 tr, 4 ps, in the caller's order
+        std::vector<int> stamps;     // [in_use], strictly ascending
+        size_t offset[5] = {};       // doubles from `targets` to slot 0 of a name
+        void *alloc = nullptr;
+        double *targets = nullptr;
+        int *mask = nullptr;         // [M] on the device, or null: every member is nudged
+        NudgePlane *planes = nullptr;
+        bool loops() const { return on && in_loop && nplanes > 0; }  // a launch follows every step of spd_model_step
+    } nudge;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {
@@ -878,6 +899,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->enstape.alloc) (void)hipFree(m->enstape.alloc);
     if (m->acctape.alloc) (void)hipFree(m->acctape.alloc);
     if (m->wintape.alloc) (void)hipFree(m->wintape.alloc);
+    if (m->nudge.alloc) (void)hipFree(m->nudge.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1071,13 +1093,19 @@ struct ProfScope {
 // Which geopotential buffer the step that is about to be issued uses: the look-ahead of the previous spectral_step_kernel if
 // there is one (then no geopotential launch is needed), otherwise the current buffer, to be filled by geopotential_kernel.
 // Returns whether the stand-alone kernel has to run.  Called once per step (not per member group).
+// Whether the spectral step computes the next step's geopotential.  Not while a nudging launch follows every step: it changes the
+// temperature behind the spectral step, and the look-ahead geopotential would be that of the temperature before it.  The fold
+// comes back when in-loop nudging is switched off.
+static bool folds(const spd_model *m) { return m->fold_geo && !m->nudge.loops(); }
+
 static bool begin_step_geopotential(spd_model *m) {
-    const bool ahead = m->fold_geo && m->phi_ahead;
+    const bool fold = folds(m);
+    const bool ahead = fold && m->phi_ahead;
     if (ahead) m->phi_cur ^= 1;
     m->P.phi = m->phi_buf[m->phi_cur];
-    m->P.phi_next = m->fold_geo ? m->phi_buf[m->phi_cur ^ 1] : nullptr;
+    m->P.phi_next = fold ? m->phi_buf[m->phi_cur ^ 1] : nullptr;
     m->reg["phi"].ptr = m->P.phi;
-    m->phi_ahead = m->fold_geo;  // true once the spectral step of this step has been issued
+    m->phi_ahead = fold;  // true once the spectral step of this step has been issued
     return !ahead;
 }
 
@@ -1539,12 +1567,33 @@ static hipError_t spectra_sample(spd_model *m, int first, int count, long long n
 static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s);  // (with spd_model_enstape_configure)
 static hipError_t wintape_step(spd_model *m, int first, int count, int k, int close, int n, int slot, hipStream_t s);  // (with spd_model_wintape_configure)
 
+// Nudging: which target the state is relaxed toward when the step counter stands at n -- the slots that bracket n and the weight
+// of the second, a = (n - s0) / (s1 - s0) in fp64.  Before the first stamp the first slot, at or after the last stamp the last
+// one, at a slot's own stamp that slot: s1 == s0 then, and the kernel takes T = T0 without the interpolation line.
+struct NudgeAt {
+    int s0, s1;
+    double a;
+};
+static NudgeAt nudge_at(const std::vector<int> &stamps, int n) {
+    const int last = static_cast<int>(stamps.size()) - 1;
+    if (n <= stamps[0]) return {0, 0, 0.0};
+    if (n >= stamps[last]) return {last, last, 0.0};
+    const int hi = static_cast<int>(std::upper_bound(stamps.begin(), stamps.end(), n) - stamps.begin()), lo = hi - 1;
+    if (n == stamps[lo]) return {lo, lo, 0.0};
+    return {lo, hi, static_cast<double>(static_cast<long long>(n) - stamps[lo]) / static_cast<double>(static_cast<long long>(stamps[hi]) - stamps[lo])};
+}
+
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
     if (int rc = usable(m, who)) return rc;
     if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized (error code -1 of the reference)");
     if (!m->dyn) return m_fail(SPD_E_ARG, std::string(who) + ": call spd_model_set_time_step first");
     if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it with spd_model_step_checked_end first");
+    const spd_model::Nudge &nd = m->nudge;
+    const bool nudge = nd.loops();
+    if (nudge && nd.in_use == 0)
+        return m_fail(SPD_E_ARG, std::string(who) + ": in-loop nudging is configured but no target slot is in use (spd_model_nudge_set_times)");
+    const long long nudged0 = nd.applied;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double delt = 86400.0 / 36;
     // Members never exchange data, so the step is issued group by group on separate streams: every group runs the same
@@ -1611,7 +1660,7 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     // for the rest of the call, which is merely slower); phi is recomputed every step from t and phis, and detect saw the +0.0
     // that this t and phis give.  Nothing is carried from call to call -- a host may write the state between calls, through
     // device views as well -- and calls of one step never skip.
-    const bool rim = nsteps >= 2 && !m->fold_geo;
+    const bool rim = nsteps >= 2 && !folds(m);
     m->rim_call = rim;
     struct HostState {  // what a step changes on the host side of the model
         Calendar cal;
@@ -1758,6 +1807,15 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                         device_failed = true;
                     }
                 }
+                if (rc == SPD_OK && nudge) {  // directly behind the step, on the group's stream: every check and sample sees the nudged state
+                    const NudgeAt at = nudge_at(nd.stamps, m->current_step + 1);
+                    const hipError_t e = run_nudge(nd.planes, nd.nplanes, nd.mask, first, count, at.s0, at.s1, at.a, gs[g]);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": nudging: " + hipGetErrorString(e));
+                        device_failed = true;
+                    }
+                }
                 if (rc == SPD_OK && record && it == nsteps - 1) {  // the last step's check: nothing comes behind it to carry it
                     const hipError_t e = run_diagnostics_range(m->P, m->ctx->dev, first, count, tl_check,
                                                                m->h_steps_err + static_cast<size_t>(it) * m->M, nullptr, m->steps_ticket, gs[g]);
@@ -1826,6 +1884,7 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
             m->cal = next;
             m->surf_cache_valid = true;
             if (round == 0) note_accepted(it + 1);
+            if (round == 0 && nudge) m->nudge.applied = nudged0 + it + 1;
             if (round == 0 && sample) m->stats.samples = samples0 + taken;
             if (round == 0 && record_tape) {  // the sample's step and the date of the sampled state, kept beside its slot
                 m->tape.taken = tape0 + tape_taken;
@@ -2103,7 +2162,7 @@ int spd_model_get_config(spd_model_handle m, int32_t *cfg) {
     cfg[1] = m->diag_every_step ? 1 : 0;
     cfg[2] = m->nchunks;
     cfg[3] = m->split_dyn_physics ? 1 : 0;
-    cfg[4] = m->fold_geo ? 1 : 0;
+    cfg[4] = folds(m) ? 1 : 0;
     cfg[5] = 1;  // (the coupling always rides in spectral_step_kernel)
     cfg[6] = m->phys_fp32;
     cfg[7] = m->stored32 ? 1 : 0;
@@ -3665,6 +3724,204 @@ int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int fir
                                          static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % wt.capacity), wt.capacity,
                                          static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// nudging: relaxation of the spectral state toward target fields (spd_model_nudge_*; kernel: nudge.hip; step loop: step_impl)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kNudgeNames = 5, kNudgeGains = 32, kNudgeRows = 8;  // gains: [n_names][8][32]; ps reads row 0 of its eight
+const char *const kNudgeName[kNudgeNames] = {"vor", "div", "t", "tr", "ps"};
+const char *const kNudgeOff = "no nudging configured (spd_model_nudge_configure)";
+int nudge_name_id(const char *name) {
+    for (int v = 0; name && v < kNudgeNames; ++v)
+        if (std::strcmp(name, kNudgeName[v]) == 0) return v;
+    return -1;
+}
+int nudge_levels(int id) { return id == 4 ? 1 : 8; }
+}  // namespace
+
+int spd_model_nudge_configure(spd_model_handle m, const char *const *names, int n_names, const double *gains, const int32_t *member_mask,
+                              int capacity, int in_loop) {
+    const char *who = "spd_model_nudge_configure";
+    // (the arguments first, in the header's order: nothing below needs the device)
+    if (n_names < 0 || n_names > kNudgeNames || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of names");
+    std::vector<int> ids;
+    for (int k = 0; k < n_names; ++k) {
+        const int id = nudge_name_id(names[k]);
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") + "' (vor, div, t, tr, ps)");
+        ids.push_back(id);
+    }
+    for (int k = 0; k < n_names; ++k)
+        for (int j = 0; j < k; ++j)
+            if (ids[j] == ids[k]) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' named twice");
+    if (n_names > 0) {
+        if (!gains) return m_fail(SPD_E_ARG, std::string(who) + ": null gains");
+        for (int k = 0; k < n_names; ++k)
+            for (int lev = 0; lev < nudge_levels(ids[k]); ++lev)
+                for (int l = 0; l < kNudgeGains; ++l) {
+                    const double g = gains[(static_cast<size_t>(k) * kNudgeRows + lev) * kNudgeGains + l];
+                    if (!std::isfinite(g) || g < 0.0 || g > 1.0)
+                        return m_fail(SPD_E_ARG, std::string(who) + ": the gain of '" + names[k] + "' at level " + std::to_string(lev) +
+                                                     ", wavenumber " + std::to_string(l) + " is not a finite number in [0, 1]");
+                }
+        if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+        if (in_loop != 0 && in_loop != 1) return m_fail(SPD_E_ARG, std::string(who) + ": in_loop must be 0 or 1");
+    }
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    for (int i = 0; n_names > 0 && member_mask && i < m->M; ++i)
+        if (member_mask[i] != 0 && member_mask[i] != 1)
+            return m_fail(SPD_E_ARG, std::string(who) + ": the mask entry of member " + std::to_string(i) + " is neither 0 nor 1");
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still read the allocation this one replaces)
+    spd_model::Nudge &nd = m->nudge;
+    void *old = nd.alloc;
+    nd = spd_model::Nudge{};  // (off before anything below can fail)
+    if (old) M_HIP(hipFree(old));
+    if (n_names == 0) return SPD_OK;  // off
+    spd_model::Nudge next;
+    next.capacity = capacity;
+    next.in_loop = in_loop != 0;
+    next.names = ids;
+    // the planes some gain of which is not zero: [name in the caller's order][level]
+    struct Row {
+        int id, lev;
+        const double *gain;
+    };
+    std::vector<Row> rows;
+    size_t target_doubles = 0;
+    for (int k = 0; k < n_names; ++k) {
+        next.offset[ids[k]] = target_doubles;
+        const size_t per_slot = static_cast<size_t>(nudge_levels(ids[k])) * NSPEC * C;
+        if (static_cast<size_t>(capacity) > (static_cast<size_t>(-1) / 16) / per_slot)
+            return m_fail(SPD_E_ARG, std::string(who) + ": the target slots' size does not fit size_t");
+        target_doubles += static_cast<size_t>(capacity) * per_slot;
+        for (int lev = 0; lev < nudge_levels(ids[k]); ++lev) {
+            const double *g = gains + (static_cast<size_t>(k) * kNudgeRows + lev) * kNudgeGains;
+            if (std::any_of(g, g + kNudgeGains, [](double x) { return x != 0.0; })) rows.push_back({ids[k], lev, g});
+        }
+    }
+    // one allocation: target slots | gain rows | plane descriptors | member mask
+    const size_t targets = sample_up(target_doubles * sizeof(double)), gain_bytes = sample_up(rows.size() * kNudgeGains * sizeof(double));
+    const size_t desc = sample_up(rows.size() * sizeof(NudgePlane)), mask_bytes = member_mask ? sample_up(sizeof(int) * m->M) : 0;
+    const size_t total = targets + gain_bytes + desc + mask_bytes;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // nudging is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the target slots (" + std::to_string(total) + " bytes asked for: " +
+                                        std::to_string(capacity) + " slots); nudging is off");
+    }
+    char *at = static_cast<char *>(p);
+    next.alloc = p;
+    next.targets = reinterpret_cast<double *>(at), at += targets;
+    double *gain_dev = reinterpret_cast<double *>(at);
+    at += gain_bytes;
+    next.planes = reinterpret_cast<NudgePlane *>(at), at += desc;
+    next.mask = member_mask ? reinterpret_cast<int *>(at) : nullptr;
+    std::vector<NudgePlane> host_planes;
+    std::vector<double> host_gains;
+    double *const base[kNudgeNames] = {m->P.vor, m->P.div, m->P.t, m->P.tr, m->P.ps};
+    for (const Row &r : rows) {
+        const size_t levels = static_cast<size_t>(nudge_levels(r.id)), plane = static_cast<size_t>(r.lev) * NSPEC * C;
+        NudgePlane d{};
+        d.state = base[r.id] + plane;
+        d.target = next.targets + next.offset[r.id] + plane;
+        d.gain = gain_dev + host_gains.size();
+        d.member_stride = static_cast<long>(2 * levels * NSPEC * C);
+        d.level_stride = static_cast<long>(levels * NSPEC * C);
+        d.slot_stride = static_cast<long>(levels * NSPEC * C);
+        host_planes.push_back(d);
+        host_gains.insert(host_gains.end(), r.gain, r.gain + kNudgeGains);
+    }
+    hipError_t e = hipMemset(next.targets, 0, targets);
+    if (e == hipSuccess && !rows.empty()) e = hipMemcpy(gain_dev, host_gains.data(), host_gains.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !rows.empty()) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(NudgePlane), hipMemcpyHostToDevice);
+    if (e == hipSuccess && member_mask) e = hipMemcpy(next.mask, member_mask, sizeof(int) * m->M, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    next.nplanes = static_cast<int>(host_planes.size());
+    next.on = true;
+    nd = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_nudge_set_times(spd_model_handle m, const int32_t *steps, int n) {
+    const char *who = "spd_model_nudge_set_times";
+    if (n < 0 || (n > 0 && !steps)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of steps");
+    for (int k = 1; k < n; ++k)
+        if (steps[k] <= steps[k - 1]) return m_fail(SPD_E_ARG, std::string(who) + ": the stamps must be strictly ascending (slot " + std::to_string(k) + ")");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    spd_model::Nudge &nd = m->nudge;
+    if (!nd.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kNudgeOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (n > nd.capacity)
+        return m_fail(SPD_E_ARG, std::string(who) + ": " + std::to_string(n) + " stamps for " + std::to_string(nd.capacity) + " slots");
+    nd.stamps.assign(steps, steps + n);  // (host state only: the steps already issued carry their slots and weight by value)
+    nd.in_use = n;
+    return SPD_OK;
+}
+
+int spd_model_nudge_set_target(spd_model_handle m, int slot, const char *name, const void *host, size_t bytes) {
+    const char *who = "spd_model_nudge_set_target";
+    if (!name || !host) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    const int id = nudge_name_id(name);
+    if (id < 0) return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + name + "' (vor, div, t, tr, ps)");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::Nudge &nd = m->nudge;
+    if (!nd.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kNudgeOff);
+    if (std::find(nd.names.begin(), nd.names.end(), id) == nd.names.end())
+        return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured names");
+    if (slot < 0 || slot >= nd.capacity)
+        return m_fail(SPD_E_ARG, std::string(who) + ": slot " + std::to_string(slot) + " of " + std::to_string(nd.capacity));
+    const size_t need = static_cast<size_t>(nudge_levels(id)) * NSPEC * C * sizeof(double);
+    if (bytes != need) return m_fail(SPD_E_SIZE, std::string(who) + ": a slot of '" + name + "' needs exactly " + std::to_string(need) + " bytes");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    // a blocking copy on the null stream, which does not order against the streams the steps were issued on (as spd_model_set)
+    M_HIP(hipDeviceSynchronize());
+    M_HIP(hipMemcpy(nd.targets + nd.offset[id] + static_cast<size_t>(slot) * (need / sizeof(double)), host, need, hipMemcpyHostToDevice));
+    return SPD_OK;
+}
+
+int spd_model_nudge_apply(spd_model_handle m, int first, int count, void *stream) {
+    const char *who = "spd_model_nudge_apply";
+    if (int rc = member_range(m, first, count, who)) return rc;
+    spd_model::Nudge &nd = m->nudge;
+    if (!nd.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kNudgeOff);
+    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (nd.in_use == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target slot is in use (spd_model_nudge_set_times)");
+    M_HIP(hipSetDevice(m->ctx->device));
+    if (int rc = settle_deferred_check(m)) return rc;  // (a range check that was put off looks at the state as it is NOW)
+    if (nd.nplanes == 0 || count == 0) return SPD_OK;
+    m->phi_ahead = false;  // the temperature changes under the look-ahead geopotential; phi itself is the next step's to recompute
+    const NudgeAt at = nudge_at(nd.stamps, m->current_step);
+    const hipError_t e = run_nudge(nd.planes, nd.nplanes, nd.mask, first, count, at.s0, at.s1, at.a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    ++nd.applied;
+    return SPD_OK;
+}
+
+int spd_model_nudge_info(spd_model_handle m, int *n_names, int *capacity, int *in_use, int *in_loop, long long *applied) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_nudge_info: null model");
+    const spd_model::Nudge &nd = m->nudge;  // (a model without nudging: all zero)
+    if (n_names) *n_names = static_cast<int>(nd.names.size());
+    if (capacity) *capacity = nd.capacity;
+    if (in_use) *in_use = nd.in_use;
+    if (in_loop) *in_loop = nd.in_loop ? 1 : 0;
+    if (applied) *applied = nd.applied;
     return SPD_OK;
 }
 

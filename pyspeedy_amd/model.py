@@ -690,6 +690,84 @@ class EnsembleModel:
                   "spd_model_wintape_read(%s, %s)" % (name, op))
         return out
 
+    # ---- nudging: relaxation of the spectral state toward target fields (spd_model_nudge_*, include/pyspeedy_amd.h) ---------
+    NUDGE_NAMES = ("vor", "div", "t", "tr", "ps")
+
+    def nudge_configure(self, gains, members=None, capacity=2, in_loop=True):
+        """Relax the spectral state toward target fields: after every step of run() / run_checked() (`in_loop`) or only when
+        nudge_apply() is called.  `gains` maps a name of NUDGE_NAMES to an array (levels, 32) of gains in [0, 1] by level and
+        total wavenumber ((32,) or (1, 32) for ps; pyspeedy_amd.nudge_gains builds one from a time scale): X' = X + g (T - X) on
+        both time levels for m + n <= 31, every operation rounded on its own.  `members`: a mask of 0 / 1 (or bools) per member,
+        None for all.  `capacity` target slots, zero-filled and shared by all members, are allocated; nudge_targets fills and
+        stamps them.  An empty dict switches nudging off.  While in-loop nudging with a gain that is not zero is configured the
+        geopotential look-ahead of small ensembles is off (config()["fold_geo"]).  Synchronises the device."""
+        names = [str(n) for n in gains]
+        table = np.zeros((max(len(names), 1), 8, 32))
+        for k, n in enumerate(names):
+            g = np.asarray(gains[n], dtype=np.float64)
+            rows = 1 if n == "ps" else 8
+            if n == "ps" and g.shape == (32,):
+                g = g.reshape(1, 32)
+            if n in self.NUDGE_NAMES and g.shape != (rows, 32):
+                raise ValueError("gains of %s must have the shape (%d, 32), got %s" % (n, rows, g.shape))
+            table[k, :g.shape[0]] = g
+        mask = None
+        if members is not None:
+            mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
+            if mask.shape != (self.nmembers,):
+                raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_nudge_configure(self._m, arr, len(names), table.ctypes.data_as(C.POINTER(C.c_double)),
+                                                      None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      int(capacity), int(bool(in_loop))), "spd_model_nudge_configure")
+
+    def nudge_off(self):
+        """Switch nudging off and free its slots."""
+        self.nudge_configure({})
+
+    def _nudge_step(self, when):
+        """absolute step counter of a datetime, from the model's current date and step at 40 minutes per step"""
+        from datetime import datetime, timedelta
+        if not isinstance(when, datetime):
+            return int(when)
+        delta = when - datetime(*self.current_date)
+        steps, rest = divmod(delta, timedelta(minutes=40))
+        if rest:
+            raise ValueError("%s is not a whole number of 40-minute steps from the model's date" % (when,))
+        return self.current_step + int(steps)
+
+    def nudge_targets(self, times, fields):
+        """Fill the first len(times) target slots and declare them in use.  `times`: strictly ascending absolute step counters or
+        datetimes (converted with the model's current date and step, 40 minutes per step).  `fields` maps every configured name
+        to a complex array (n, 31, 32, 8) ((n, 31, 32) for ps) in the state's stored units, as get() returns a time level.
+        Between two stamps the target is interpolated linearly; before the first and after the last it is held."""
+        stamps = np.asarray([self._nudge_step(t) for t in times], dtype=np.int32)
+        for name, value in fields.items():
+            shape = (len(stamps), 31, 32) + (() if name == "ps" else (8,))
+            a = np.asarray(value, dtype=np.complex128)
+            if a.shape != shape:
+                raise ValueError("Array shape missmatch: targets of %s expect %s, got %s" % (name, shape, a.shape))
+            for slot in range(len(stamps)):
+                flat = np.ascontiguousarray(a[slot].ravel(order="F"))
+                check(self._lib.spd_model_nudge_set_target(self._m, slot, str(name).encode(), flat.ctypes.data_as(C.c_void_p),
+                                                           flat.nbytes), "spd_model_nudge_set_target(%s)" % name)
+        check(self._lib.spd_model_nudge_set_times(self._m, stamps.ctypes.data_as(C.POINTER(C.c_int32)), len(stamps)),
+              "spd_model_nudge_set_times")
+
+    def nudge_apply(self, first=0, count=None):
+        """The nudging launch once, on the state as it stands, at the current step counter, for members [first, first + count)
+        (of which the masked ones move); asynchronous on the current stream."""
+        check(self._lib.spd_model_nudge_apply(self._m, *self._range(first, count), self._stream()), "spd_model_nudge_apply")
+
+    def nudge_info(self):
+        """dict(names, capacity, in_use, in_loop, applied): the number of configured names (0: off), the slots allocated and in use,
+        the mode, and the steps nudged since nudge_configure."""
+        n, capacity, in_use, in_loop, applied = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
+        check(self._lib.spd_model_nudge_info(self._m, C.byref(n), C.byref(capacity), C.byref(in_use), C.byref(in_loop),
+                                             C.byref(applied)), "spd_model_nudge_info")
+        return dict(names=n.value, capacity=capacity.value, in_use=in_use.value, in_loop=bool(in_loop.value), applied=int(applied.value))
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

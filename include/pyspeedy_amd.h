@@ -677,6 +677,63 @@ int spd_model_nudge_set_times(spd_model_handle m, const int32_t *steps, int n);
 int spd_model_nudge_set_target(spd_model_handle m, int slot, const char *name, const void *host, size_t bytes);
 int spd_model_nudge_apply(spd_model_handle m, int first, int count, void *stream);
 int spd_model_nudge_info(spd_model_handle m, int *n_names, int *capacity, int *in_use, int *in_loop, long long *applied);
+/* Breeding: the perturbation of a bred member against its control run is rescaled to a fixed amplitude, on the device inside
+ * spd_model_step / spd_model_step_checked_begin calls of any length (in-loop mode) or once on the state as it stands (_apply): the
+ * breeding cycle of bred vectors, for ensemble initialisation and error-growth studies.  Off unless configured, and a model that
+ * never configures it issues the launches it always issued.
+ * Definition.  control[M] (int32) names each member's control run, or -1 for a member that is not bred; a control must itself have
+ * -1, control[i] != i, and the indices are in range.  For a bred member p with control c take D = X_p - X_c on time level 1 (the
+ * level the spectra read), w_m = 1 for m = 0 and 2 otherwise, and sum over the 527 coefficients (m, nn) with m + nn <= 31:
+ *     E(vor | div, k) = 1/4 sum elm2(m + nn) w_m |D|^2     the kinetic energy of the difference wind (the model's own elm2 table)
+ *     E(t | tr | ps, k) = 1/2 sum w_m |D|^2                 the area mean square
+ *     A = sqrt(sum over names and levels of weights[name][k] * E(name, k)),   s = target / A
+ * weights[5][8] >= 0 by name in the order vor, div, t, tr, ps and level (ps reads entry 0 of its row; a plane of weight zero takes
+ * no part).  sqrt and the division are the correctly rounded ones.  If A is zero or not finite, s = 1 and the member is left
+ * alone.  The order of summation is fixed by the kernels (breed.hip: a lane's four coefficients, a tree over the 256 lanes, the 33
+ * planes ascending) and depends on nothing else: A is the same bits whatever the member groups, the rounds, the call length or
+ * the set of bred members, and within 34 782 * 2^-53 of the exact sum of its terms.  The rescale moves all five variables, all
+ * levels, BOTH time levels, at the coefficients with m + nn <= 31 only:
+ *     X_p' = X_c + s * (X_p - X_c)          real and imaginary part separately
+ * every operation an IEEE fp64 operation rounded on its own (no fused multiply-add): given s, numpy's xc + s * (xp - xc) gives the
+ * same bits.  Coefficients with m + nn >= 32 are neither loaded nor stored (the quiet rim stays valid); controls, members that are
+ * not bred and every other registry variable are untouched -- the surface models' prognostic anomalies (land and sea temperatures)
+ * among them.
+ * In-loop mode: after the step that leaves the absolute step counter at n with n % every == 0 every bred member is rescaled
+ * before step n + 1 starts.  A control may lie in another member group or round than its bred member, so such a call is issued in
+ * segments that end at the rescale steps: the group streams join the caller's stream (no host synchronisation), the two breeding
+ * launches go out there, the next segment forks again.  The range check of step n and every recorder's sample at step n see the
+ * state the step left.  A multi-step call is bit for bit the host loop  step(k); _apply; step(k); ...  -- checked calls with all
+ * their rows, `accepted` and codes included.  Nudging and breeding may be on together: the nudge follows every step, the rescale
+ * comes behind it at the segment's end.  spd_model_step_dynamics is never bred.
+ * Each rescale writes one slot of a ring of `capacity` events: fp64 amplitude[M], the A before the rescale (0.0 for a member that
+ * is not bred), and factor[M], the s (1.0 for a member that is not bred); the step counter and date of an event are kept on the
+ * host (_rows: 6 int32 per event, oldest first -- step, year, month, day, hour, minute; returns the number written).
+ *   _configure  a null `control` switches breeding off and frees everything.  Otherwise one hipMalloc of its own (synchronises the
+ *               device); the ring is empty and `applied` 0.  in_loop = 0 keeps the configuration for _apply / _compute only.  A
+ *               configuration without a bred member launches nothing.  SPD_E_ARG, before anything is allocated: null weights; a
+ *               weight that is negative or not finite; all weights zero; target not a finite number > 0; every < 1; capacity < 1;
+ *               in_loop neither 0 nor 1; a null model; a checked call in flight; then, per member, a control out of range, a
+ *               member that is its own control, a control that is itself bred.
+ *   spd_breed_check  the same checks without a model, for `members` members (control may be NULL: only the rest is checked then;
+ *               with a control its checks come first); the messages are those of _configure.
+ *   _apply      rescale once on the state as it stands, stream-ordered; writes a ring slot; drops the look-ahead geopotential and
+ *               the day's interpolated climatologies as spd_model_set does, and settles a deferred range check first.
+ *   _compute    the amplitudes [M] (fp64, 0.0 for members that are not bred) of the state as it stands into device memory; writes no
+ *               state and no ring.  It uses the configuration's scratch: order it against _apply and the steps by the stream.
+ *   _read       what = 0: amplitude, 1: factor; the events [t0, t0 + nt) of the held ones, oldest first, as [nt][M] fp64.
+ *   _reset      empties the ring (no device work).
+ *   _info       bred members, every, capacity, events taken since _configure / _reset, the mode, and `applied`: the rescales
+ *               launched since _configure; any pointer may be NULL; all zero without a configuration.
+ * spd_model_copy_member does not carry the configuration, and the outer boundary (spd_parallel_step*) does not keep it. */
+int spd_breed_check(const int32_t *control, int members, const double *weights, double target, int every, int capacity, int in_loop);
+int spd_model_breed_configure(spd_model_handle m, const int32_t *control, const double *weights, double target, int every, int capacity,
+                              int in_loop);
+int spd_model_breed_apply(spd_model_handle m, void *stream);
+int spd_model_breed_compute(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_breed_read(spd_model_handle m, int what, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_breed_rows(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_breed_reset(spd_model_handle m);
+int spd_model_breed_info(spd_model_handle m, int *bred, int *every, int *capacity, long long *taken, int *in_loop, long long *applied);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

@@ -11,7 +11,8 @@
 !! time series recorded on the device (spd_model_tape_*), spectra of the spectral state (spd_model_spectra_*), the series of
 !! the ensemble mean and spread (spd_model_enstape_*), window sums, means and extremes of the physics fluxes (spd_model_acctape_*)
 !! window means, extremes and threshold counts of the state's fields (spd_model_wintape_*, spd_wintape_plan), and nudging of the
-!! spectral state toward target fields inside the device loop (spd_model_nudge_*)
+!! spectral state toward target fields inside the device loop (spd_model_nudge_*), and breeding: the rescaling of member
+!! perturbations against their control runs inside the device loop (spd_model_breed_*, spd_breed_check)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -399,6 +400,60 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model
             integer(c_int), intent(out) :: n_names, capacity, in_use, in_loop
             integer(c_long_long), intent(out) :: applied
+        end function
+        ! breeding: the perturbation of a bred member against its control rescaled to `target` after every step that leaves the step
+        ! counter at a multiple of `every` (in_loop = 1) or once on the state as it stands (_apply) (pyspeedy_amd.h:
+        ! spd_model_breed_*).  control: c_loc of an integer(c_int32_t) array of one entry per member (0-based index of the control,
+        ! -1: not bred), or c_null_ptr to switch breeding off; weights(8, 5) >= 0 by level and name (vor, div, t, tr, ps; ps reads
+        ! its first entry); _read: what = 0 amplitude, 1 factor, (members, nt) fp64 in device memory; _rows: rows(6, *)
+        integer(c_int) function spd_breed_check(control, members, weights, target, every, capacity, in_loop) &
+                bind(C, name="spd_breed_check")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: control
+            real(c_double), intent(in) :: weights(8, 5)
+            real(c_double), value :: target
+            integer(c_int), value :: members, every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_breed_configure(model, control, weights, target, every, capacity, in_loop) &
+                bind(C, name="spd_model_breed_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model, control
+            real(c_double), intent(in) :: weights(8, 5)
+            real(c_double), value :: target
+            integer(c_int), value :: every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_breed_apply(model, stream) bind(C, name="spd_model_breed_apply")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, stream
+        end function
+        integer(c_int) function spd_model_breed_compute(model, dst_device, dst_bytes, stream) bind(C, name="spd_model_breed_compute")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_breed_read(model, what, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_breed_read")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: what, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_breed_rows(model, rows, max_rows) bind(C, name="spd_model_breed_rows")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_breed_reset(model) bind(C, name="spd_model_breed_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_breed_info(model, bred, every, capacity, taken, in_loop, applied) &
+                bind(C, name="spd_model_breed_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_int), intent(out) :: bred, every, capacity, in_loop
+            integer(c_long_long), intent(out) :: taken, applied
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
         ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for

@@ -170,6 +170,14 @@ _SIGNATURES = {
     "spd_model_nudge_set_target": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_size_t]),
     "spd_model_nudge_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "spd_model_nudge_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)]),
+    "spd_breed_check": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int, C.c_int]),
+    "spd_model_breed_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int, C.c_int]),
+    "spd_model_breed_apply": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "spd_model_breed_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_breed_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_breed_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_breed_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_breed_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),
@@ -330,3 +338,41 @@ def nudge_gains(tau_hours, levels=None, l_max=31, taper=0):
     if np.any(g > 1.0):
         raise ValueError("a gain exceeds 1: tau_hours must be at least one 40-minute step (2/3 h)")
     return g
+
+
+BREED_NAMES = ("vor", "div", "t", "tr", "ps")
+# sigma thicknesses of the eight levels (half levels 0, 0.05, 0.14, 0.26, 0.42, 0.60, 0.77, 0.90, 1 as the model holds them: fp32
+# literals, differenced in fp64)
+_HALF_LEVELS = (0.000, 0.050, 0.140, 0.260, 0.420, 0.600, 0.770, 0.900, 1.000)
+
+
+def breed_weights(kind="kinetic_energy", levels=None):
+    """The weights of a breeding norm for EnsembleModel.breed_configure: a dict name -> array (8,) over vor, div, t, tr, ps (ps
+    reads entry 0).  With E the quadratic forms of the definition (the kinetic energy of the difference wind per level for vor and
+    div, the area mean square for t, tr and ps) and dhs[k] the sigma thickness of level k, A^2 = sum weights * E is
+      "kinetic_energy"  dhs[k] on vor and div: the column kinetic energy per unit mass [m^2 s^-2]
+      "total_energy"    adds (cp / Tr) dhs[k] on t and R Tr on ps (ln ps): the dry total-energy norm with the reference temperature
+                        Tr = 270 K, cp = 1004 J kg^-1 K^-1 and R = (2 / 7) cp, the model's own constants
+      "t_rms"           dhs[k] on t: the column mean square of the temperature difference [K^2]
+    `levels`: None for all eight, or the 0-based indices of the levels that take part (the others get weight zero; ps stays)."""
+    import numpy as np
+    half = np.asarray(_HALF_LEVELS, dtype=np.float32).astype(np.float64)
+    dhs = half[1:] - half[:-1]
+    if levels is not None:
+        keep = np.zeros(8, dtype=bool)
+        keep[[int(k) for k in levels]] = True
+        dhs = np.where(keep, dhs, 0.0)
+    cp, tref = 1004.0, 270.0
+    rgas = float(np.float32(2.0) / np.float32(7.0)) * cp
+    out = {n: np.zeros(8) for n in BREED_NAMES}
+    if kind == "kinetic_energy":
+        out["vor"], out["div"] = dhs.copy(), dhs.copy()
+    elif kind == "total_energy":
+        out["vor"], out["div"] = dhs.copy(), dhs.copy()
+        out["t"] = (cp / tref) * dhs
+        out["ps"][0] = rgas * tref
+    elif kind == "t_rms":
+        out["t"] = dhs.copy()
+    else:
+        raise ValueError("unknown kind of breeding weights '%s' (kinetic_energy, total_energy, t_rms)" % (kind,))
+    return out

@@ -32,6 +32,7 @@
 #include "enstape.hpp"
 #include "acctape.hpp"
 #include "nudge.hpp"
+#include "breed.hpp"
 #include "wintape.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
@@ -375,6 +376,26 @@ struct spd_model {
         NudgePlane *planes = nullptr;
         bool loops() const { return on && in_loop && nplanes > 0; }  // a launch follows every step of spd_model_step
     } nudge;
+    // Breeding (spd_model_breed_*): the perturbation of a bred member against its control is rescaled to `target` after every step
+    // that leaves the step counter at a multiple of `every` (breed.hip).  The one operation that couples members across member
+    // groups and rounds: a call with in-loop breeding is issued as segments that end at the rescale steps (step_impl), and the two
+    // launches go out on the caller's stream behind the join of the group streams.  One allocation of its own (hipMalloc): the
+    // plane descriptors with their weights, the compact list of (member, control), each member's index in that list, the partial
+    // norms [bred][33] and the ring [capacity][2][M] of amplitudes and factors.  Steps and dates of the events are host state.
+    struct Breed {
+        bool on = false, in_loop = false;
+        int every = 0, capacity = 0, nbred = 0;
+        double target = 0.0;
+        long long taken = 0;    // events written to the ring since _configure / _reset
+        long long applied = 0;  // rescales launched since _configure: in-loop ones and calls of _apply
+        std::vector<int32_t> rows;  // [capacity][6]: step counter, y, m, d, h, min of an event's state
+        void *alloc = nullptr;
+        BreedPlane *planes = nullptr;
+        BreedPair *pairs = nullptr;
+        int *slot_of = nullptr;
+        double *partial = nullptr, *ring = nullptr;
+        bool loops() const { return on && in_loop && nbred > 0; }  // spd_model_step is issued in segments
+    } breed;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {
@@ -900,6 +921,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->acctape.alloc) (void)hipFree(m->acctape.alloc);
     if (m->wintape.alloc) (void)hipFree(m->wintape.alloc);
     if (m->nudge.alloc) (void)hipFree(m->nudge.alloc);
+    if (m->breed.alloc) (void)hipFree(m->breed.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1583,7 +1605,10 @@ static NudgeAt nudge_at(const std::vector<int> &stamps, int n) {
     return {lo, hi, static_cast<double>(static_cast<long long>(n) - stamps[lo]) / static_cast<double>(static_cast<long long>(stamps[hi]) - stamps[lo])};
 }
 
-static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
+// One segment of a call: `nsteps` steps for all members, all rounds and member groups, forked from and joined into the caller's
+// stream.  A call without in-loop breeding is one segment (row0 = 0, rows = nsteps); with it, step_impl issues the segments between
+// the rescale steps, and the rows of a checked call (h_steps_err, steps_accepted) of this segment start at row0 of the call's `rows`.
+static int step_segment(spd_model *m, int nsteps, void *stream, bool record, const char *who, int row0, int rows) {
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
     if (int rc = usable(m, who)) return rc;
     if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized (error code -1 of the reference)");
@@ -1683,11 +1708,11 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
     int rc = SPD_OK;
     auto note_accepted = [&](int row) {  // (record: what the host side of the model looks like after `row` steps of the call)
         if (!record) return;
-        int32_t *a = m->steps_accepted.data() + 7 * static_cast<size_t>(row);
+        int32_t *a = m->steps_accepted.data() + 7 * static_cast<size_t>(row0 + row);
         a[0] = m->current_step; a[1] = m->cal.year; a[2] = m->cal.month; a[3] = m->cal.day; a[4] = m->cal.hour; a[5] = m->cal.minute;
         a[6] = m->cal.month_idx;
     };
-    if (record) m->steps_accepted.assign(7 * static_cast<size_t>(nsteps + 1), 0);
+    if (record && row0 == 0) m->steps_accepted.assign(7 * static_cast<size_t>(rows + 1), 0);
     note_accepted(0);
     bool launched = false, device_failed = false;  // a launch of this call went out / a device call of it failed
     const int tl_check = 1;  // the check looks at time level 2 (do_single_step checks the state the step has just produced)
@@ -1795,7 +1820,7 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                     if (rim && it == 0 && e == hipSuccess)  // arm the flags of this group's members, on its stream
                         e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_rim + first), 1, static_cast<size_t>(count), gs[g]);
                     // (the check of the step before this one, for these members: written to that step's row)
-                    const CheckArgs chk{m->P.vor, m->P.div, m->P.t, tl_check, record && it > 0 ? m->h_steps_err + static_cast<size_t>(it - 1) * m->M : nullptr,
+                    const CheckArgs chk{m->P.vor, m->P.div, m->P.t, tl_check, record && it > 0 ? m->h_steps_err + static_cast<size_t>(row0 + it - 1) * m->M : nullptr,
                                         nullptr, m->steps_ticket, first};
                     if (e == hipSuccess)
                         e = step_range(m, 2, 2, 2 * delt, sw, first, count, diag, run_geo, &cpl, gs[g],
@@ -1818,7 +1843,7 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
                 }
                 if (rc == SPD_OK && record && it == nsteps - 1) {  // the last step's check: nothing comes behind it to carry it
                     const hipError_t e = run_diagnostics_range(m->P, m->ctx->dev, first, count, tl_check,
-                                                               m->h_steps_err + static_cast<size_t>(it) * m->M, nullptr, m->steps_ticket, gs[g]);
+                                                               m->h_steps_err + static_cast<size_t>(row0 + it) * m->M, nullptr, m->steps_ticket, gs[g]);
                     if (e != hipSuccess) {
                         rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
                         device_failed = true;
@@ -1936,6 +1961,29 @@ static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const 
         (void)m_fail(rc, text);
     }
     return rc;
+}
+
+static int breed_rescale(spd_model *m, hipStream_t s, const char *who);  // (with spd_model_breed_configure)
+
+// A call of spd_model_step / spd_model_step_checked_begin.  Without in-loop breeding: one segment, the launches it always issued.
+// With it, the control of a bred member may lie in another member group or another round, so the call is cut at the steps that
+// leave the step counter at a multiple of `every`: all rounds and groups finish a segment and join the caller's stream (no host
+// synchronisation), the two breeding launches go out there for all bred members, and the next segment forks again.  Every
+// segment does its own bookkeeping exactly as a call of its own would -- recorder counters, open windows, nudge.applied -- so the
+// call is, bit for bit, the host loop  run(k); breed_apply(); run(k); ...  The last step of a segment carries its own range check
+// in front of the join: the check and every recorder's sample of a rescale step see the state the step left.
+static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
+    if (!m || !m->breed.loops() || nsteps < 1) return step_segment(m, nsteps, stream, record, who, 0, nsteps);
+    const int every = m->breed.every;
+    for (int done = 0; done < nsteps;) {
+        const int phase = ((m->current_step % every) + every) % every;
+        const int len = std::min(every - phase, nsteps - done);
+        if (int rc = step_segment(m, len, stream, record, who, done, nsteps)) return rc;
+        done += len;
+        if (m->current_step % every == 0)
+            if (int rc = breed_rescale(m, static_cast<hipStream_t>(stream), who)) return rc;
+    }
+    return SPD_OK;
 }
 
 int spd_model_step(spd_model_handle m, int nsteps, void *stream) { return step_impl(m, nsteps, stream, false, "spd_model_step"); }
@@ -3922,6 +3970,248 @@ int spd_model_nudge_info(spd_model_handle m, int *n_names, int *capacity, int *i
     if (in_use) *in_use = nd.in_use;
     if (in_loop) *in_loop = nd.in_loop ? 1 : 0;
     if (applied) *applied = nd.applied;
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// breeding: the perturbation of a bred member against its control rescaled to a fixed amplitude (spd_model_breed_*; kernels:
+// breed.hip; segments of a call: step_impl)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kBreedNames = 5, kBreedRows = 8;  // weights: [5][8] for vor, div, t, tr, ps; ps reads entry 0 of its row
+const char *const kBreedName[kBreedNames] = {"vor", "div", "t", "tr", "ps"};
+const char *const kBreedOff = "no breeding configured (spd_model_breed_configure)";
+int breed_levels(int id) { return id == 4 ? 1 : 8; }
+}  // namespace
+
+int spd_breed_check(const int32_t *control, int members, const double *weights, double target, int every, int capacity, int in_loop) {
+    const char *who = "spd_model_breed_configure";
+    for (int i = 0; control && i < members; ++i) {
+        const int c = control[i];
+        if (c == -1) continue;
+        if (c < -1 || c >= members)
+            return m_fail(SPD_E_ARG, std::string(who) + ": the control of member " + std::to_string(i) + " (" + std::to_string(c) + ") is out of range (-1 ... " +
+                                         std::to_string(members - 1) + ")");
+        if (c == i) return m_fail(SPD_E_ARG, std::string(who) + ": member " + std::to_string(i) + " is its own control");
+        if (control[c] != -1)
+            return m_fail(SPD_E_ARG, std::string(who) + ": the control of member " + std::to_string(i) + " (" + std::to_string(c) +
+                                         ") is itself bred: a control must have -1 (no chains)");
+    }
+    if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
+    bool some = false;
+    for (int v = 0; v < kBreedNames; ++v)
+        for (int k = 0; k < breed_levels(v); ++k) {
+            const double w = weights[v * kBreedRows + k];
+            if (!std::isfinite(w) || w < 0.0)
+                return m_fail(SPD_E_ARG, std::string(who) + ": the weight of '" + kBreedName[v] + "' at level " + std::to_string(k) +
+                                             " is not a finite number >= 0");
+            some = some || w > 0.0;
+        }
+    if (!some) return m_fail(SPD_E_ARG, std::string(who) + ": all weights are zero");
+    if (!std::isfinite(target) || !(target > 0.0)) return m_fail(SPD_E_ARG, std::string(who) + ": target must be a finite number > 0");
+    if (every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+    if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+    if (in_loop != 0 && in_loop != 1) return m_fail(SPD_E_ARG, std::string(who) + ": in_loop must be 0 or 1");
+    return SPD_OK;
+}
+
+int spd_model_breed_configure(spd_model_handle m, const int32_t *control, const double *weights, double target, int every, int capacity,
+                              int in_loop) {
+    const char *who = "spd_model_breed_configure";
+    // (the arguments first: what does not need the member count, then the model, then the controls)
+    if (control)
+        if (int rc = spd_breed_check(nullptr, 0, weights, target, every, capacity, in_loop)) return rc;
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (control)
+        if (int rc = spd_breed_check(control, m->M, weights, target, every, capacity, in_loop)) return rc;
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (launches in flight may still use the allocation this one replaces)
+    spd_model::Breed &br = m->breed;
+    void *old = br.alloc;
+    br = spd_model::Breed{};  // (off before anything below can fail)
+    if (old) M_HIP(hipFree(old));
+    if (!control) return SPD_OK;  // off
+    spd_model::Breed next;
+    next.in_loop = in_loop != 0;
+    next.every = every;
+    next.capacity = capacity;
+    next.target = target;
+    const size_t M = static_cast<size_t>(m->M);
+    std::vector<BreedPair> pairs;
+    std::vector<int> slot_of(M, -1);
+    for (int i = 0; i < m->M; ++i)
+        if (control[i] >= 0) {
+            slot_of[i] = static_cast<int>(pairs.size());
+            pairs.push_back({i, control[i]});
+        }
+    next.nbred = static_cast<int>(pairs.size());
+    if (static_cast<size_t>(capacity) > (static_cast<size_t>(-1) / 64) / M)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the ring's size does not fit size_t");
+    std::vector<BreedPlane> planes;
+    double *const base[kBreedNames] = {m->P.vor, m->P.div, m->P.t, m->P.tr, m->P.ps};
+    for (int v = 0; v < kBreedNames; ++v)
+        for (int k = 0; k < breed_levels(v); ++k) {
+            const size_t levels = static_cast<size_t>(breed_levels(v));
+            BreedPlane d{};
+            d.state = base[v] + static_cast<size_t>(k) * NSPEC * C;
+            d.member_stride = static_cast<long>(2 * levels * NSPEC * C);
+            d.level_stride = static_cast<long>(levels * NSPEC * C);
+            d.weight = weights[v * kBreedRows + k];
+            d.kinetic = v < 2 ? 1 : 0;
+            planes.push_back(d);
+        }
+    // one allocation: plane descriptors | pairs | each member's index among the pairs | partial norms | ring
+    const size_t plane_bytes = sample_up(planes.size() * sizeof(BreedPlane)), pair_bytes = sample_up(std::max<size_t>(pairs.size(), 1) * sizeof(BreedPair));
+    const size_t slot_bytes = sample_up(M * sizeof(int)), partial_bytes = sample_up(std::max<size_t>(pairs.size(), 1) * kBreedPlanes * sizeof(double));
+    const size_t ring_doubles = static_cast<size_t>(capacity) * 2 * M, ring_bytes = sample_up(ring_doubles * sizeof(double));
+    const size_t total = plane_bytes + pair_bytes + slot_bytes + partial_bytes + ring_bytes;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // breeding is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the ring (" + std::to_string(total) + " bytes asked for: " +
+                                        std::to_string(capacity) + " events); breeding is off");
+    }
+    char *at = static_cast<char *>(p);
+    next.alloc = p;
+    next.planes = reinterpret_cast<BreedPlane *>(at), at += plane_bytes;
+    next.pairs = reinterpret_cast<BreedPair *>(at), at += pair_bytes;
+    next.slot_of = reinterpret_cast<int *>(at), at += slot_bytes;
+    next.partial = reinterpret_cast<double *>(at), at += partial_bytes;
+    next.ring = reinterpret_cast<double *>(at);
+    std::vector<double> ring(ring_doubles);  // what a member that is not bred shows: amplitude 0.0, factor 1.0
+    for (size_t slot = 0; slot < static_cast<size_t>(capacity); ++slot) {
+        std::fill(ring.begin() + slot * 2 * M, ring.begin() + slot * 2 * M + M, 0.0);
+        std::fill(ring.begin() + slot * 2 * M + M, ring.begin() + (slot + 1) * 2 * M, 1.0);
+    }
+    hipError_t e = hipMemcpy(next.planes, planes.data(), planes.size() * sizeof(BreedPlane), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !pairs.empty()) e = hipMemcpy(next.pairs, pairs.data(), pairs.size() * sizeof(BreedPair), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.slot_of, slot_of.data(), M * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(next.partial, 0, partial_bytes);
+    if (e == hipSuccess) e = hipMemcpy(next.ring, ring.data(), ring_doubles * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    next.rows.assign(static_cast<size_t>(capacity) * 6, 0);
+    next.on = true;
+    br = std::move(next);
+    return SPD_OK;
+}
+
+// The rescale of all bred members on the state as it stands, on stream s: the norm launch, the rescale launch behind it, one slot
+// of the ring.  What the model derived from the state is dropped as spd_model_set drops it (the look-ahead geopotential, the day's
+// interpolated climatologies); a range check that was put off looks at the state as it is now and goes out first.
+static int breed_rescale(spd_model *m, hipStream_t s, const char *who) {
+    spd_model::Breed &br = m->breed;
+    if (br.nbred == 0) return SPD_OK;
+    if (int rc = settle_deferred_check(m)) return rc;
+    m->surf_cache_valid = m->phi_ahead = false;
+    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>(br.taken % br.capacity);
+    double *amplitude = br.ring + slot * 2 * M;
+    hipError_t e = run_breed_norm(br.planes, br.pairs, br.nbred, m->ctx->dev.elm2, br.partial, s);
+    if (e == hipSuccess) e = run_breed_rescale(br.planes, br.pairs, br.nbred, br.partial, br.target, amplitude, amplitude + M, s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": breeding: " + hipGetErrorString(e));
+    }
+    int32_t *row = br.rows.data() + 6 * slot;
+    row[0] = m->current_step; row[1] = m->cal.year; row[2] = m->cal.month; row[3] = m->cal.day; row[4] = m->cal.hour; row[5] = m->cal.minute;
+    ++br.taken;
+    ++br.applied;
+    return SPD_OK;
+}
+
+int spd_model_breed_apply(spd_model_handle m, void *stream) {
+    const char *who = "spd_model_breed_apply";
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (!m->breed.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kBreedOff);
+    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    M_HIP(hipSetDevice(m->ctx->device));
+    return breed_rescale(m, static_cast<hipStream_t>(stream), who);
+}
+
+int spd_model_breed_compute(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_breed_compute";
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::Breed &br = m->breed;
+    if (!br.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kBreedOff);
+    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    const size_t need = static_cast<size_t>(m->M) * sizeof(double);
+    if (!dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    M_HIP(hipSetDevice(m->ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = run_breed_norm(br.planes, br.pairs, br.nbred, m->ctx->dev.elm2, br.partial, s);
+    if (e == hipSuccess) e = run_breed_amplitude(br.planes, br.slot_of, m->M, br.partial, static_cast<double *>(dst_device), s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    return SPD_OK;
+}
+
+int spd_model_breed_read(spd_model_handle m, int what, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_breed_read";
+    if (what != 0 && what != 1) return m_fail(SPD_E_ARG, std::string(who) + ": what is 0 (amplitude) or 1 (factor)");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    const spd_model::Breed &br = m->breed;
+    if (!br.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kBreedOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    const long long held = std::min<long long>(br.taken, br.capacity), oldest = br.taken - held;
+    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
+        return m_fail(SPD_E_ARG, std::string(who) + ": event range out of bounds (" + std::to_string(held) + " events held)");
+    const size_t M = static_cast<size_t>(m->M), need = static_cast<size_t>(nt) * M * sizeof(double);
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    if (nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    // (the spectra's gather with one "member" whose entry is the M values of a slot: dst[t][i] = ring[slot(t)][what][i])
+    const hipError_t e = run_spectra_gather(br.ring + static_cast<size_t>(what) * M, static_cast<double *>(dst_device), m->M, static_cast<long>(2 * M), 1, nt,
+                                            static_cast<int>((oldest + t0) % br.capacity), br.capacity, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+int spd_model_breed_rows(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_rows: null model");
+    const spd_model::Breed &br = m->breed;
+    if (!br.on) return m_fail(SPD_E_ARG, std::string("spd_model_breed_rows: ") + kBreedOff);
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_breed_rows: bad destination");
+    const long long held = std::min<long long>(br.taken, br.capacity), oldest = br.taken - held;
+    int n = 0;
+    for (; n < held && n < max_rows; ++n)
+        std::memcpy(rows + 6 * static_cast<size_t>(n), br.rows.data() + 6 * static_cast<size_t>((oldest + n) % br.capacity), 6 * sizeof(int32_t));
+    return n;
+}
+
+int spd_model_breed_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_reset: null model");
+    if (!m->breed.on) return m_fail(SPD_E_ARG, std::string("spd_model_breed_reset: ") + kBreedOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_breed_reset: a checked multi-step call is in flight; end it first");
+    m->breed.taken = 0;  // (the next event goes into slot 0: no device work)
+    return SPD_OK;
+}
+
+int spd_model_breed_info(spd_model_handle m, int *bred, int *every, int *capacity, long long *taken, int *in_loop, long long *applied) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_info: null model");
+    const spd_model::Breed &br = m->breed;  // (a model without breeding: all zero)
+    if (bred) *bred = br.nbred;
+    if (every) *every = br.every;
+    if (capacity) *capacity = br.capacity;
+    if (taken) *taken = br.taken;
+    if (in_loop) *in_loop = br.in_loop ? 1 : 0;
+    if (applied) *applied = br.applied;
     return SPD_OK;
 }
 

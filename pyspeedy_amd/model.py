@@ -768,6 +768,119 @@ class EnsembleModel:
                                              C.byref(applied)), "spd_model_nudge_info")
         return dict(names=n.value, capacity=capacity.value, in_use=in_use.value, in_loop=bool(in_loop.value), applied=int(applied.value))
 
+    # ---- breeding: member perturbations rescaled against their control runs (spd_model_breed_*, include/pyspeedy_amd.h) ------
+    BREED_NAMES = ("vor", "div", "t", "tr", "ps")
+
+    def breed_configure(self, control, target, every, weights="kinetic_energy", capacity=64, in_loop=True):
+        """Breed perturbations: after every step that leaves current_step at a multiple of `every`, inside run() / run_checked()
+        calls of any length (`in_loop`) or only when breed_apply() is called, every bred member p is pulled back to the distance
+        `target` from its control c: X_p' = X_c + s (X_p - X_c), s = target / A, on both time levels of vor, div, t, tr, ps for
+        m + n <= 31, every operation rounded on its own.  `control`: one entry per member, the index of its control run or -1 for
+        a member that is not bred (a control must itself have -1).  `weights`: a kind of pyspeedy_amd.breed_weights, or a dict
+        name of BREED_NAMES -> (8,) weights >= 0 of the quadratic forms that make A^2 (names left out weigh nothing; ps reads
+        entry 0).  Every rescale writes the amplitudes before it and the factors to a ring of `capacity` events (breed()).  Land and
+        sea temperatures are not rescaled.  Synchronises the device."""
+        from ._lib import breed_weights
+        ctl = np.ascontiguousarray(np.asarray(control).astype(np.int32))
+        if ctl.shape != (self.nmembers,):
+            raise ValueError("control must have one entry per member (%d), got shape %s" % (self.nmembers, ctl.shape))
+        table = self._breed_table(breed_weights(weights) if isinstance(weights, str) else weights)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_breed_configure(self._m, ctl.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      table.ctypes.data_as(C.POINTER(C.c_double)), float(target), int(every),
+                                                      int(capacity), int(bool(in_loop))), "spd_model_breed_configure")
+
+    @classmethod
+    def _breed_table(cls, weights):
+        """dict name -> (8,) (a scalar or (1,) for ps) as the library's [5][8] table"""
+        table = np.zeros((5, 8))
+        for n, w in weights.items():
+            if n not in cls.BREED_NAMES:
+                raise ValueError("unknown variable '%s' in the breeding weights %s" % (n, cls.BREED_NAMES))
+            w = np.atleast_1d(np.asarray(w, dtype=np.float64))
+            rows = (1, 8) if n == "ps" else (8,)
+            if w.ndim != 1 or w.shape[0] not in rows:
+                raise ValueError("weights of %s must have the shape (8,), got %s" % (n, w.shape))
+            table[cls.BREED_NAMES.index(n), :w.shape[0]] = w
+        return table
+
+    def breed_off(self):
+        """Switch breeding off and free its ring."""
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_breed_configure(self._m, None, None, 0.0, 0, 0, 0), "spd_model_breed_configure")
+
+    def breed_apply(self):
+        """Rescale every bred member once, on the state as it stands; asynchronous on the current stream; writes a ring slot."""
+        check(self._lib.spd_model_breed_apply(self._m, self._stream()), "spd_model_breed_apply")
+
+    def breed_amplitude(self):
+        """The amplitude A of every member's perturbation on the state as it stands (0.0 for members that are not bred): a float64
+        tensor [members] on the model's device.  Writes neither the state nor the ring."""
+        out = torch.empty(self.nmembers, dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_breed_compute(self._m, C.c_void_p(out.data_ptr()), out.numel() * 8, self._stream()),
+                  "spd_model_breed_compute")
+        return out
+
+    def breed_info(self):
+        """dict(bred, every, capacity, taken, held, in_loop, applied): bred members (all zero: off), the configuration, events
+        since breed_configure / breed_reset and events the ring holds, the mode, and the rescales launched since breed_configure."""
+        bred, every, capacity, in_loop = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        taken, applied = C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.spd_model_breed_info(self._m, C.byref(bred), C.byref(every), C.byref(capacity), C.byref(taken), C.byref(in_loop),
+                                             C.byref(applied)), "spd_model_breed_info")
+        return dict(bred=bred.value, every=every.value, capacity=capacity.value, taken=int(taken.value),
+                    held=int(min(taken.value, capacity.value)), in_loop=bool(in_loop.value), applied=int(applied.value))
+
+    def breed_reset(self):
+        """Empty the ring of breeding events (no device work)."""
+        check(self._lib.spd_model_breed_reset(self._m), "spd_model_breed_reset")
+
+    def breed(self, t0=0, nt=None):
+        """The events [t0, t0 + nt) of the held ones, oldest first: dict(amplitude, factor) of float64 tensors [nt][members] on
+        the model's device -- the A before each rescale (0.0 for members that are not bred) and the s (1.0 for those)."""
+        t0 = int(t0)
+        nt = self.breed_info()["held"] - t0 if nt is None else int(nt)
+        out = {}
+        with torch.cuda.device(self.sp.device):
+            for what, name in enumerate(("amplitude", "factor")):
+                buf = torch.empty((max(nt, 0), self.nmembers), dtype=torch.float64, device=self.sp.device)
+                check(self._lib.spd_model_breed_read(self._m, what, t0, nt, C.c_void_p(buf.data_ptr()), buf.numel() * 8, self._stream()),
+                      "spd_model_breed_read(%s)" % name)
+                out[name] = buf
+        return out
+
+    def _breed_rows(self):
+        held = self.breed_info()["held"]
+        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
+        n = self._lib.spd_model_breed_rows(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
+        if n < 0:
+            check(n, "spd_model_breed_rows")
+        return rows[:n]
+
+    def breed_steps(self):
+        """The model's step counter at each held event, oldest first (numpy int array)."""
+        return self._breed_rows()[:, 0].astype(np.int64)
+
+    def breed_times(self):
+        """The date of each held event's state, oldest first (a list of datetime)."""
+        from datetime import datetime
+        return [datetime(*(int(v) for v in row[1:6])) for row in self._breed_rows()]
+
+    def breed_growth(self):
+        """Growth rates [1/s] of the held events: a float64 numpy array [events][members] of ln(A_k / A'_(k-1)) / dt, with
+        A'_(k-1) = s_(k-1) A_(k-1) the amplitude the event before left behind (the target, unless that member was left alone) and
+        dt the time between the two events (2400 s per step).  NaN for the first held event and for members that are not bred."""
+        got = self.breed()
+        a, s = got["amplitude"].cpu().numpy(), got["factor"].cpu().numpy()
+        steps = self.breed_steps()
+        out = np.full(a.shape, np.nan)
+        if len(steps) > 1:
+            dt = 2400.0 * np.diff(steps)[:, None]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[1:] = np.log(a[1:] / (a[:-1] * s[:-1])) / dt
+        return out
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

@@ -34,6 +34,7 @@
 #include "nudge.hpp"
 #include "breed.hpp"
 #include "wintape.hpp"
+#include "ring.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
 
@@ -248,10 +249,10 @@ struct spd_model {
             int id, levels;
             size_t offset;  // doubles from `mean` / `m2` to member 0 of the variable
         };
-        bool on = false, variance = false, valid = true;
+        bool on = false, variance = false;
         int every = 1, nplanes = 0;
         long long samples = 0;
-        std::string invalid_why;
+        Validity validity;
         std::vector<Var> vars;
         void *alloc = nullptr;
         double *mean = nullptr, *m2 = nullptr;
@@ -259,33 +260,30 @@ struct spd_model {
     } stats;
     // The tape (spd_model_tape_*): a ring of the last `capacity` samples of chosen fields, taken where the statistics take theirs
     // (its own `every`, slab and tables).  One allocation of its own (hipMalloc): the ring, per variable [slot][M][levels][4608] in
-    // `dtype`, then slab, tables and the plane descriptors of the store kernel.  Sample n (1-based since the last reset) lies in
-    // slot (n - 1) % capacity; its step and date are kept on the host in `rows` at issue time.
+    // `dtype`, then slab, tables and the plane descriptors of the store kernel.  Slots, and the step and date of each sample: `ring`
+    // (ring.hpp).
     struct Tape : SampleFront {
         struct Var {
             int id, levels;
             size_t offset;  // elements from `data` to slot 0, member 0 of the variable
         };
-        bool on = false, valid = true;
-        int every = 1, capacity = 0, dtype = 0, nplanes = 0;
-        long long taken = 0;
-        std::string invalid_why;
+        bool on = false;
+        int every = 1, dtype = 0, nplanes = 0;
+        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
+        Validity validity;
         std::vector<Var> vars;
-        std::vector<int32_t> rows;  // [capacity][6]: absolute step after the sampled step, year, month, day, hour, minute
         void *alloc = nullptr, *data = nullptr;
         TapePlane *planes = nullptr;
     } tape;
     // Spectra and global means of the spectral state (spd_model_spectra_*): a ring of the last `capacity` samples of the chosen
     // names, fp64, written by one launch per member group and sample behind the tape's (no transform, no slab: spectra.hip).  One
-    // allocation of its own (hipMalloc): per name [slot][M][per] doubles.  Sample n (1-based since the last reset) lies in slot
-    // (n - 1) % capacity; its step and date are kept on the host in `rows` at issue time.
+    // allocation of its own (hipMalloc): per name [slot][M][per] doubles.  Slots, and the step and date of each sample: `ring`.
     struct Spectra {
-        bool on = false, valid = true;
-        int every = 1, capacity = 0;
+        bool on = false;
+        int every = 1;
         unsigned mask = 0;
-        long long taken = 0;
-        std::string invalid_why;
-        std::vector<int32_t> rows;  // [capacity][6]: absolute step after the sampled step, year, month, day, hour, minute
+        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
+        Validity validity;
         void *alloc = nullptr;
         size_t offset[SPECTRA_NNAMES] = {};  // doubles from `alloc` to slot 0, member 0 of a name of the mask
     } spectra;
@@ -293,27 +291,26 @@ struct spd_model {
     // squared deviations from it (M2), per grid point, fp64, taken by the tape's rule (its own `every`, slab and tables) behind the
     // spectra's sample.  One allocation of its own (hipMalloc): mean and M2 rings, each [slot][4][planes][4608] -- one partial per
     // group stream, written only from that stream (enstape.hpp) --, then slab, tables and the plane descriptors of the fold kernel.
-    // Sample n (1-based since the last reset) lies in slot (n - 1) % capacity; its step and date (`rows`) and the members already
-    // folded into each of its partials (`counts`) are kept on the host at issue time.
+    // Slots, and the step and date of each sample: `ring`; the members already folded into each partial of a slot (`counts`) are
+    // kept on the host at issue time as well.
     struct EnsTape : SampleFront {
         struct Var {
             int id, levels;
             size_t first_plane;  // planes of the variables before this one
         };
-        bool on = false, valid = true;
-        int every = 1, capacity = 0, nplanes = 0;
-        long long taken = 0;
-        std::string invalid_why;
+        bool on = false;
+        int every = 1, nplanes = 0;
+        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
+        Validity validity;
         std::vector<Var> vars;
-        std::vector<int32_t> rows;  // [capacity][6]: absolute step after the sampled step, year, month, day, hour, minute
-        std::vector<int> counts;    // [capacity][4]: members folded into partial (slot, group)
+        std::vector<int> counts;  // [capacity][4]: members folded into partial (slot, group)
         void *alloc = nullptr;
         double *mean = nullptr, *m2 = nullptr;
         EnsTapePlane *planes = nullptr;
     } enstape;
     // The accumulation tape (spd_model_acctape_*): window sums, means, minima and maxima of the column physics' 2-D outputs.  An
-    // accumulate launch follows EVERY step while it is on (acctape.hip); a window closes by the tape's rule into ring slot
-    // (k - 1) % capacity, k the number of windows closed since the last reset.  No front end: the values are read where the column
+    // accumulate launch follows EVERY step while it is on (acctape.hip); a window closes by the tape's rule into the slot of
+    // `ring`, which counts the windows closed since the last reset.  No front end: the values are read where the column
     // kernel stores them.  One allocation of its own (hipMalloc): ring (per entry [slot][M][planes][4608], float or double), the
     // fp64 accumulators some entry needs ([M][planes][4608] each), the plane descriptors.  The step the open window started at and
     // the rows of the closed ones (step, date, number of steps) are host state.
@@ -322,20 +319,19 @@ struct spd_model {
             int name, op, planes;
             size_t offset;  // elements from `data` to slot 0, member 0 of the entry
         };
-        bool on = false, valid = true;
-        int every = 1, capacity = 0, dtype = SPD_TAPE_F32, nplanes = 0;
+        bool on = false;
+        int every = 1, dtype = SPD_TAPE_F32, nplanes = 0;
         int window_start = -1;  // absolute step counter the open window began at (-1: at the next step that runs)
-        long long taken = 0;    // windows closed since the last reset
-        std::string invalid_why;
+        SampleRing ring;        // of closed windows; rows [7]: step after the window, year, month, day, hour, minute of that state, steps in it
+        Validity validity;
         std::vector<Entry> entries;
-        std::vector<int32_t> rows;  // [capacity][7]: step after the window, year, month, day, hour, minute of that state, steps in it
         void *alloc = nullptr, *data = nullptr;
         AccTapePlane *planes = nullptr;
     } acctape;
     // The window tape (spd_model_wintape_*): window sums, means, extremes and threshold counts of the state's grid-space fields.
     // The tape's front end (its own slab and tables) and an accumulate launch follow every step that samples (the tape's rule
-    // with `sample_every`); a window closes every `every` steps, at midnight or at month ends (wintape_advance) into ring slot
-    // (k - 1) % capacity, k the number of windows closed since the last reset; a closing step that does not sample launches the
+    // with `sample_every`); a window closes every `every` steps, at midnight or at month ends (wintape_advance) into the slot of
+    // `ring`, which counts the windows closed since the last reset; a closing step that does not sample launches the
     // kernel alone.  One allocation of its own (hipMalloc): ring (per entry [slot][M][levels][4608], float or double), the fp64
     // accumulators some entry needs ([M][levels][4608] each), slab, tables, plane descriptors.  The step the open window started
     // at, its samples so far and the rows of the closed ones are host state.
@@ -345,14 +341,13 @@ struct spd_model {
             double threshold;
             size_t offset;  // elements from `data` to slot 0, member 0 of the entry
         };
-        bool on = false, valid = true;
-        int window = SPD_WINDOW_STEPS, every = 1, sample_every = 1, capacity = 0, dtype = SPD_TAPE_F32, nplanes = 0;
+        bool on = false;
+        int window = SPD_WINDOW_STEPS, every = 1, sample_every = 1, dtype = SPD_TAPE_F32, nplanes = 0;
         int window_start = -1;  // absolute step counter the open window began at (-1: at the next step that runs)
         int samples = 0;        // samples the open window holds
-        long long taken = 0;    // windows closed since the last reset
-        std::string invalid_why;
+        SampleRing ring;        // of closed windows; rows [8]: step after the window, year, month, day, hour, minute, samples, steps
+        Validity validity;
         std::vector<Entry> entries;
-        std::vector<int32_t> rows;  // [capacity][8]: step after the window, year, month, day, hour, minute, samples, steps
         void *alloc = nullptr, *data = nullptr;
         WinTapePlane *planes = nullptr;
     } wintape;
@@ -381,19 +376,18 @@ struct spd_model {
     // groups and rounds: a call with in-loop breeding is issued as segments that end at the rescale steps (step_impl), and the two
     // launches go out on the caller's stream behind the join of the group streams.  One allocation of its own (hipMalloc): the
     // plane descriptors with their weights, the compact list of (member, control), each member's index in that list, the partial
-    // norms [bred][33] and the ring [capacity][2][M] of amplitudes and factors.  Steps and dates of the events are host state.
+    // norms [bred][33] and the ring [capacity][2][M] of amplitudes and factors (`data`).  Slots, steps and dates of the events: `ring`.
     struct Breed {
         bool on = false, in_loop = false;
-        int every = 0, capacity = 0, nbred = 0;
+        int every = 0, nbred = 0;
         double target = 0.0;
-        long long taken = 0;    // events written to the ring since _configure / _reset
+        SampleRing ring;        // of events since _configure / _reset; rows [6]: step counter, y, m, d, h, min of an event's state
         long long applied = 0;  // rescales launched since _configure: in-loop ones and calls of _apply
-        std::vector<int32_t> rows;  // [capacity][6]: step counter, y, m, d, h, min of an event's state
         void *alloc = nullptr;
         BreedPlane *planes = nullptr;
         BreedPair *pairs = nullptr;
         int *slot_of = nullptr;
-        double *partial = nullptr, *ring = nullptr;
+        double *partial = nullptr, *data = nullptr;
         bool loops() const { return on && in_loop && nbred > 0; }  // spd_model_step is issued in segments
     } breed;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
@@ -428,7 +422,7 @@ WinDecision wintape_advance(const WinSchedule &s, WinOpen &w, int step_after, co
     d.close = s.window == SPD_WINDOW_STEPS ? step_after % s.every == 0 : s.window == SPD_WINDOW_DAY ? midnight : midnight && next.day == 1;
     if (d.sample) ++w.samples;
     if (d.close) {
-        row[0] = step_after; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+        stamp_row(row, step_after, next);
         row[6] = w.samples;
         row[7] = step_after - w.start;
         w.start = step_after;
@@ -665,6 +659,42 @@ static int build_tables(spd_model *m) {
     }
     return batch.upload(m);
 }
+
+// ---- the in-loop features (statistics, tapes, spectra, nudging, breeding): what every _configure does around its own work.  (Here
+// and not beside the features: a template cannot stand inside the extern "C" block below.)
+namespace {
+// A _configure call, behind its argument checks: the model is there, usable and not inside a checked call ...
+int configure_allowed(const spd_model *m, const char *who) {
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    return SPD_OK;
+}
+// ... and, behind the checks that need the model: the feature as it was configured goes.  It is OFF before anything can fail --
+// here or in the caller below -- so that no later step samples into, or reads, memory whose state is unknown.
+template <class Feature>
+int retire(spd_model *m, Feature &f) {
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipDeviceSynchronize());  // (steps in flight may still use the allocation this one replaces)
+    void *old = f.alloc;
+    f = Feature{};
+    if (old) M_HIP(hipFree(old));
+    return SPD_OK;
+}
+
+constexpr size_t kSampleAlign = 256;
+size_t sample_up(size_t b) { return (b + kSampleAlign - 1) / kSampleAlign * kSampleAlign; }
+// the parts of a feature's one allocation, one behind the other, each starting on a kSampleAlign boundary
+struct Carve {
+    char *at;
+    template <class T>
+    T *take(size_t bytes) {
+        T *part = reinterpret_cast<T *>(at);
+        at += sample_up(bytes);
+        return part;
+    }
+};
+}  // namespace
 
 extern "C" {
 
@@ -1465,20 +1495,20 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->steps_pending = 0;
     m->fail_launch_after = -1;
     m->stats.samples = 0;  // (a new run: a new averaging period)
-    m->stats.valid = true;
-    m->tape.taken = 0;  // (... and an empty tape)
-    m->tape.valid = true;
-    m->spectra.taken = 0;  // (... and an empty series of spectra)
-    m->spectra.valid = true;
-    m->enstape.taken = 0;  // (... and an empty ensemble tape)
-    m->enstape.valid = true;
-    m->acctape.taken = 0;  // (... and an accumulation tape whose first window starts at the first step)
+    m->stats.validity.clear();
+    m->tape.ring.clear();  // (... and an empty tape)
+    m->tape.validity.clear();
+    m->spectra.ring.clear();  // (... and an empty series of spectra)
+    m->spectra.validity.clear();
+    m->enstape.ring.clear();  // (... and an empty ensemble tape)
+    m->enstape.validity.clear();
+    m->acctape.ring.clear();  // (... and an accumulation tape whose first window starts at the first step)
     m->acctape.window_start = -1;
-    m->acctape.valid = true;
-    m->wintape.taken = 0;  // (... and a window tape whose first window starts at the first step)
+    m->acctape.validity.clear();
+    m->wintape.ring.clear();  // (... and a window tape whose first window starts at the first step)
     m->wintape.window_start = -1;
     m->wintape.samples = 0;
-    m->wintape.valid = true;
+    m->wintape.validity.clear();
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1709,22 +1739,28 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
     auto note_accepted = [&](int row) {  // (record: what the host side of the model looks like after `row` steps of the call)
         if (!record) return;
         int32_t *a = m->steps_accepted.data() + 7 * static_cast<size_t>(row0 + row);
-        a[0] = m->current_step; a[1] = m->cal.year; a[2] = m->cal.month; a[3] = m->cal.day; a[4] = m->cal.hour; a[5] = m->cal.minute;
+        stamp_row(a, m->current_step, m->cal);
         a[6] = m->cal.month_idx;
     };
     if (record && row0 == 0) m->steps_accepted.assign(7 * static_cast<size_t>(rows + 1), 0);
     note_accepted(0);
     bool launched = false, device_failed = false;  // a launch of this call went out / a device call of it failed
+    auto check_launch = [&](hipError_t e, const char *feature) {  // what a launch of a step returned; feature: "" or "<label>: "
+        if (e == hipSuccess) return;
+        (void)hipGetLastError();
+        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + feature + hipGetErrorString(e));
+        device_failed = true;
+    };
     const int tl_check = 1;  // the check looks at time level 2 (do_single_step checks the state the step has just produced)
     const long long samples0 = m->stats.samples;  // (statistics: every round takes the same samples)
-    const long long tape0 = m->tape.taken;        // (... and writes the same slots of the tape, for its own members)
-    const long long spectra0 = m->spectra.taken;  // (... and of the spectra)
-    const long long enstape0 = m->enstape.taken;  // (... and folds its members into the same slots of the ensemble tape)
+    const long long tape0 = m->tape.ring.taken;        // (... and writes the same slots of the tape, for its own members)
+    const long long spectra0 = m->spectra.ring.taken;  // (... and of the spectra)
+    const long long enstape0 = m->enstape.ring.taken;  // (... and folds its members into the same slots of the ensemble tape)
     // the accumulation tape: the open window's first step and the windows closed are put back for every round, whose members
     // accumulate into their own part of the accumulators and close into their own part of the same slots
     spd_model::AccTape &ac = m->acctape;
     if (ac.on && (ac.window_start < 0 || ac.window_start > m->current_step)) ac.window_start = m->current_step;
-    const long long acctape0 = ac.taken;
+    const long long acctape0 = ac.ring.taken;
     const int acc_start0 = ac.window_start;
     // the window tape: the open window (its first step, its samples so far) and the windows closed, put back for every round likewise
     spd_model::WinTape &wt = m->wintape;
@@ -1732,7 +1768,7 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
         wt.window_start = m->current_step;
         wt.samples = 0;
     }
-    const long long wintape0 = wt.taken;
+    const long long wintape0 = wt.ring.taken;
     const WinOpen win_open0{wt.window_start, wt.samples};
     const WinSchedule win_schedule{wt.window, wt.every, wt.sample_every};
     // the ensemble tape's last sample of this call: a sample whose slot a later sample of the SAME call takes again is not folded at
@@ -1772,10 +1808,10 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
             if (record_spectra) ++spectra_taken;
             const bool record_enstape = m->enstape.on && (m->current_step + 1) % m->enstape.every == 0;
             if (record_enstape) ++enstape_taken;
-            const bool fold_enstape = record_enstape && enstape0 + enstape_taken + m->enstape.capacity > enstape_last;
+            const bool fold_enstape = record_enstape && enstape0 + enstape_taken + m->enstape.ring.capacity > enstape_last;
             // (round 0 opens the sample: its slot holds no member yet, in any of its partials)
             if (fold_enstape && round == 0) {
-                int *held = m->enstape.counts.data() + kEnsTapeGroups * static_cast<size_t>((enstape0 + enstape_taken - 1) % m->enstape.capacity);
+                int *held = m->enstape.counts.data() + kEnsTapeGroups * static_cast<size_t>(m->enstape.ring.slot(enstape0 + enstape_taken));
                 std::fill(held, held + kEnsTapeGroups, 0);
             }
             // the accumulation tape reads the diagnostics-only outputs of EVERY step; this step is number acc_step of its window
@@ -1826,20 +1862,11 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
                         e = step_range(m, 2, 2, 2 * delt, sw, first, count, diag, run_geo, &cpl, gs[g],
                                        (offset && first_of_call && g == 0) ? m->ev_offset : nullptr, record && it > 0 ? &chk : nullptr,
                                        rim ? (it == 0 ? kRimDetect : kRimSkip) : kRimPlain);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(e, "");
                 }
                 if (rc == SPD_OK && nudge) {  // directly behind the step, on the group's stream: every check and sample sees the nudged state
                     const NudgeAt at = nudge_at(nd.stamps, m->current_step + 1);
-                    const hipError_t e = run_nudge(nd.planes, nd.nplanes, nd.mask, first, count, at.s0, at.s1, at.a, gs[g]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": nudging: " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(run_nudge(nd.planes, nd.nplanes, nd.mask, first, count, at.s0, at.s1, at.a, gs[g]), "nudging: ");
                 }
                 if (rc == SPD_OK && record && it == nsteps - 1) {  // the last step's check: nothing comes behind it to carry it
                     const hipError_t e = run_diagnostics_range(m->P, m->ctx->dev, first, count, tl_check,
@@ -1851,55 +1878,26 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
                     ++m->checks_alone;
                 }
                 if (rc == SPD_OK && sample) {  // behind this group's last launch of the step, on its stream
-                    const hipError_t e = stats_sample(m, first, count, samples0 + taken, gs[g]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": time statistics: " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(stats_sample(m, first, count, samples0 + taken, gs[g]), "time statistics: ");
                 }
                 if (rc == SPD_OK && record_tape) {  // behind the statistics' sample, on the same stream
-                    const hipError_t e = tape_sample(m, first, count, tape0 + tape_taken, gs[g]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": tape: " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(tape_sample(m, first, count, tape0 + tape_taken, gs[g]), "tape: ");
                 }
                 if (rc == SPD_OK && record_spectra) {  // behind the tape's sample, on the same stream
-                    const hipError_t e = spectra_sample(m, first, count, spectra0 + spectra_taken, gs[g]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": spectra: " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(spectra_sample(m, first, count, spectra0 + spectra_taken, gs[g]), "spectra: ");
                 }
                 if (rc == SPD_OK && fold_enstape) {  // behind the spectra's sample, on the same stream: partial g of the slot
-                    const hipError_t e = enstape_sample(m, first, count, enstape0 + enstape_taken, g, gs[g]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": ensemble tape: " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(enstape_sample(m, first, count, enstape0 + enstape_taken, g, gs[g]), "ensemble tape: ");
                 }
                 if (rc == SPD_OK && ac.on) {  // behind the ensemble tape's sample, on the same stream, on every step
-                    const hipError_t e = run_acctape_step(ac.planes, ac.nplanes, first, count, acc_step, acc_close ? 1 : 0,
-                                                          static_cast<int>((acctape0 + acctape_taken) % ac.capacity), m->stored32 ? 1 : 0,
-                                                          ac.dtype == SPD_TAPE_F64 ? 1 : 0, gs[g]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": accumulation tape: " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(run_acctape_step(ac.planes, ac.nplanes, first, count, acc_step, acc_close ? 1 : 0,
+                                                  ac.ring.slot(acctape0 + acctape_taken + 1), m->stored32 ? 1 : 0,
+                                                  ac.dtype == SPD_TAPE_F64 ? 1 : 0, gs[g]),
+                                 "accumulation tape: ");
                 }
                 if (rc == SPD_OK && (win.sample || win.close)) {  // behind the accumulation tape's launch, on the same stream
-                    const hipError_t e = wintape_step(m, first, count, win_k, win.close ? 1 : 0, win_n,
-                                                      static_cast<int>((wintape0 + wintape_taken) % wt.capacity), gs[g]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": window tape: " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
+                    check_launch(wintape_step(m, first, count, win_k, win.close ? 1 : 0, win_n, wt.ring.slot(wintape0 + wintape_taken + 1), gs[g]),
+                                 "window tape: ");
                 }
                 first += count;
             }
@@ -1912,29 +1910,25 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
             if (round == 0 && nudge) m->nudge.applied = nudged0 + it + 1;
             if (round == 0 && sample) m->stats.samples = samples0 + taken;
             if (round == 0 && record_tape) {  // the sample's step and the date of the sampled state, kept beside its slot
-                m->tape.taken = tape0 + tape_taken;
-                int32_t *row = m->tape.rows.data() + 6 * static_cast<size_t>((m->tape.taken - 1) % m->tape.capacity);
-                row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+                m->tape.ring.taken = tape0 + tape_taken;
+                m->tape.ring.stamp(m->tape.ring.taken, m->current_step, next);
             }
             if (round == 0 && record_spectra) {  // (the same for the spectra)
-                m->spectra.taken = spectra0 + spectra_taken;
-                int32_t *row = m->spectra.rows.data() + 6 * static_cast<size_t>((m->spectra.taken - 1) % m->spectra.capacity);
-                row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+                m->spectra.ring.taken = spectra0 + spectra_taken;
+                m->spectra.ring.stamp(m->spectra.ring.taken, m->current_step, next);
             }
             if (round == 0 && record_enstape) {  // (... and for the ensemble tape)
-                m->enstape.taken = enstape0 + enstape_taken;
-                int32_t *row = m->enstape.rows.data() + 6 * static_cast<size_t>((m->enstape.taken - 1) % m->enstape.capacity);
-                row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
+                m->enstape.ring.taken = enstape0 + enstape_taken;
+                m->enstape.ring.stamp(m->enstape.ring.taken, m->current_step, next);
             }
             if (acc_close) {  // the window is closed and the next one starts at the step counter as it stands now
                 ++acctape_taken;
                 acc_start = m->current_step;
                 if (round == 0) {
-                    ac.taken = acctape0 + acctape_taken;
+                    ac.ring.taken = acctape0 + acctape_taken;
                     ac.window_start = acc_start;
-                    int32_t *row = ac.rows.data() + 7 * static_cast<size_t>((ac.taken - 1) % ac.capacity);
-                    row[0] = m->current_step; row[1] = next.year; row[2] = next.month; row[3] = next.day; row[4] = next.hour; row[5] = next.minute;
-                    row[6] = acc_step;
+                    ac.ring.stamp(ac.ring.taken, m->current_step, next);
+                    ac.ring.row(ac.ring.taken)[6] = acc_step;
                 }
             }
             win_open = win_after;  // (the window tape's open window with this step's sample, or the next one after a close)
@@ -1943,8 +1937,8 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
                 wt.window_start = win_open.start;
                 wt.samples = win_open.samples;
                 if (win.close) {
-                    wt.taken = wintape0 + wintape_taken;
-                    std::memcpy(wt.rows.data() + 8 * static_cast<size_t>((wt.taken - 1) % wt.capacity), win_row, sizeof(win_row));
+                    wt.ring.taken = wintape0 + wintape_taken;
+                    std::memcpy(wt.ring.row(wt.ring.taken), win_row, sizeof(win_row));
                 }
             }
         }
@@ -2026,42 +2020,18 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
             if ((c >> 2) != m->steps_ticket) return m_fail(SPD_E_DEVICE, std::string(who) + ": a range check finished without publishing its code");
             if (c & 1) first_failed_step[i] = k;
         }
-    for (int i = 0; i < M && m->stats.on && m->stats.valid; ++i)
-        if (first_failed_step[i] >= 0) {  // the samples behind a failed step are taken from a state the model does not accept
-            m->stats.valid = false;
-            m->stats.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
-                                   " of a checked call";
-        }
-    for (int i = 0; i < M && m->tape.on && m->tape.valid; ++i)
-        if (first_failed_step[i] >= 0) {  // (the same for the samples on the tape)
-            m->tape.valid = false;
-            m->tape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
-                                  " of a checked call";
-        }
-    for (int i = 0; i < M && m->spectra.on && m->spectra.valid; ++i)
-        if (first_failed_step[i] >= 0) {  // (... and for the spectra)
-            m->spectra.valid = false;
-            m->spectra.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
-                                     " of a checked call";
-        }
-    for (int i = 0; i < M && m->enstape.on && m->enstape.valid; ++i)
-        if (first_failed_step[i] >= 0) {  // (... and for the ensemble tape)
-            m->enstape.valid = false;
-            m->enstape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
-                                     " of a checked call";
-        }
-    for (int i = 0; i < M && m->acctape.on && m->acctape.valid; ++i)
-        if (first_failed_step[i] >= 0) {  // (... and for the accumulation tape)
-            m->acctape.valid = false;
-            m->acctape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
-                                     " of a checked call";
-        }
-    for (int i = 0; i < M && m->wintape.on && m->wintape.valid; ++i)
-        if (first_failed_step[i] >= 0) {  // (... and for the window tape)
-            m->wintape.valid = false;
-            m->wintape.invalid_why = "member " + std::to_string(i) + " failed the range check at step " + std::to_string(first_failed_step[i]) +
-                                     " of a checked call";
-        }
+    // the samples behind a failed step are taken from a state the model does not accept: the first member that failed, by number,
+    // is the one every recorder that is on names until it is reset
+    const int32_t *const failed = std::find_if(first_failed_step, first_failed_step + M, [](int32_t k) { return k >= 0; });
+    if (failed != first_failed_step + M) {
+        const int i = static_cast<int>(failed - first_failed_step);
+        if (m->stats.on && m->stats.validity.valid) m->stats.validity.fail(i, *failed);
+        if (m->tape.on && m->tape.validity.valid) m->tape.validity.fail(i, *failed);
+        if (m->spectra.on && m->spectra.validity.valid) m->spectra.validity.fail(i, *failed);
+        if (m->enstape.on && m->enstape.validity.valid) m->enstape.validity.fail(i, *failed);
+        if (m->acctape.on && m->acctape.validity.valid) m->acctape.validity.fail(i, *failed);
+        if (m->wintape.on && m->wintape.validity.valid) m->wintape.validity.fail(i, *failed);
+    }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)
             std::memcpy(accepted + 7 * static_cast<size_t>(i),
@@ -2461,9 +2431,6 @@ static int stats_id(const char *name) {
 
 // ---- the layout of a sample's front end, shared by the statistics and the tape (spd_model::SampleFront) ----
 namespace {
-constexpr size_t kSampleAlign = 256;
-size_t sample_up(size_t b) { return (b + kSampleAlign - 1) / kSampleAlign * kSampleAlign; }
-
 // the list of names of a _configure call -> catalogue ids (the arguments first: nothing here needs the device or a model)
 int sample_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
     if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
@@ -2607,6 +2574,47 @@ hipError_t sample_front(spd_model *m, const spd_model::SampleFront &f, int first
 }
 }  // namespace
 
+
+// ---- what every _configure and _read of the in-loop features does around its own work (with configure_allowed, retire, Carve) ----
+namespace {
+// slab | tables[2] of a front end
+void carve_front(Carve &carve, const SamplePlan &plan, spd_model::SampleFront &front) {
+    front.slab = carve.take<double>(plan.slab_bytes);
+    front.table[0] = carve.take<FieldDesc>(plan.table_bytes);
+    front.table[1] = carve.take<FieldDesc>(plan.table_bytes);
+}
+// an upload into the new allocation `p` failed: the feature stays off
+int upload_failed(const char *who, hipError_t e, void *p) {
+    (void)hipGetLastError();
+    (void)hipFree(p);
+    return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+}
+
+// A _read call of a model that is there: usable, the recorder on ("no ... configured (...)"), no checked call in flight, and
+// nothing recorded behind a failed range check ("the ... invalid until spd_model_..._reset")
+int read_allowed(const spd_model *m, const char *who, bool on, const char *off, const Validity &validity, const char *invalid) {
+    if (int rc = usable(m, who)) return rc;
+    if (!on) return m_fail(SPD_E_ARG, std::string(who) + ": " + off);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (!validity.valid) return m_fail(SPD_E_ARG, std::string(who) + ": " + invalid + ": " + validity.why);
+    return SPD_OK;
+}
+// samples (windows, events) [t0, t0 + nt) of those the ring holds
+int held_range(const char *who, const SampleRing &ring, int t0, int nt, const char *unit) {
+    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > ring.held())
+        return m_fail(SPD_E_ARG, std::string(who) + ": " + unit + " range out of bounds (" + std::to_string(ring.held()) + " " + unit + "s held)");
+    return SPD_OK;
+}
+// `need` bytes into the caller's device buffer
+int destination_fits(const char *who, const void *dst_device, size_t dst_bytes, size_t need, size_t align) {
+    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (reinterpret_cast<uintptr_t>(dst_device) % align != 0)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be " + std::to_string(align) + "-byte aligned");
+    return SPD_OK;
+}
+}  // namespace
+
 // the sample of members [first, first + count): the front end, then the moments
 static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
     const spd_model::Stats &st = m->stats;
@@ -2620,7 +2628,7 @@ static hipError_t tape_sample(spd_model *m, int first, int count, long long n, h
     const spd_model::Tape &tp = m->tape;
     hipError_t e = sample_front(m, tp, first, count, s);
     if (e == hipSuccess)
-        e = run_tape_store(tp.planes, tp.nplanes, tp.slab, tp.slab_fields, first, count, static_cast<int>((n - 1) % tp.capacity),
+        e = run_tape_store(tp.planes, tp.nplanes, tp.slab, tp.slab_fields, first, count, tp.ring.slot(n),
                            m->stored32 ? 1 : 0, tp.dtype == SPD_TAPE_F64 ? 1 : 0, s);
     return e;
 }
@@ -2629,7 +2637,7 @@ static hipError_t tape_sample(spd_model *m, int first, int count, long long n, h
 // (n - 1) % capacity, behind the members the partial already holds (rounds: the same stream, one after the other)
 static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s) {
     spd_model::EnsTape &et = m->enstape;
-    const int slot = static_cast<int>((n - 1) % et.capacity);
+    const int slot = et.ring.slot(n);
     int &held = et.counts[static_cast<size_t>(slot) * kEnsTapeGroups + group];
     hipError_t e = sample_front(m, et, first, count, s);
     if (e == hipSuccess)
@@ -2645,17 +2653,12 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     std::vector<int> ids;
     if (int rc = sample_ids(who, names, n_names, ids)) return rc;
     if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (int rc = configure_allowed(m, who)) return rc;
     for (size_t k = 0; k < ids.size(); ++k)
         if (ids[k] >= kPlevFirst && m->plev.n == 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
     spd_model::Stats &st = m->stats;
-    if (st.alloc) M_HIP(hipFree(st.alloc));
-    st = spd_model::Stats{};
+    if (int rc = retire(m, st)) return rc;
     if (n_names == 0) return SPD_OK;  // off
     spd_model::Stats next;
     next.every = every;
@@ -2671,14 +2674,12 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     const size_t total = acc * (next.variance ? 2 : 1) + plan.slab_bytes + 2 * plan.table_bytes + desc;
     void *p = nullptr;
     M_HIP(hipMalloc(&p, total));
-    char *at = static_cast<char *>(p);
+    Carve carve{static_cast<char *>(p)};
     next.alloc = p;
-    next.mean = reinterpret_cast<double *>(at), at += acc;
-    if (next.variance) next.m2 = reinterpret_cast<double *>(at), at += acc;
-    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
-    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.planes = reinterpret_cast<StatsPlane *>(at);
+    next.mean = carve.take<double>(acc);
+    if (next.variance) next.m2 = carve.take<double>(acc);
+    carve_front(carve, plan, next);
+    next.planes = carve.take<StatsPlane>(desc);
     std::vector<int> slab_plane;
     hipError_t e = build_sample_front(m, plan, next, slab_plane);
     std::vector<StatsPlane> host_planes;
@@ -2694,11 +2695,7 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
             host_planes.push_back(d);
         }
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(StatsPlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return upload_failed(who, e, p);
     next.on = true;
     st = std::move(next);
     return SPD_OK;
@@ -2709,8 +2706,7 @@ int spd_model_stats_reset(spd_model_handle m) {
     if (!m->stats.on) return m_fail(SPD_E_ARG, "spd_model_stats_reset: no statistics configured (spd_model_stats_configure)");
     if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_stats_reset: a checked multi-step call is in flight; end it first");
     m->stats.samples = 0;  // (the next sample overwrites the accumulators instead of reading them: no device work)
-    m->stats.valid = true;
-    m->stats.invalid_why.clear();
+    m->stats.validity.clear();
     return SPD_OK;
 }
 
@@ -2723,12 +2719,10 @@ int spd_model_stats_samples(spd_model_handle m) {
 // what every read checks; -> the variable's entry
 static int stats_readable(spd_model *m, const char *name, const char *who, const spd_model::Stats::Var **out) {
     if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    if (int rc = usable(m, who)) return rc;
     const spd_model::Stats &st = m->stats;
-    if (!st.on) return m_fail(SPD_E_ARG, std::string(who) + ": no statistics configured (spd_model_stats_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (!st.valid)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the statistics are invalid until spd_model_stats_reset: " + st.invalid_why);
+    if (int rc = read_allowed(m, who, st.on, "no statistics configured (spd_model_stats_configure)", st.validity,
+                              "the statistics are invalid until spd_model_stats_reset"))
+        return rc;
     const int id = stats_id(name);
     for (const auto &v : st.vars)
         if (v.id == id) {
@@ -2793,21 +2787,15 @@ int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n
     if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
     if (n_names > 0 && dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64)
         return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (int rc = configure_allowed(m, who)) return rc;
     for (size_t k = 0; k < ids.size(); ++k)
         if (ids[k] >= kPlevFirst && m->plev.n == 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
     spd_model::Tape &tp = m->tape;
-    if (tp.alloc) M_HIP(hipFree(tp.alloc));
-    tp = spd_model::Tape{};
+    if (int rc = retire(m, tp)) return rc;
     if (n_names == 0) return SPD_OK;  // off
     spd_model::Tape next;
     next.every = every;
-    next.capacity = capacity;
     next.dtype = dtype;
     const size_t M = static_cast<size_t>(m->M), elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
     SamplePlan plan;
@@ -2827,13 +2815,11 @@ int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n
         return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the tape (" + std::to_string(total) + " bytes asked for: " +
                                         std::to_string(capacity) + " samples of " + std::to_string(per_slot) + " bytes); the tape is off");
     }
-    char *at = static_cast<char *>(p);
+    Carve carve{static_cast<char *>(p)};
     next.alloc = p;
-    next.data = at, at += ring;
-    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
-    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.planes = reinterpret_cast<TapePlane *>(at);
+    next.data = carve.take<char>(ring);
+    carve_front(carve, plan, next);
+    next.planes = carve.take<TapePlane>(desc);
     std::vector<int> slab_plane;
     hipError_t e = build_sample_front(m, plan, next, slab_plane);
     std::vector<TapePlane> host_planes;
@@ -2849,12 +2835,8 @@ int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n
             host_planes.push_back(d);
         }
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(TapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    next.rows.assign(slots * 6, 0);
+    if (e != hipSuccess) return upload_failed(who, e, p);
+    next.ring = SampleRing(capacity, 6);
     next.on = true;
     tp = std::move(next);
     return SPD_OK;
@@ -2864,9 +2846,8 @@ int spd_model_tape_reset(spd_model_handle m) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_reset: null model");
     if (!m->tape.on) return m_fail(SPD_E_ARG, "spd_model_tape_reset: no tape configured (spd_model_tape_configure)");
     if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_tape_reset: a checked multi-step call is in flight; end it first");
-    m->tape.taken = 0;  // (the next sample goes into slot 0: no device work)
-    m->tape.valid = true;
-    m->tape.invalid_why.clear();
+    m->tape.ring.clear();
+    m->tape.validity.clear();
     return SPD_OK;
 }
 
@@ -2874,9 +2855,9 @@ int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *ca
     if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_info: null model");
     const spd_model::Tape &tp = m->tape;
     if (!tp.on) return m_fail(SPD_E_ARG, "spd_model_tape_info: no tape configured (spd_model_tape_configure)");
-    if (taken) *taken = tp.taken;
-    if (held) *held = static_cast<int>(std::min<long long>(tp.taken, tp.capacity));
-    if (capacity) *capacity = tp.capacity;
+    if (taken) *taken = tp.ring.taken;
+    if (held) *held = static_cast<int>(tp.ring.held());
+    if (capacity) *capacity = tp.ring.capacity;
     if (every) *every = tp.every;
     if (dtype) *dtype = tp.dtype;
     return SPD_OK;
@@ -2887,41 +2868,31 @@ int spd_model_tape_times(spd_model_handle m, int32_t *rows, int max_rows) {
     const spd_model::Tape &tp = m->tape;
     if (!tp.on) return m_fail(SPD_E_ARG, "spd_model_tape_times: no tape configured (spd_model_tape_configure)");
     if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_tape_times: bad destination");
-    const long long held = std::min<long long>(tp.taken, tp.capacity), oldest = tp.taken - held;  // (sample numbers from 0)
-    int n = 0;
-    for (; n < held && n < max_rows; ++n)
-        std::memcpy(rows + 6 * static_cast<size_t>(n), tp.rows.data() + 6 * static_cast<size_t>((oldest + n) % tp.capacity), 6 * sizeof(int32_t));
-    return n;
+    return tp.ring.copy_rows(rows, max_rows);
 }
 
 int spd_model_tape_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
                         void *stream) {
     const char *who = "spd_model_tape_read";
     if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    if (int rc = usable(m, who)) return rc;
     const spd_model::Tape &tp = m->tape;
-    if (!tp.on) return m_fail(SPD_E_ARG, std::string(who) + ": no tape configured (spd_model_tape_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (!tp.valid) return m_fail(SPD_E_ARG, std::string(who) + ": the tape is invalid until spd_model_tape_reset: " + tp.invalid_why);
+    if (int rc = read_allowed(m, who, tp.on, "no tape configured (spd_model_tape_configure)", tp.validity, "the tape is invalid until spd_model_tape_reset"))
+        return rc;
     const int id = stats_id(name);
     const spd_model::Tape::Var *v = nullptr;
     for (const auto &x : tp.vars)
         if (x.id == id) v = &x;
     if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
     if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    const long long held = std::min<long long>(tp.taken, tp.capacity), oldest = tp.taken - held;
-    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
-        return m_fail(SPD_E_ARG, std::string(who) + ": sample range out of bounds (" + std::to_string(held) + " samples held)");
+    if (int rc = held_range(who, tp.ring, t0, nt, "sample")) return rc;
     const size_t elem = tp.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->levels) * NG;
     const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
     if (count == 0 || nt == 0) return SPD_OK;
     M_HIP(hipSetDevice(m->ctx->device));
     const char *src = static_cast<const char *>(tp.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
     const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
-                                         static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % tp.capacity), tp.capacity,
+                                         static_cast<int>(elem), count, nt, tp.ring.slot_of_held(t0), tp.ring.capacity,
                                          static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
@@ -2968,7 +2939,7 @@ SpectraArgs spectra_args(const spd_model *m, unsigned mask, int first, int out_f
 // a sample: one launch for the group's members, straight into ring slot (n - 1) % capacity
 static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
     const spd_model::Spectra &sp = m->spectra;
-    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>((n - 1) % sp.capacity);
+    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>(sp.ring.slot(n));
     SpectraArgs a = spectra_args(m, sp.mask, first, 0);
     for (int v = 0; v < SPECTRA_NNAMES; ++v)
         if (sp.mask & (1u << v)) a.out[v] = static_cast<double *>(sp.alloc) + sp.offset[v] + slot * M * spectra_per_member(v);
@@ -2982,19 +2953,12 @@ int spd_model_spectra_configure(spd_model_handle m, const char *const *names, in
     if (int rc = spectra_ids(who, names, n_names, ids)) return rc;
     if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
     if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
+    if (int rc = configure_allowed(m, who)) return rc;
     spd_model::Spectra &sp = m->spectra;
-    void *old = sp.alloc;
-    sp = spd_model::Spectra{};  // (off before anything below can fail)
-    if (old) M_HIP(hipFree(old));
+    if (int rc = retire(m, sp)) return rc;
     if (n_names == 0) return SPD_OK;  // off
     spd_model::Spectra next;
     next.every = every;
-    next.capacity = capacity;
     const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
     size_t per_slot = 0;  // doubles of a sample
     for (int id : ids) {
@@ -3018,7 +2982,7 @@ int spd_model_spectra_configure(spd_model_handle m, const char *const *names, in
                                         " bytes); the spectra are off");
     }
     next.alloc = p;
-    next.rows.assign(slots * 6, 0);
+    next.ring = SampleRing(capacity, 6);
     next.on = true;
     sp = std::move(next);
     return SPD_OK;
@@ -3028,9 +2992,8 @@ int spd_model_spectra_reset(spd_model_handle m) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: null model");
     if (!m->spectra.on) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: no spectra configured (spd_model_spectra_configure)");
     if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: a checked multi-step call is in flight; end it first");
-    m->spectra.taken = 0;  // (the next sample goes into slot 0: no device work)
-    m->spectra.valid = true;
-    m->spectra.invalid_why.clear();
+    m->spectra.ring.clear();
+    m->spectra.validity.clear();
     return SPD_OK;
 }
 
@@ -3038,9 +3001,9 @@ int spd_model_spectra_info(spd_model_handle m, long long *taken, int *held, int 
     if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_info: null model");
     const spd_model::Spectra &sp = m->spectra;
     if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_info: no spectra configured (spd_model_spectra_configure)");
-    if (taken) *taken = sp.taken;
-    if (held) *held = static_cast<int>(std::min<long long>(sp.taken, sp.capacity));
-    if (capacity) *capacity = sp.capacity;
+    if (taken) *taken = sp.ring.taken;
+    if (held) *held = static_cast<int>(sp.ring.held());
+    if (capacity) *capacity = sp.ring.capacity;
     if (every) *every = sp.every;
     return SPD_OK;
 }
@@ -3050,39 +3013,30 @@ int spd_model_spectra_times(spd_model_handle m, int32_t *rows, int max_rows) {
     const spd_model::Spectra &sp = m->spectra;
     if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_times: no spectra configured (spd_model_spectra_configure)");
     if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_spectra_times: bad destination");
-    const long long held = std::min<long long>(sp.taken, sp.capacity), oldest = sp.taken - held;  // (sample numbers from 0)
-    int n = 0;
-    for (; n < held && n < max_rows; ++n)
-        std::memcpy(rows + 6 * static_cast<size_t>(n), sp.rows.data() + 6 * static_cast<size_t>((oldest + n) % sp.capacity), 6 * sizeof(int32_t));
-    return n;
+    return sp.ring.copy_rows(rows, max_rows);
 }
 
 int spd_model_spectra_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
                            void *stream) {
     const char *who = "spd_model_spectra_read";
     if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    if (int rc = usable(m, who)) return rc;
     const spd_model::Spectra &sp = m->spectra;
-    if (!sp.on) return m_fail(SPD_E_ARG, std::string(who) + ": no spectra configured (spd_model_spectra_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (!sp.valid) return m_fail(SPD_E_ARG, std::string(who) + ": the spectra are invalid until spd_model_spectra_reset: " + sp.invalid_why);
+    if (int rc = read_allowed(m, who, sp.on, "no spectra configured (spd_model_spectra_configure)", sp.validity,
+                              "the spectra are invalid until spd_model_spectra_reset"))
+        return rc;
     const int id = spectra_id(name);
     if (id < 0 || !(sp.mask & (1u << id))) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured names");
     if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    const long long held = std::min<long long>(sp.taken, sp.capacity), oldest = sp.taken - held;
-    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
-        return m_fail(SPD_E_ARG, std::string(who) + ": sample range out of bounds (" + std::to_string(held) + " samples held)");
+    if (int rc = held_range(who, sp.ring, t0, nt, "sample")) return rc;
     const size_t per = static_cast<size_t>(spectra_per_member(id));
     const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
     if (count == 0 || nt == 0) return SPD_OK;
     M_HIP(hipSetDevice(m->ctx->device));
     const double *src = static_cast<const double *>(sp.alloc) + sp.offset[id] + static_cast<size_t>(first) * per;
     const hipError_t e = run_spectra_gather(src, static_cast<double *>(dst_device), static_cast<int>(per),
                                             static_cast<long>(static_cast<size_t>(m->M) * per), count, nt,
-                                            static_cast<int>((oldest + t0) % sp.capacity), sp.capacity, static_cast<hipStream_t>(stream));
+                                            sp.ring.slot_of_held(t0), sp.ring.capacity, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
 }
@@ -3098,9 +3052,7 @@ int spd_model_spectra_compute(spd_model_handle m, const char *const *names, int 
     size_t per = 0;
     for (int id : ids) per += static_cast<size_t>(spectra_per_member(id));
     const size_t need = static_cast<size_t>(count) * per * sizeof(double);
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
     if (need == 0) return SPD_OK;
     M_HIP(hipSetDevice(m->ctx->device));
     SpectraArgs a = spectra_args(m, 0, first, first);
@@ -3125,22 +3077,15 @@ int spd_model_enstape_configure(spd_model_handle m, const char *const *names, in
     if (int rc = sample_ids(who, names, n_names, ids)) return rc;
     if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
     if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (int rc = configure_allowed(m, who)) return rc;
     for (size_t k = 0; k < ids.size(); ++k)
         if (ids[k] >= kPlevFirst && m->plev.n == 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still sample into the allocation this one replaces)
     spd_model::EnsTape &et = m->enstape;
-    void *old = et.alloc;
-    et = spd_model::EnsTape{};  // (off before anything below can fail)
-    if (old) M_HIP(hipFree(old));
+    if (int rc = retire(m, et)) return rc;
     if (n_names == 0) return SPD_OK;  // off
     spd_model::EnsTape next;
     next.every = every;
-    next.capacity = capacity;
     SamplePlan plan;
     plan_sample(m, ids, next, plan);
     const size_t slots = static_cast<size_t>(capacity);
@@ -3159,14 +3104,12 @@ int spd_model_enstape_configure(spd_model_handle m, const char *const *names, in
                                         std::to_string(capacity) + " samples of " + std::to_string(2 * per_slot) +
                                         " bytes); the ensemble tape is off");
     }
-    char *at = static_cast<char *>(p);
+    Carve carve{static_cast<char *>(p)};
     next.alloc = p;
-    next.mean = reinterpret_cast<double *>(at), at += ring;
-    next.m2 = reinterpret_cast<double *>(at), at += ring;
-    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
-    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.planes = reinterpret_cast<EnsTapePlane *>(at);
+    next.mean = carve.take<double>(ring);
+    next.m2 = carve.take<double>(ring);
+    carve_front(carve, plan, next);
+    next.planes = carve.take<EnsTapePlane>(desc);
     std::vector<int> slab_plane;
     hipError_t e = build_sample_front(m, plan, next, slab_plane);
     std::vector<EnsTapePlane> host_planes;
@@ -3181,12 +3124,8 @@ int spd_model_enstape_configure(spd_model_handle m, const char *const *names, in
             host_planes.push_back(d);
         }
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(EnsTapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    next.rows.assign(slots * 6, 0);
+    if (e != hipSuccess) return upload_failed(who, e, p);
+    next.ring = SampleRing(capacity, 6);
     next.counts.assign(slots * kEnsTapeGroups, 0);
     next.on = true;
     et = std::move(next);
@@ -3197,9 +3136,8 @@ int spd_model_enstape_reset(spd_model_handle m) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: null model");
     if (!m->enstape.on) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: no ensemble tape configured (spd_model_enstape_configure)");
     if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: a checked multi-step call is in flight; end it first");
-    m->enstape.taken = 0;  // (the next sample goes into slot 0 and opens its partials anew: no device work)
-    m->enstape.valid = true;
-    m->enstape.invalid_why.clear();
+    m->enstape.ring.clear();  // (the next sample opens the partials of slot 0 anew)
+    m->enstape.validity.clear();
     return SPD_OK;
 }
 
@@ -3207,9 +3145,9 @@ int spd_model_enstape_info(spd_model_handle m, long long *taken, int *held, int 
     if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_info: null model");
     const spd_model::EnsTape &et = m->enstape;
     if (!et.on) return m_fail(SPD_E_ARG, "spd_model_enstape_info: no ensemble tape configured (spd_model_enstape_configure)");
-    if (taken) *taken = et.taken;
-    if (held) *held = static_cast<int>(std::min<long long>(et.taken, et.capacity));
-    if (capacity) *capacity = et.capacity;
+    if (taken) *taken = et.ring.taken;
+    if (held) *held = static_cast<int>(et.ring.held());
+    if (capacity) *capacity = et.ring.capacity;
     if (every) *every = et.every;
     if (members) *members = m->M;
     return SPD_OK;
@@ -3220,22 +3158,16 @@ int spd_model_enstape_times(spd_model_handle m, int32_t *rows, int max_rows) {
     const spd_model::EnsTape &et = m->enstape;
     if (!et.on) return m_fail(SPD_E_ARG, "spd_model_enstape_times: no ensemble tape configured (spd_model_enstape_configure)");
     if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_enstape_times: bad destination");
-    const long long held = std::min<long long>(et.taken, et.capacity), oldest = et.taken - held;  // (sample numbers from 0)
-    int n = 0;
-    for (; n < held && n < max_rows; ++n)
-        std::memcpy(rows + 6 * static_cast<size_t>(n), et.rows.data() + 6 * static_cast<size_t>((oldest + n) % et.capacity), 6 * sizeof(int32_t));
-    return n;
+    return et.ring.copy_rows(rows, max_rows);
 }
 
 int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
     const char *who = "spd_model_enstape_read";
     if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    if (int rc = usable(m, who)) return rc;
     const spd_model::EnsTape &et = m->enstape;
-    if (!et.on) return m_fail(SPD_E_ARG, std::string(who) + ": no ensemble tape configured (spd_model_enstape_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (!et.valid)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape is invalid until spd_model_enstape_reset: " + et.invalid_why);
+    if (int rc = read_allowed(m, who, et.on, "no ensemble tape configured (spd_model_enstape_configure)", et.validity,
+                              "the ensemble tape is invalid until spd_model_enstape_reset"))
+        return rc;
     const int id = stats_id(name);
     const spd_model::EnsTape::Var *v = nullptr;
     for (const auto &x : et.vars)
@@ -3243,23 +3175,19 @@ int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t
     if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
     if (kind != SPD_ENS_MEAN && kind != SPD_ENS_STD && kind != SPD_ENS_M2)
         return m_fail(SPD_E_ARG, std::string(who) + ": kind must be SPD_ENS_MEAN, SPD_ENS_STD or SPD_ENS_M2");
-    const long long held = std::min<long long>(et.taken, et.capacity), oldest = et.taken - held;
-    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
-        return m_fail(SPD_E_ARG, std::string(who) + ": sample range out of bounds (" + std::to_string(held) + " samples held)");
+    if (int rc = held_range(who, et.ring, t0, nt, "sample")) return rc;
     const size_t per = static_cast<size_t>(v->levels) * NG, need = static_cast<size_t>(nt) * per * sizeof(double);
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
     if (nt == 0) return SPD_OK;
     M_HIP(hipSetDevice(m->ctx->device));
-    const int slot0 = static_cast<int>((oldest + t0) % et.capacity);
+    const int slot0 = et.ring.slot_of_held(t0);
     std::vector<int> counts(static_cast<size_t>(nt) * kEnsTapeGroups);  // of the samples of the read, in its order
     for (int t = 0; t < nt; ++t)
         std::memcpy(counts.data() + static_cast<size_t>(t) * kEnsTapeGroups,
-                    et.counts.data() + static_cast<size_t>((slot0 + static_cast<long long>(t)) % et.capacity) * kEnsTapeGroups,
+                    et.counts.data() + static_cast<size_t>(et.ring.slot_of_held(t0 + static_cast<long long>(t))) * kEnsTapeGroups,
                     kEnsTapeGroups * sizeof(int));
     const size_t var_at = v->first_plane * NG;
-    const hipError_t e = run_enstape_read(et.mean + var_at, et.m2 + var_at, static_cast<long>(per), et.nplanes, kind, nt, slot0, et.capacity,
+    const hipError_t e = run_enstape_read(et.mean + var_at, et.m2 + var_at, static_cast<long>(per), et.nplanes, kind, nt, slot0, et.ring.capacity,
                                           counts.data(), static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
@@ -3319,19 +3247,12 @@ int spd_model_acctape_configure(spd_model_handle m, const char *const *names, co
     if (n_entries > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
     if (n_entries > 0 && dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64)
         return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still accumulate into the allocation this one replaces)
+    if (int rc = configure_allowed(m, who)) return rc;
     spd_model::AccTape &ac = m->acctape;
-    void *old = ac.alloc;
-    ac = spd_model::AccTape{};  // (off before anything below can fail)
-    if (old) M_HIP(hipFree(old));
+    if (int rc = retire(m, ac)) return rc;
     if (n_entries == 0) return SPD_OK;  // off
     spd_model::AccTape next;
     next.every = every;
-    next.capacity = capacity;
     next.dtype = dtype;
     const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
     const size_t elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
@@ -3362,12 +3283,11 @@ int spd_model_acctape_configure(spd_model_handle m, const char *const *names, co
                                         " bytes asked for: " + std::to_string(capacity) + " windows of " + std::to_string(per_slot) +
                                         " bytes and " + std::to_string(accs) + " bytes of accumulators); the accumulation tape is off");
     }
-    char *at = static_cast<char *>(p);
+    Carve carve{static_cast<char *>(p)};
     next.alloc = p;
-    next.data = at, at += ring;
-    double *acc_at = reinterpret_cast<double *>(at);
-    at += accs;
-    next.planes = reinterpret_cast<AccTapePlane *>(at);
+    next.data = carve.take<char>(ring);
+    double *acc_at = carve.take<double>(accs);
+    next.planes = carve.take<AccTapePlane>(desc);
     std::vector<AccTapePlane> host_planes;
     for (int v = 0; v < kAccNNames; ++v) {
         if (!need[v][0] && !need[v][1] && !need[v][2]) continue;
@@ -3392,14 +3312,10 @@ int spd_model_acctape_configure(spd_model_handle m, const char *const *names, co
         }
     }
     const hipError_t e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(AccTapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return upload_failed(who, e, p);
     next.nplanes = static_cast<int>(host_planes.size());
     next.entries = std::move(entries);
-    next.rows.assign(slots * 7, 0);
+    next.ring = SampleRing(capacity, 7);
     next.window_start = -1;  // (the first window starts at the model's current step: step_impl reads the counter when it next runs)
     next.on = true;
     ac = std::move(next);
@@ -3410,10 +3326,9 @@ int spd_model_acctape_reset(spd_model_handle m) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: null model");
     if (!m->acctape.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_reset: ") + kAccOff);
     if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: a checked multi-step call is in flight; end it first");
-    m->acctape.taken = 0;          // (the next window goes into slot 0 ...
-    m->acctape.window_start = -1;  //  ... and starts at the next step, which overwrites the accumulators: no device work)
-    m->acctape.valid = true;
-    m->acctape.invalid_why.clear();
+    m->acctape.ring.clear();
+    m->acctape.window_start = -1;  // (the next window starts at the next step, which overwrites the accumulators: no device work)
+    m->acctape.validity.clear();
     return SPD_OK;
 }
 
@@ -3421,9 +3336,9 @@ int spd_model_acctape_info(spd_model_handle m, long long *taken, int *held, int 
     if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_info: null model");
     const spd_model::AccTape &ac = m->acctape;
     if (!ac.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_info: ") + kAccOff);
-    if (taken) *taken = ac.taken;
-    if (held) *held = static_cast<int>(std::min<long long>(ac.taken, ac.capacity));
-    if (capacity) *capacity = ac.capacity;
+    if (taken) *taken = ac.ring.taken;
+    if (held) *held = static_cast<int>(ac.ring.held());
+    if (capacity) *capacity = ac.ring.capacity;
     if (every) *every = ac.every;
     if (dtype) *dtype = ac.dtype;
     return SPD_OK;
@@ -3434,42 +3349,30 @@ int spd_model_acctape_times(spd_model_handle m, int32_t *rows, int max_rows) {
     const spd_model::AccTape &ac = m->acctape;
     if (!ac.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_times: ") + kAccOff);
     if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_acctape_times: bad destination");
-    const long long held = std::min<long long>(ac.taken, ac.capacity), oldest = ac.taken - held;  // (window numbers from 0)
-    int n = 0;
-    for (; n < held && n < max_rows; ++n)
-        std::memcpy(rows + 7 * static_cast<size_t>(n), ac.rows.data() + 7 * static_cast<size_t>((oldest + n) % ac.capacity), 7 * sizeof(int32_t));
-    return n;
+    return ac.ring.copy_rows(rows, max_rows);
 }
 
 int spd_model_acctape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
                            size_t dst_bytes, void *stream) {
     const char *who = "spd_model_acctape_read";
     if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    if (int rc = usable(m, who)) return rc;
     const spd_model::AccTape &ac = m->acctape;
-    if (!ac.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kAccOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (!ac.valid)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the accumulation tape is invalid until spd_model_acctape_reset: " + ac.invalid_why);
+    if (int rc = read_allowed(m, who, ac.on, kAccOff, ac.validity, "the accumulation tape is invalid until spd_model_acctape_reset")) return rc;
     const int id = acc_name_id(name);
     const spd_model::AccTape::Entry *v = nullptr;
     for (const auto &x : ac.entries)
         if (x.name == id && x.op == op) v = &x;
     if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": ('" + name + "', " + std::to_string(op) + ") is not among the configured entries");
     if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    const long long held = std::min<long long>(ac.taken, ac.capacity), oldest = ac.taken - held;
-    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
-        return m_fail(SPD_E_ARG, std::string(who) + ": window range out of bounds (" + std::to_string(held) + " windows held)");
+    if (int rc = held_range(who, ac.ring, t0, nt, "window")) return rc;
     const size_t elem = ac.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->planes) * NG;
     const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
     if (count == 0 || nt == 0) return SPD_OK;
     M_HIP(hipSetDevice(m->ctx->device));
     const char *src = static_cast<const char *>(ac.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
     const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
-                                         static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % ac.capacity), ac.capacity,
+                                         static_cast<int>(elem), count, nt, ac.ring.slot_of_held(t0), ac.ring.capacity,
                                          static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
@@ -3576,24 +3479,17 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
         if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
         if (dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64) return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
     }
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (int rc = configure_allowed(m, who)) return rc;
     for (int k = 0; k < n_entries; ++k)
         if (win_needs_levels(entries[k].name) && m->plev.n == 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still accumulate into the allocation this one replaces)
     spd_model::WinTape &wt = m->wintape;
-    void *old = wt.alloc;
-    wt = spd_model::WinTape{};  // (off before anything below can fail)
-    if (old) M_HIP(hipFree(old));
+    if (int rc = retire(m, wt)) return rc;
     if (n_entries == 0) return SPD_OK;  // off
     spd_model::WinTape next;
     next.window = window;
     next.every = every;
     next.sample_every = sample_every;
-    next.capacity = capacity;
     next.dtype = dtype;
     const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
     const size_t elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
@@ -3643,15 +3539,12 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
                                         " bytes asked for: " + std::to_string(capacity) + " windows of " + std::to_string(per_slot) +
                                         " bytes and " + std::to_string(accs) + " bytes of accumulators); the window tape is off");
     }
-    char *at = static_cast<char *>(p);
+    Carve carve{static_cast<char *>(p)};
     next.alloc = p;
-    next.data = at, at += ring;
-    double *acc_at = reinterpret_cast<double *>(at);
-    at += accs;
-    next.slab = reinterpret_cast<double *>(at), at += plan.slab_bytes;
-    next.table[0] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.table[1] = reinterpret_cast<FieldDesc *>(at), at += plan.table_bytes;
-    next.planes = reinterpret_cast<WinTapePlane *>(at);
+    next.data = carve.take<char>(ring);
+    double *acc_at = carve.take<double>(accs);
+    carve_front(carve, plan, next);
+    next.planes = carve.take<WinTapePlane>(desc);
     std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
     hipError_t e = build_sample_front(m, plan, next, slab_plane);
     std::vector<WinTapePlane> host_planes;
@@ -3689,14 +3582,10 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
         }
     }
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(WinTapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return upload_failed(who, e, p);
     next.nplanes = static_cast<int>(host_planes.size());
     next.entries = std::move(entries);
-    next.rows.assign(slots * 8, 0);
+    next.ring = SampleRing(capacity, 8);
     next.window_start = -1;  // (the first window starts at the model's current step: step_impl reads the counter when it next runs)
     next.on = true;
     wt = std::move(next);
@@ -3707,11 +3596,10 @@ int spd_model_wintape_reset(spd_model_handle m) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: null model");
     if (!m->wintape.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_reset: ") + kWinOff);
     if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: a checked multi-step call is in flight; end it first");
-    m->wintape.taken = 0;          // (the next window goes into slot 0 ...
-    m->wintape.window_start = -1;  //  ... and starts at the next step; its first sample overwrites the accumulators: no device work)
+    m->wintape.ring.clear();
+    m->wintape.window_start = -1;  // (the next window starts at the next step; its first sample overwrites the accumulators: no device work)
     m->wintape.samples = 0;
-    m->wintape.valid = true;
-    m->wintape.invalid_why.clear();
+    m->wintape.validity.clear();
     return SPD_OK;
 }
 
@@ -3720,9 +3608,9 @@ int spd_model_wintape_info(spd_model_handle m, long long *taken, int *held, int 
     if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_info: null model");
     const spd_model::WinTape &wt = m->wintape;
     if (!wt.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_info: ") + kWinOff);
-    if (taken) *taken = wt.taken;
-    if (held) *held = static_cast<int>(std::min<long long>(wt.taken, wt.capacity));
-    if (capacity) *capacity = wt.capacity;
+    if (taken) *taken = wt.ring.taken;
+    if (held) *held = static_cast<int>(wt.ring.held());
+    if (capacity) *capacity = wt.ring.capacity;
     if (window) *window = wt.window;
     if (every) *every = wt.every;
     if (sample_every) *sample_every = wt.sample_every;
@@ -3735,41 +3623,30 @@ int spd_model_wintape_times(spd_model_handle m, int32_t *rows, int max_rows) {
     const spd_model::WinTape &wt = m->wintape;
     if (!wt.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_times: ") + kWinOff);
     if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_wintape_times: bad destination");
-    const long long held = std::min<long long>(wt.taken, wt.capacity), oldest = wt.taken - held;  // (window numbers from 0)
-    int n = 0;
-    for (; n < held && n < max_rows; ++n)
-        std::memcpy(rows + 8 * static_cast<size_t>(n), wt.rows.data() + 8 * static_cast<size_t>((oldest + n) % wt.capacity), 8 * sizeof(int32_t));
-    return n;
+    return wt.ring.copy_rows(rows, max_rows);
 }
 
 int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
                            size_t dst_bytes, void *stream) {
     const char *who = "spd_model_wintape_read";
     if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    if (int rc = usable(m, who)) return rc;
     const spd_model::WinTape &wt = m->wintape;
-    if (!wt.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kWinOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (!wt.valid) return m_fail(SPD_E_ARG, std::string(who) + ": the window tape is invalid until spd_model_wintape_reset: " + wt.invalid_why);
+    if (int rc = read_allowed(m, who, wt.on, kWinOff, wt.validity, "the window tape is invalid until spd_model_wintape_reset")) return rc;
     const int id = win_name_id(name);
     const spd_model::WinTape::Entry *v = nullptr;
     for (const auto &x : wt.entries)
         if (x.name == id && x.op == op) v = &x;
     if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": ('" + name + "', " + std::to_string(op) + ") is not among the configured entries");
     if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    const long long held = std::min<long long>(wt.taken, wt.capacity), oldest = wt.taken - held;
-    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
-        return m_fail(SPD_E_ARG, std::string(who) + ": window range out of bounds (" + std::to_string(held) + " windows held)");
+    if (int rc = held_range(who, wt.ring, t0, nt, "window")) return rc;
     const size_t elem = wt.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->levels) * NG;
     const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % 16 != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 16-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
     if (count == 0 || nt == 0) return SPD_OK;
     M_HIP(hipSetDevice(m->ctx->device));
     const char *src = static_cast<const char *>(wt.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
     const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
-                                         static_cast<int>(elem), count, nt, static_cast<int>((oldest + t0) % wt.capacity), wt.capacity,
+                                         static_cast<int>(elem), count, nt, wt.ring.slot_of_held(t0), wt.ring.capacity,
                                          static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
@@ -3818,18 +3695,12 @@ int spd_model_nudge_configure(spd_model_handle m, const char *const *names, int 
         if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
         if (in_loop != 0 && in_loop != 1) return m_fail(SPD_E_ARG, std::string(who) + ": in_loop must be 0 or 1");
     }
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (int rc = configure_allowed(m, who)) return rc;
     for (int i = 0; n_names > 0 && member_mask && i < m->M; ++i)
         if (member_mask[i] != 0 && member_mask[i] != 1)
             return m_fail(SPD_E_ARG, std::string(who) + ": the mask entry of member " + std::to_string(i) + " is neither 0 nor 1");
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still read the allocation this one replaces)
     spd_model::Nudge &nd = m->nudge;
-    void *old = nd.alloc;
-    nd = spd_model::Nudge{};  // (off before anything below can fail)
-    if (old) M_HIP(hipFree(old));
+    if (int rc = retire(m, nd)) return rc;
     if (n_names == 0) return SPD_OK;  // off
     spd_model::Nudge next;
     next.capacity = capacity;
@@ -3863,13 +3734,12 @@ int spd_model_nudge_configure(spd_model_handle m, const char *const *names, int 
         return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the target slots (" + std::to_string(total) + " bytes asked for: " +
                                         std::to_string(capacity) + " slots); nudging is off");
     }
-    char *at = static_cast<char *>(p);
+    Carve carve{static_cast<char *>(p)};
     next.alloc = p;
-    next.targets = reinterpret_cast<double *>(at), at += targets;
-    double *gain_dev = reinterpret_cast<double *>(at);
-    at += gain_bytes;
-    next.planes = reinterpret_cast<NudgePlane *>(at), at += desc;
-    next.mask = member_mask ? reinterpret_cast<int *>(at) : nullptr;
+    next.targets = carve.take<double>(targets);
+    double *gain_dev = carve.take<double>(gain_bytes);
+    next.planes = carve.take<NudgePlane>(desc);
+    next.mask = member_mask ? carve.take<int>(mask_bytes) : nullptr;
     std::vector<NudgePlane> host_planes;
     std::vector<double> host_gains;
     double *const base[kNudgeNames] = {m->P.vor, m->P.div, m->P.t, m->P.tr, m->P.ps};
@@ -3890,11 +3760,7 @@ int spd_model_nudge_configure(spd_model_handle m, const char *const *names, int 
     if (e == hipSuccess && !rows.empty()) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(NudgePlane), hipMemcpyHostToDevice);
     if (e == hipSuccess && member_mask) e = hipMemcpy(next.mask, member_mask, sizeof(int) * m->M, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return upload_failed(who, e, p);
     next.nplanes = static_cast<int>(host_planes.size());
     next.on = true;
     nd = std::move(next);
@@ -4021,22 +3887,15 @@ int spd_model_breed_configure(spd_model_handle m, const int32_t *control, const 
     // (the arguments first: what does not need the member count, then the model, then the controls)
     if (control)
         if (int rc = spd_breed_check(nullptr, 0, weights, target, every, capacity, in_loop)) return rc;
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    if (int rc = configure_allowed(m, who)) return rc;
     if (control)
         if (int rc = spd_breed_check(control, m->M, weights, target, every, capacity, in_loop)) return rc;
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (launches in flight may still use the allocation this one replaces)
     spd_model::Breed &br = m->breed;
-    void *old = br.alloc;
-    br = spd_model::Breed{};  // (off before anything below can fail)
-    if (old) M_HIP(hipFree(old));
+    if (int rc = retire(m, br)) return rc;
     if (!control) return SPD_OK;  // off
     spd_model::Breed next;
     next.in_loop = in_loop != 0;
     next.every = every;
-    next.capacity = capacity;
     next.target = target;
     const size_t M = static_cast<size_t>(m->M);
     std::vector<BreedPair> pairs;
@@ -4073,13 +3932,13 @@ int spd_model_breed_configure(spd_model_handle m, const int32_t *control, const 
         return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the ring (" + std::to_string(total) + " bytes asked for: " +
                                         std::to_string(capacity) + " events); breeding is off");
     }
-    char *at = static_cast<char *>(p);
+    Carve carve{static_cast<char *>(p)};
     next.alloc = p;
-    next.planes = reinterpret_cast<BreedPlane *>(at), at += plane_bytes;
-    next.pairs = reinterpret_cast<BreedPair *>(at), at += pair_bytes;
-    next.slot_of = reinterpret_cast<int *>(at), at += slot_bytes;
-    next.partial = reinterpret_cast<double *>(at), at += partial_bytes;
-    next.ring = reinterpret_cast<double *>(at);
+    next.planes = carve.take<BreedPlane>(plane_bytes);
+    next.pairs = carve.take<BreedPair>(pair_bytes);
+    next.slot_of = carve.take<int>(slot_bytes);
+    next.partial = carve.take<double>(partial_bytes);
+    next.data = carve.take<double>(ring_bytes);
     std::vector<double> ring(ring_doubles);  // what a member that is not bred shows: amplitude 0.0, factor 1.0
     for (size_t slot = 0; slot < static_cast<size_t>(capacity); ++slot) {
         std::fill(ring.begin() + slot * 2 * M, ring.begin() + slot * 2 * M + M, 0.0);
@@ -4089,14 +3948,10 @@ int spd_model_breed_configure(spd_model_handle m, const int32_t *control, const 
     if (e == hipSuccess && !pairs.empty()) e = hipMemcpy(next.pairs, pairs.data(), pairs.size() * sizeof(BreedPair), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(next.slot_of, slot_of.data(), M * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(next.partial, 0, partial_bytes);
-    if (e == hipSuccess) e = hipMemcpy(next.ring, ring.data(), ring_doubles * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.data, ring.data(), ring_doubles * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    next.rows.assign(static_cast<size_t>(capacity) * 6, 0);
+    if (e != hipSuccess) return upload_failed(who, e, p);
+    next.ring = SampleRing(capacity, 6);
     next.on = true;
     br = std::move(next);
     return SPD_OK;
@@ -4110,17 +3965,16 @@ static int breed_rescale(spd_model *m, hipStream_t s, const char *who) {
     if (br.nbred == 0) return SPD_OK;
     if (int rc = settle_deferred_check(m)) return rc;
     m->surf_cache_valid = m->phi_ahead = false;
-    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>(br.taken % br.capacity);
-    double *amplitude = br.ring + slot * 2 * M;
+    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>(br.ring.slot(br.ring.taken + 1));
+    double *amplitude = br.data + slot * 2 * M;
     hipError_t e = run_breed_norm(br.planes, br.pairs, br.nbred, m->ctx->dev.elm2, br.partial, s);
     if (e == hipSuccess) e = run_breed_rescale(br.planes, br.pairs, br.nbred, br.partial, br.target, amplitude, amplitude + M, s);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return m_fail(SPD_E_DEVICE, std::string(who) + ": breeding: " + hipGetErrorString(e));
     }
-    int32_t *row = br.rows.data() + 6 * slot;
-    row[0] = m->current_step; row[1] = m->cal.year; row[2] = m->cal.month; row[3] = m->cal.day; row[4] = m->cal.hour; row[5] = m->cal.minute;
-    ++br.taken;
+    ++br.ring.taken;
+    br.ring.stamp(br.ring.taken, m->current_step, m->cal);
     ++br.applied;
     return SPD_OK;
 }
@@ -4145,9 +3999,7 @@ int spd_model_breed_compute(spd_model_handle m, void *dst_device, size_t dst_byt
     if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
     if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
     const size_t need = static_cast<size_t>(m->M) * sizeof(double);
-    if (!dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
     M_HIP(hipSetDevice(m->ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = run_breed_norm(br.planes, br.pairs, br.nbred, m->ctx->dev.elm2, br.partial, s);
@@ -4167,18 +4019,14 @@ int spd_model_breed_read(spd_model_handle m, int what, int t0, int nt, void *dst
     const spd_model::Breed &br = m->breed;
     if (!br.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kBreedOff);
     if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    const long long held = std::min<long long>(br.taken, br.capacity), oldest = br.taken - held;
-    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > held)
-        return m_fail(SPD_E_ARG, std::string(who) + ": event range out of bounds (" + std::to_string(held) + " events held)");
+    if (int rc = held_range(who, br.ring, t0, nt, "event")) return rc;
     const size_t M = static_cast<size_t>(m->M), need = static_cast<size_t>(nt) * M * sizeof(double);
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % sizeof(double) != 0) return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be 8-byte aligned");
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
     if (nt == 0) return SPD_OK;
     M_HIP(hipSetDevice(m->ctx->device));
     // (the spectra's gather with one "member" whose entry is the M values of a slot: dst[t][i] = ring[slot(t)][what][i])
-    const hipError_t e = run_spectra_gather(br.ring + static_cast<size_t>(what) * M, static_cast<double *>(dst_device), m->M, static_cast<long>(2 * M), 1, nt,
-                                            static_cast<int>((oldest + t0) % br.capacity), br.capacity, static_cast<hipStream_t>(stream));
+    const hipError_t e = run_spectra_gather(br.data + static_cast<size_t>(what) * M, static_cast<double *>(dst_device), m->M, static_cast<long>(2 * M), 1, nt,
+                                            br.ring.slot_of_held(t0), br.ring.capacity, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     return SPD_OK;
 }
@@ -4188,18 +4036,14 @@ int spd_model_breed_rows(spd_model_handle m, int32_t *rows, int max_rows) {
     const spd_model::Breed &br = m->breed;
     if (!br.on) return m_fail(SPD_E_ARG, std::string("spd_model_breed_rows: ") + kBreedOff);
     if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_breed_rows: bad destination");
-    const long long held = std::min<long long>(br.taken, br.capacity), oldest = br.taken - held;
-    int n = 0;
-    for (; n < held && n < max_rows; ++n)
-        std::memcpy(rows + 6 * static_cast<size_t>(n), br.rows.data() + 6 * static_cast<size_t>((oldest + n) % br.capacity), 6 * sizeof(int32_t));
-    return n;
+    return br.ring.copy_rows(rows, max_rows);
 }
 
 int spd_model_breed_reset(spd_model_handle m) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_reset: null model");
     if (!m->breed.on) return m_fail(SPD_E_ARG, std::string("spd_model_breed_reset: ") + kBreedOff);
     if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_breed_reset: a checked multi-step call is in flight; end it first");
-    m->breed.taken = 0;  // (the next event goes into slot 0: no device work)
+    m->breed.ring.clear();
     return SPD_OK;
 }
 
@@ -4208,8 +4052,8 @@ int spd_model_breed_info(spd_model_handle m, int *bred, int *every, int *capacit
     const spd_model::Breed &br = m->breed;  // (a model without breeding: all zero)
     if (bred) *bred = br.nbred;
     if (every) *every = br.every;
-    if (capacity) *capacity = br.capacity;
-    if (taken) *taken = br.taken;
+    if (capacity) *capacity = br.ring.capacity;
+    if (taken) *taken = br.ring.taken;
     if (in_loop) *in_loop = br.in_loop ? 1 : 0;
     if (applied) *applied = br.applied;
     return SPD_OK;

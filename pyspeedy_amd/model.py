@@ -411,22 +411,33 @@ class EnsembleModel:
         name = [k for k, v in self.TAPE_DTYPES.items() if v[0] == dtype.value][0]
         return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, dtype=name)
 
-    def _tape_rows(self):
-        held = self.tape_info["held"]
-        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
-        n = self._lib.spd_model_tape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
+    # ---- the rows a ring keeps beside its slots (csrc/ring.hpp): step and date of each held sample, window or event, oldest first ----
+    def _ring_rows(self, symbol, held, width):
+        rows = np.zeros((max(held, 1), width), dtype=np.int32)
+        n = getattr(self._lib, symbol)(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
         if n < 0:
-            check(n, "spd_model_tape_times")
+            check(n, symbol)
         return rows[:n]
+
+    @staticmethod
+    def _row_steps(rows):
+        return rows[:, 0].astype(np.int64)
+
+    @staticmethod
+    def _row_times(rows):
+        from datetime import datetime
+        return [datetime(*(int(v) for v in row[1:6])) for row in rows]
+
+    def _tape_rows(self):
+        return self._ring_rows("spd_model_tape_times", self.tape_info["held"], 6)
 
     def tape_steps(self):
         """The model's step counter after each held sample's step, oldest first (numpy int array)."""
-        return self._tape_rows()[:, 0].astype(np.int64)
+        return self._row_steps(self._tape_rows())
 
     def tape_times(self):
         """The date of each held sample's state, oldest first (a list of datetime)."""
-        from datetime import datetime
-        return [datetime(*(int(v) for v in row[1:6])) for row in self._tape_rows()]
+        return self._row_times(self._tape_rows())
 
     def tape(self, name, first=0, count=None, t0=0, nt=None):
         """Members [first, first + count) and samples [t0, t0 + nt) of the held ones (oldest first) of one variable: a tensor
@@ -469,21 +480,15 @@ class EnsembleModel:
         return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, members=members.value)
 
     def _enstape_rows(self):
-        held = self.enstape_info["held"]
-        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
-        n = self._lib.spd_model_enstape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
-        if n < 0:
-            check(n, "spd_model_enstape_times")
-        return rows[:n]
+        return self._ring_rows("spd_model_enstape_times", self.enstape_info["held"], 6)
 
     def enstape_steps(self):
         """The model's step counter after each held sample's step, oldest first (numpy int array)."""
-        return self._enstape_rows()[:, 0].astype(np.int64)
+        return self._row_steps(self._enstape_rows())
 
     def enstape_times(self):
         """The date of each held sample's state, oldest first (a list of datetime)."""
-        from datetime import datetime
-        return [datetime(*(int(v) for v in row[1:6])) for row in self._enstape_rows()]
+        return self._row_times(self._enstape_rows())
 
     def _enstape_read(self, name, kind, t0, nt):
         t0 = int(t0)
@@ -548,21 +553,15 @@ class EnsembleModel:
         return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, dtype=name)
 
     def _acctape_rows(self):
-        held = self.acctape_info["held"]
-        rows = np.zeros((max(held, 1), 7), dtype=np.int32)
-        n = self._lib.spd_model_acctape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
-        if n < 0:
-            check(n, "spd_model_acctape_times")
-        return rows[:n]
+        return self._ring_rows("spd_model_acctape_times", self.acctape_info["held"], 7)
 
     def acctape_steps(self):
         """The model's step counter after the last step of each held window, oldest first (numpy int array)."""
-        return self._acctape_rows()[:, 0].astype(np.int64)
+        return self._row_steps(self._acctape_rows())
 
     def acctape_times(self):
         """The date of the state after each held window's last step, oldest first (a list of datetime)."""
-        from datetime import datetime
-        return [datetime(*(int(v) for v in row[1:6])) for row in self._acctape_rows()]
+        return self._row_times(self._acctape_rows())
 
     def acctape_counts(self):
         """The number of steps in each held window, oldest first (numpy int array)."""
@@ -653,21 +652,15 @@ class EnsembleModel:
                     dtype=name)
 
     def _wintape_rows(self):
-        held = self.wintape_info["held"]
-        rows = np.zeros((max(held, 1), 8), dtype=np.int32)
-        n = self._lib.spd_model_wintape_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
-        if n < 0:
-            check(n, "spd_model_wintape_times")
-        return rows[:n]
+        return self._ring_rows("spd_model_wintape_times", self.wintape_info["held"], 8)
 
     def wintape_steps(self):
         """The model's step counter after the last step of each held window, oldest first (numpy int array)."""
-        return self._wintape_rows()[:, 0].astype(np.int64)
+        return self._row_steps(self._wintape_rows())
 
     def wintape_times(self):
         """The date of the state after each held window's last step, oldest first (a list of datetime)."""
-        from datetime import datetime
-        return [datetime(*(int(v) for v in row[1:6])) for row in self._wintape_rows()]
+        return self._row_times(self._wintape_rows())
 
     def wintape_counts(self):
         """(samples, steps) in each held window, oldest first (two numpy int arrays)."""
@@ -851,21 +844,15 @@ class EnsembleModel:
         return out
 
     def _breed_rows(self):
-        held = self.breed_info()["held"]
-        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
-        n = self._lib.spd_model_breed_rows(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
-        if n < 0:
-            check(n, "spd_model_breed_rows")
-        return rows[:n]
+        return self._ring_rows("spd_model_breed_rows", self.breed_info()["held"], 6)
 
     def breed_steps(self):
         """The model's step counter at each held event, oldest first (numpy int array)."""
-        return self._breed_rows()[:, 0].astype(np.int64)
+        return self._row_steps(self._breed_rows())
 
     def breed_times(self):
         """The date of each held event's state, oldest first (a list of datetime)."""
-        from datetime import datetime
-        return [datetime(*(int(v) for v in row[1:6])) for row in self._breed_rows()]
+        return self._row_times(self._breed_rows())
 
     def breed_growth(self):
         """Growth rates [1/s] of the held events: a float64 numpy array [events][members] of ln(A_k / A'_(k-1)) / dt, with
@@ -918,21 +905,15 @@ class EnsembleModel:
         return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value)
 
     def _spectra_rows(self):
-        held = self.spectra_info()["held"]
-        rows = np.zeros((max(held, 1), 6), dtype=np.int32)
-        n = self._lib.spd_model_spectra_times(self._m, rows.ctypes.data_as(C.POINTER(C.c_int32)), held)
-        if n < 0:
-            check(n, "spd_model_spectra_times")
-        return rows[:n]
+        return self._ring_rows("spd_model_spectra_times", self.spectra_info()["held"], 6)
 
     def spectra_steps(self):
         """The model's step counter after each held sample's step, oldest first (numpy int array)."""
-        return self._spectra_rows()[:, 0].astype(np.int64)
+        return self._row_steps(self._spectra_rows())
 
     def spectra_times(self):
         """The date of each held sample's state, oldest first (a list of datetime)."""
-        from datetime import datetime
-        return [datetime(*(int(v) for v in row[1:6])) for row in self._spectra_rows()]
+        return self._row_times(self._spectra_rows())
 
     def _spectra_derive(self, name, rot, div):
         """ke_spectrum = rot + div [..., 8, 32]; ke_mean = its sum over l [..., 8]; ke_column = sum over the levels of dhs[k] *

@@ -504,6 +504,78 @@ def test_the_recorders_are_independent(spectral, bc, twin64):
                 assert np.array_equal(a, b), (key, n)
 
 
+def test_all_six_recorders_together_in_rounds_with_rings_that_wrap(spectral, bc):
+    """Statistics, tape, spectra, ensemble tape, accumulation tape and window tape on at once, in ONE checked call of 13 steps that
+    is issued as five rounds of 2, 2, 2, 2 and 1 members (9 members, two member groups, block_members 1: the last round leaves a
+    group empty), into rings of two slots that wrap inside the call (the ensemble tape takes six samples and folds the last two
+    only).  Everything a recorder hands out -- its info, steps, times, counts and every tensor -- equals what it hands out when it
+    is the only one on in the same plan, and the final state, every registry variable, is bitwise that of a run with none."""
+    import torch
+    M, steps = 9, 13
+    fields = ("t_grid", "precnv")
+    names = ("ke_rot_spectrum", "lnps_mean")
+    acc = (("precnv", "sum"), ("olr", "mean"))
+    win = (("t_grid", "mean"), ("precnv", "max"), ("wspd_grid", "max"))
+    configure = {
+        "stats": lambda m: m.stats_configure(fields, 2, variance=True),
+        "tape": lambda m: m.tape_configure(fields, 3, 2, dtype="float64"),
+        "spectra": lambda m: m.spectra_configure(names, 2, 2),
+        "enstape": lambda m: m.enstape_configure(fields, 2, 2),
+        "acctape": lambda m: m.acctape_configure(acc, 3, 2, dtype="float64"),
+        "wintape": lambda m: m.wintape_configure(win, 2, 2, sample_every=1, dtype="float64"),
+    }
+    read = {
+        "stats": lambda m: dict(samples=m.stats_samples, mean={n: m.stats_mean(n) for n in fields}, var={n: m.stats_var(n) for n in fields}),
+        "tape": lambda m: dict(info=m.tape_info, steps=m.tape_steps().tolist(), times=m.tape_times(), data={n: m.tape(n) for n in fields}),
+        "spectra": lambda m: dict(info=m.spectra_info(), steps=m.spectra_steps().tolist(), times=m.spectra_times(),
+                                  data={n: m.spectra(n) for n in names}),
+        "enstape": lambda m: dict(info=m.enstape_info, steps=m.enstape_steps().tolist(), times=m.enstape_times(),
+                                  data={n: m.enstape(n) + m.enstape_moments(n)[2:] for n in fields}),
+        "acctape": lambda m: dict(info=m.acctape_info, steps=m.acctape_steps().tolist(), times=m.acctape_times(),
+                                  counts=m.acctape_counts().tolist(), data={e: m.acctape(*e) for e in acc}),
+        "wintape": lambda m: dict(info=m.wintape_info, steps=m.wintape_steps().tolist(), times=m.wintape_times(),
+                                  counts=[c.tolist() for c in m.wintape_counts()], data={e: m.wintape(*e) for e in win}),
+    }
+    taken = {"tape": 4, "spectra": 6, "enstape": 6, "acctape": 4, "wintape": 6}  # 13 steps from step 0, every 3 or 2
+
+    def run(on):
+        model = perturbed(spectral, bc, M, options=(("member_groups", 2), ("block_members", 1)), levels=None)
+        assert model.config()["chunks"] == 2 and model.config()["rounds"] == 5
+        for key in on:
+            configure[key](model)
+        failed, _ = model.run_checked(steps)
+        assert (failed == -1).all()
+        out = {key: read[key](model) for key in on}
+        out["state"] = {n: [model.get(n, i) for i in range(M)] for n in model.variables() if n not in ("lon", "lat", "lev")}
+        torch.cuda.synchronize()
+        model.close()
+        return out
+
+    def assert_same(got, ref, what):
+        if torch.is_tensor(ref):
+            assert_bitwise(got, ref, what)
+        elif isinstance(ref, dict):
+            assert got.keys() == ref.keys(), what
+            for k in ref:
+                assert_same(got[k], ref[k], "%s, %s" % (what, k))
+        elif isinstance(ref, tuple):
+            assert len(got) == len(ref), what
+            for k, (a, b) in enumerate(zip(got, ref)):
+                assert_same(a, b, "%s, %d" % (what, k))
+        else:
+            assert got == ref, (what, got, ref)
+
+    together, none = run(tuple(configure)), run(())
+    assert together["stats"]["samples"] == 6
+    for key, n in taken.items():  # (every ring has wrapped)
+        assert together[key]["info"]["taken"] == n and together[key]["info"]["held"] == 2 and len(together[key]["steps"]) == 2, key
+    for key in configure:
+        assert_same(together[key], run((key,))[key], key + " beside the others")
+    for n, per_member in none["state"].items():
+        for i, (a, b) in enumerate(zip(together["state"][n], per_member)):
+            assert np.array_equal(a, b), (n, i)
+
+
 def test_shapes_dtypes_device_and_levels(spectral, bc):
     """wintape() follows the tape's shape conventions, in the ring's dtype, on the model's device; pressure-level names (the wind
     speed at levels among them) are refused before levels are configured."""

@@ -629,6 +629,52 @@ int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int fir
                            size_t dst_bytes, void *stream);
 int spd_wintape_plan(int year, int month, int day, int hour, int minute, int step0, int nsteps, int window, int every,
                      int sample_every, int32_t *rows, int max_rows);
+/* The projection tape: scalar time series taken from grid-space fields -- box, band and global means, differences of boxes,
+ * station values, any fixed linear functional of one plane -- formed on the device behind the sampled steps of spd_model_step /
+ * spd_model_step_checked_begin calls of any length and kept in a ring in device memory.  Off unless configured; a model that never
+ * configures it issues the launches it always issued.
+ * Definition.  P weight maps (patterns), 1 <= P <= 64, each fp64 [48][96] in the layout of one level of a tape sample (row j = 0
+ * the southernmost Gaussian latitude, column i at 3.75 i degrees east), uploaded once and shared by all members; every weight must
+ * be finite.  E entries (name, level, pattern), 1 <= E <= 1024: name one of the tape's fourteen catalogue names, level from 0 up
+ * to the name's level count (8 for the sigma fields, 1 for ps_grid, precnv, precls, mslp, the configured count for *_plev, which
+ * need spd_model_plev_configure first), pattern an index into the maps.  x[p], p = 96 j + i, is exactly what an fp64 tape of that
+ * name holds at that level after the sampled step, in export units (precnv / precls widened from float first under
+ * physics_storage32; a sampled step stores the diagnostics-only outputs when either is an entry).  The result of an entry is one
+ * double per member and sample, summed in a fixed order with every product and every sum rounded on its own (no contraction):
+ *   lane t of 256:  s_t = w[t] x[t];  for r = 1 ... 17 in that order  s_t = s_t + w[t + 256 r] x[t + 256 r]
+ *   tree[t] = s_t;  for half = 128, 64, ..., 1:  tree[t] = tree[t] + tree[t + half] for t < half;  result = tree[0]
+ * All 4608 = 18 x 256 terms take part; a zero weight is not skipped.  The result does not depend on the launch plan (member
+ * groups, rounds, checked or plain calls), and a numpy restatement of the order reproduces it bit for bit.
+ * Sampling is the tape's: after every step that leaves the absolute step counter at a multiple of `every`, with the recorder's own
+ * slab and tables, behind the other recorders' launches of that step on each member group's stream.  Sample n (from 1 since the
+ * last reset) lies in slot (n - 1) % capacity of the ring [slot][M][E] doubles.
+ *   _configure  weights[n_patterns][48][96] (host memory), names / levels / patterns[n_entries]; allocates (one hipMalloc of the
+ *               recorder's own, synchronises the device) and empties the ring; n_entries = 0 switches the recorder off and frees
+ *               it (the other arguments are then not looked at).  SPD_E_ARG, checked in this order before a model or a device is
+ *               needed: every < 1; capacity < 1; n_patterns outside 1 ... 64; n_entries outside 0 ... 1024; null weights; a null
+ *               names, levels or patterns; a weight that is not finite (the message names pattern and point); an unknown name
+ *               (with the catalogue's list); per entry a level below 0 or, for a name of fixed level count, beyond it, then a
+ *               pattern index outside the maps; then a null model or a checked call in flight; then a pressure-level name (mslp included)
+ *               before spd_model_plev_configure or with a level beyond the configured count.  SPD_E_DEVICE with the number of bytes asked
+ *               for when the allocation fails: the recorder is then off and the model as usable as before.
+ *               spd_model_plev_configure is refused while the recorder holds a pressure-level name.
+ *   _reset      empties the ring (host only, no device work).  spd_model_init does the same.
+ *   _info       taken: samples since the last reset; held = min(taken, capacity); any pointer may be NULL.
+ *   _times      rows[held][6] for the held samples, oldest first: the absolute step counter after the sampled step, then year,
+ *               month, day, hour, minute of that state (host memory).  Returns the number of rows written (at most max_rows).
+ *   _read       members [first, first + count) and samples [t0, t0 + nt) of the held ones, oldest first, of every entry in the
+ *               configured order into dst_device[count][nt][n_entries] doubles, stream-ordered; dst_device must be 8-byte aligned.
+ *               SPD_E_SIZE when dst_bytes is too small.
+ * Reads fail (SPD_E_ARG, with the reason) while a checked call is in flight and after a checked call that reported a failed range
+ * check (the message names the member and the step): the series stays invalid until _reset or spd_model_init.
+ * spd_model_copy_member does not carry the recorder, and the outer boundary (spd_parallel_step*) does not keep it across the
+ * models it merges and splits. */
+int spd_model_projtape_configure(spd_model_handle m, const double *weights, int n_patterns, const char *const *names, const int *levels,
+                                 const int *patterns, int n_entries, int every, int capacity);
+int spd_model_projtape_reset(spd_model_handle m);
+int spd_model_projtape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *n_patterns, int *n_entries);
+int spd_model_projtape_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_projtape_read(spd_model_handle m, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
 /* Nudging: operator-split Newtonian relaxation of the spectral state toward target fields, on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length (in-loop mode) or once on the state as it stands (_apply): replay experiments,
  * spectral nudging of the large scales, the cheapest form of data assimilation.  The only thing in the device loop that WRITES the

@@ -363,6 +363,43 @@ module pyspeedy_amd_c
             integer(c_int), value :: year, month, day, hour, minute, step0, nsteps, window, every, sample_every, max_rows
             integer(c_int32_t), intent(out) :: rows(8, *)
         end function
+        ! the projection tape: weighted sums of single planes of the state's grid-space fields as scalar series, formed on the
+        ! device behind the sampled steps (pyspeedy_amd.h: spd_model_projtape_*).  weights(96, 48, n_patterns); an entry is
+        ! names(k) at the 0-based level levels(k) under the 0-based pattern patterns(k); rows(6, *): as the tape's; _read:
+        ! real(c_double) (n_entries, nt, count)
+        integer(c_int) function spd_model_projtape_configure(model, weights, n_patterns, names, levels, patterns, n_entries, every, &
+                capacity) bind(C, name="spd_model_projtape_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model
+            real(c_double), intent(in) :: weights(*)
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), patterns(*)
+            integer(c_int), value :: n_patterns, n_entries, every, capacity
+        end function
+        integer(c_int) function spd_model_projtape_reset(model) bind(C, name="spd_model_projtape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_projtape_info(model, taken, held, capacity, every, n_patterns, n_entries) &
+                bind(C, name="spd_model_projtape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken
+            integer(c_int), intent(out) :: held, capacity, every, n_patterns, n_entries
+        end function
+        integer(c_int) function spd_model_projtape_times(model, rows, max_rows) bind(C, name="spd_model_projtape_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_projtape_read(model, first, count, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_projtape_read")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: first, count, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
         ! nudging: relaxation of the spectral state toward target fields behind every step of spd_model_step (in_loop = 1) or once on
         ! the state as it stands (_apply) (pyspeedy_amd.h: spd_model_nudge_*).  names: any of vor, div, t, tr, ps; gains(32, 8,
         ! n_names) in [0, 1] by total wavenumber, level and name (ps reads its first row); member_mask: c_loc of an

@@ -164,6 +164,12 @@ _SIGNATURES = {
     "spd_model_wintape_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),
     "spd_wintape_plan": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_projtape_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]),
+    "spd_model_projtape_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_projtape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 5),
+    "spd_model_projtape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_projtape_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spd_model_nudge_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int,
                                             C.c_int]),
     "spd_model_nudge_set_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
@@ -376,3 +382,89 @@ def breed_weights(kind="kinetic_energy", levels=None):
     else:
         raise ValueError("unknown kind of breeding weights '%s' (kinetic_energy, total_energy, t_rms)" % (kind,))
     return out
+
+
+class ProjectionWeights:
+    """Weight maps [48][96] for EnsembleModel.projtape_configure, in the layout of one level of a tape sample: row j = 0 is the
+    southernmost Gaussian latitude, column i lies at 3.75 i degrees east.  `lat` and `lon` are the export's coordinates in degrees
+    (float32 values, as a Dataset carries them); `area` is the quadrature weight of a grid point, summing to 1 over the sphere: the
+    library's Gaussian weight of its row (table "wt", which sums to 1 over a hemisphere) over two hemispheres and the 96 points
+    of the row.  Host only: no device is needed."""
+
+    def __init__(self, spectral=None):
+        import numpy as np
+        handle = None if spectral is None else spectral.handle
+
+        def table(name):
+            n = lib().spd_get_table_host(handle, name.encode(), None, 0)
+            if n < 0:
+                check(int(n), "spd_get_table_host(%s)" % name)
+            out = np.empty(int(n), dtype=np.float64)
+            lib().spd_get_table_host(handle, name.encode(), out.ctypes.data_as(C.c_void_p), out.size)
+            return out
+
+        radang, wt = table("radang"), table("wt")
+        # the export's coordinates (the outer boundary's "lon" and "lat": 3.75 i and radang * 90 / asin(1), in single precision)
+        self.lon = (np.float32(3.75) * np.arange(IX, dtype=np.float32)).astype(np.float64)
+        self.lat = (radang.astype(np.float32) * np.float32(90.0) / np.arcsin(np.float32(1.0))).astype(np.float64)
+        rows = np.concatenate([wt, wt[::-1]])  # (wt: the 24 rows of a hemisphere from the pole; radang runs south to north)
+        self.area = np.repeat(rows[:, None], IX, axis=1) / (2 * IX)
+
+    def _normalised(self, mask, what):
+        import math
+
+        import numpy as np
+        w = np.where(mask, self.area, 0.0)
+        total = math.fsum(w.ravel())
+        if not total > 0.0:
+            raise ValueError("%s holds no grid point" % what)
+        return w / total
+
+    def box(self, lon0, lon1, lat0, lat1):
+        """The quadrature weights of the grid points with lat0 <= lat <= lat1 and longitude from lon0 eastward to lon1 (both ends
+        included; lon0 > lon1 after reduction to [0, 360) crosses the date line of the grid, lon1 - lon0 >= 360 is every
+        longitude), normalised to sum 1: the area mean over the box.  Raises ValueError for a box without a grid point."""
+        import numpy as np
+        if lon1 - lon0 >= 360.0:
+            in_lon = np.ones(IX, dtype=bool)
+        else:
+            a, b = lon0 % 360.0, lon1 % 360.0
+            in_lon = (self.lon >= a) & (self.lon <= b) if a <= b else (self.lon >= a) | (self.lon <= b)
+        in_lat = (self.lat >= lat0) & (self.lat <= lat1)
+        return self._normalised(in_lat[:, None] & in_lon[None, :], "the box lon %g ... %g, lat %g ... %g" % (lon0, lon1, lat0, lat1))
+
+    def band(self, lat0, lat1):
+        """The zonal band lat0 <= lat <= lat1: box(0, 360, lat0, lat1)."""
+        return self.box(0.0, 360.0, lat0, lat1)
+
+    def global_mean(self):
+        """The quadrature weights of the whole sphere, normalised to sum 1: box(0, 360, -90, 90)."""
+        return self.box(0.0, 360.0, -90.0, 90.0)
+
+    def point(self, lon, lat):
+        """The four bilinear weights of the station (lon, lat) in degrees: periodic in longitude, linear in latitude between the
+        two Gaussian rows around it and clamped to the outermost rows beyond them."""
+        import numpy as np
+        x = (lon % 360.0) / 3.75
+        i0 = int(np.floor(x))
+        fx = x - i0
+        i0, i1 = i0 % IX, (i0 + 1) % IX
+        if lat <= self.lat[0]:
+            j0, fy = 0, 0.0
+        elif lat >= self.lat[-1]:
+            j0, fy = IL - 2, 1.0
+        else:
+            j0 = int(np.searchsorted(self.lat, lat, side="right")) - 1
+            fy = (lat - self.lat[j0]) / (self.lat[j0 + 1] - self.lat[j0])
+        w = np.zeros((IL, IX))
+        w[j0, i0] += (1.0 - fx) * (1.0 - fy)
+        w[j0, i1] += fx * (1.0 - fy)
+        w[j0 + 1, i0] += (1.0 - fx) * fy
+        w[j0 + 1, i1] += fx * fy
+        return w
+
+
+def projection_weights(spectral=None):
+    """The builder of weight maps for EnsembleModel.projtape_configure (ProjectionWeights: global_mean, box, band, point), from
+    the library's own tables -- those of `spectral` (a ModSpectral), or the library's device-less copy of the same tables."""
+    return ProjectionWeights(spectral)

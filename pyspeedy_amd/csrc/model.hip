@@ -34,6 +34,7 @@
 #include "nudge.hpp"
 #include "breed.hpp"
 #include "wintape.hpp"
+#include "projtape.hpp"
 #include "ring.hpp"
 #include "stream_apart.hpp"
 #include "surface.hpp"
@@ -351,6 +352,25 @@ struct spd_model {
         void *alloc = nullptr, *data = nullptr;
         WinTapePlane *planes = nullptr;
     } wintape;
+    // The projection tape (spd_model_projtape_*): weighted sums of single planes of the state's grid-space fields under fixed weight
+    // maps -- one double per entry, member and sample.  Sampled by the tape's rule (its own `every`, slab and tables) behind the
+    // window tape's launch.  One allocation of its own (hipMalloc): the ring [slot][M][E] doubles, the patterns [P][4608], slab,
+    // tables, the descriptors of the distinct planes and the entry list sorted by plane (projtape.hpp).  Slots, and the step and
+    // date of each sample: `ring`.
+    struct ProjTape : SampleFront {
+        struct Entry {
+            int name, level, pattern;  // name: catalogue id
+        };
+        bool on = false;
+        int every = 1, npatterns = 0, nplanes = 0;
+        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
+        Validity validity;
+        std::vector<Entry> entries;
+        void *alloc = nullptr;
+        double *data = nullptr, *weights = nullptr;
+        ProjTapePlane *planes = nullptr;
+        ProjTapeItem *items = nullptr;
+    } projtape;
     // Nudging (spd_model_nudge_*): relaxation of the spectral state toward target fields, the one thing in the device loop that
     // WRITES the state.  In the in-loop mode a launch follows the step_range of every member group on the group's stream, in front
     // of the last step's range check and of every recorder (nudge.hip); spd_model_nudge_apply is the same launch once, on the state
@@ -950,6 +970,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->enstape.alloc) (void)hipFree(m->enstape.alloc);
     if (m->acctape.alloc) (void)hipFree(m->acctape.alloc);
     if (m->wintape.alloc) (void)hipFree(m->wintape.alloc);
+    if (m->projtape.alloc) (void)hipFree(m->projtape.alloc);
     if (m->nudge.alloc) (void)hipFree(m->nudge.alloc);
     if (m->breed.alloc) (void)hipFree(m->breed.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
@@ -1509,6 +1530,8 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->wintape.window_start = -1;
     m->wintape.samples = 0;
     m->wintape.validity.clear();
+    m->projtape.ring.clear();  // (... and an empty projection tape)
+    m->projtape.validity.clear();
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1618,6 +1641,7 @@ static hipError_t tape_sample(spd_model *m, int first, int count, long long n, h
 static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_spectra_configure)
 static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s);  // (with spd_model_enstape_configure)
 static hipError_t wintape_step(spd_model *m, int first, int count, int k, int close, int n, int slot, hipStream_t s);  // (with spd_model_wintape_configure)
+static hipError_t projtape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_projtape_configure)
 
 // Nudging: which target the state is relaxed toward when the step counter stands at n -- the slots that bracket n and the weight
 // of the second, a = (n - s0) / (s1 - s0) in fp64.  Before the first stamp the first slot, at or after the last stamp the last
@@ -1771,6 +1795,7 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
     const long long wintape0 = wt.ring.taken;
     const WinOpen win_open0{wt.window_start, wt.samples};
     const WinSchedule win_schedule{wt.window, wt.every, wt.sample_every};
+    const long long projtape0 = m->projtape.ring.taken;  // (the projection tape: every round writes the same slots, for its own members)
     // the ensemble tape's last sample of this call: a sample whose slot a later sample of the SAME call takes again is not folded at
     // all -- nobody can read it, and with rounds its members would otherwise land in the partials of the sample that replaced it
     long long enstape_last = enstape0;
@@ -1779,7 +1804,7 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
     for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
         long long taken = 0, tape_taken = 0, spectra_taken = 0, enstape_taken = 0, acctape_taken = 0;
         int acc_start = acc_start0;
-        long long wintape_taken = 0;
+        long long wintape_taken = 0, projtape_taken = 0;
         WinOpen win_open = win_open0;
         const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
         if (round > 0) {  // the same steps again, for the next members
@@ -1825,8 +1850,11 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
             int32_t win_row[8] = {};
             if (wt.on) win = wintape_advance(win_schedule, win_after, m->current_step + 1, next, win_row);
             const int win_k = win.sample ? win_open.samples + 1 : 0, win_n = win_open.samples + (win.sample ? 1 : 0);
+            const bool record_projtape = m->projtape.on && (m->current_step + 1) % m->projtape.every == 0;
+            if (record_projtape) ++projtape_taken;
             const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip) ||
-                              (fold_enstape && m->enstape.precip) || ac.on || (win.sample && wt.precip)) ? 1 : 0;
+                              (fold_enstape && m->enstape.precip) || ac.on || (win.sample && wt.precip) ||
+                              (record_projtape && m->projtape.precip)) ? 1 : 0;
             // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
             // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
             // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
@@ -1899,6 +1927,9 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
                     check_launch(wintape_step(m, first, count, win_k, win.close ? 1 : 0, win_n, wt.ring.slot(wintape0 + wintape_taken + 1), gs[g]),
                                  "window tape: ");
                 }
+                if (rc == SPD_OK && record_projtape) {  // behind the window tape's launch, on the same stream
+                    check_launch(projtape_sample(m, first, count, projtape0 + projtape_taken, gs[g]), "projection tape: ");
+                }
                 first += count;
             }
             if (rc != SPD_OK) break;
@@ -1920,6 +1951,10 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
             if (round == 0 && record_enstape) {  // (... and for the ensemble tape)
                 m->enstape.ring.taken = enstape0 + enstape_taken;
                 m->enstape.ring.stamp(m->enstape.ring.taken, m->current_step, next);
+            }
+            if (round == 0 && record_projtape) {  // (... and for the projection tape)
+                m->projtape.ring.taken = projtape0 + projtape_taken;
+                m->projtape.ring.stamp(m->projtape.ring.taken, m->current_step, next);
             }
             if (acc_close) {  // the window is closed and the next one starts at the step counter as it stands now
                 ++acctape_taken;
@@ -2031,6 +2066,7 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
         if (m->enstape.on && m->enstape.validity.valid) m->enstape.validity.fail(i, *failed);
         if (m->acctape.on && m->acctape.validity.valid) m->acctape.validity.fail(i, *failed);
         if (m->wintape.on && m->wintape.validity.valid) m->wintape.validity.fail(i, *failed);
+        if (m->projtape.on && m->projtape.validity.valid) m->projtape.validity.fail(i, *failed);
     }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)
@@ -3653,6 +3689,196 @@ int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int fir
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the projection tape: weighted sums of single planes of the state's fields as scalar series (spd_model_projtape_*; kernel: projtape.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kProjMaxPatterns = 64, kProjMaxEntries = 1024;
+const char *const kProjOff = "no projection tape configured (spd_model_projtape_configure)";
+}  // namespace
+
+// the sample of members [first, first + count): the front end into the recorder's own slab, then every entry's sum into ring slot
+// (n - 1) % capacity
+static hipError_t projtape_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
+    const spd_model::ProjTape &pt = m->projtape;
+    const size_t per_slot = static_cast<size_t>(m->M) * pt.entries.size();
+    hipError_t e = sample_front(m, pt, first, count, s);
+    if (e == hipSuccess)
+        e = run_projtape_sample(pt.planes, pt.nplanes, pt.items, pt.weights, pt.slab, pt.slab_fields,
+                                pt.data + static_cast<size_t>(pt.ring.slot(n)) * per_slot, static_cast<int>(pt.entries.size()), first, count,
+                                m->stored32 ? 1 : 0, s);
+    return e;
+}
+
+int spd_model_projtape_configure(spd_model_handle m, const double *weights, int n_patterns, const char *const *names, const int *levels,
+                                 const int *patterns, int n_entries, int every, int capacity) {
+    const char *who = "spd_model_projtape_configure";
+    // (the arguments first, in the header's order: nothing in this block needs the device or a model; n_entries = 0 is "off")
+    std::vector<spd_model::ProjTape::Entry> entries;
+    if (n_entries != 0) {
+        if (every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+        if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+        if (n_patterns < 1 || n_patterns > kProjMaxPatterns)
+            return m_fail(SPD_E_ARG, std::string(who) + ": n_patterns must be 1 ... " + std::to_string(kProjMaxPatterns) + ", got " +
+                                         std::to_string(n_patterns));
+        if (n_entries < 0 || n_entries > kProjMaxEntries)
+            return m_fail(SPD_E_ARG, std::string(who) + ": n_entries must be 0 ... " + std::to_string(kProjMaxEntries) + ", got " +
+                                         std::to_string(n_entries));
+        if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
+        if (!names || !levels || !patterns) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
+        for (int p = 0; p < n_patterns; ++p)
+            for (int q = 0; q < NG; ++q)
+                if (!std::isfinite(weights[static_cast<size_t>(p) * NG + q]))
+                    return m_fail(SPD_E_ARG, std::string(who) + ": weight of pattern " + std::to_string(p) + " at point " + std::to_string(q) +
+                                                 " (row " + std::to_string(q / IX) + ", column " + std::to_string(q % IX) + ") is not finite");
+        for (int k = 0; k < n_entries; ++k) {
+            const int id = names[k] ? stats_id(names[k]) : -1;
+            if (id < 0)
+                return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
+                                             "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
+                                             "q_plev, z_plev, mslp)");
+            entries.push_back({id, levels[k], patterns[k]});
+        }
+        // (a level is checked here against the name's fixed count; a pressure-level name's count is the model's, below)
+        for (int k = 0; k < n_entries; ++k) {
+            const int fixed = kStatsCatalogue[entries[k].name].levels;
+            if (levels[k] < 0 || (fixed > 0 && levels[k] >= fixed))
+                return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
+                                             names[k] + "') is out of range" + (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
+            if (patterns[k] < 0 || patterns[k] >= n_patterns)
+                return m_fail(SPD_E_ARG, std::string(who) + ": pattern " + std::to_string(patterns[k]) + " of entry " + std::to_string(k) + " ('" +
+                                             names[k] + "') is out of range (0 ... " + std::to_string(n_patterns - 1) + ")");
+        }
+    }
+    if (int rc = configure_allowed(m, who)) return rc;
+    for (int k = 0; k < n_entries; ++k) {
+        if (entries[k].name < kPlevFirst) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
+        if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+        if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
+            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
+                                         names[k] + "') is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
+    }
+    spd_model::ProjTape &pt = m->projtape;
+    if (int rc = retire(m, pt)) return rc;
+    if (n_entries == 0) return SPD_OK;  // off
+    spd_model::ProjTape next;
+    next.every = every;
+    next.npatterns = n_patterns;
+    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity), E = static_cast<size_t>(n_entries);
+    // the sample plan: the names among the entries in the order they first appear (the front end transforms a name's every level)
+    std::vector<int> ids;
+    for (const auto &e : entries)
+        if (std::find(ids.begin(), ids.end(), e.name) == ids.end()) ids.push_back(e.name);
+    SamplePlan plan;
+    plan_sample(m, ids, next, plan);
+    // the distinct planes in the order they first appear, and the entries sorted by plane (stable: the caller's order within a plane)
+    std::vector<std::pair<int, int>> distinct;  // (name, level)
+    std::vector<int> plane_of(E);
+    for (size_t k = 0; k < E; ++k) {
+        const std::pair<int, int> key{entries[k].name, entries[k].level};
+        const auto at = std::find(distinct.begin(), distinct.end(), key);
+        plane_of[k] = static_cast<int>(at - distinct.begin());
+        if (at == distinct.end()) distinct.push_back(key);
+    }
+    // one allocation: ring | patterns | slab | tables[2] | plane descriptors | entry list
+    const size_t per_slot = M * E * sizeof(double);
+    if (slots > (static_cast<size_t>(-1) / 2) / per_slot) return m_fail(SPD_E_ARG, std::string(who) + ": the size of the series does not fit size_t");
+    const size_t ring = sample_up(slots * per_slot), maps = sample_up(static_cast<size_t>(n_patterns) * NG * sizeof(double));
+    const size_t desc = sample_up(distinct.size() * sizeof(ProjTapePlane)), list = sample_up(E * sizeof(ProjTapeItem));
+    const size_t total = ring + maps + plan.slab_bytes + 2 * plan.table_bytes + desc + list;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the projection tape is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the projection tape (" + std::to_string(total) +
+                                        " bytes asked for: " + std::to_string(capacity) + " samples of " + std::to_string(per_slot) +
+                                        " bytes); the projection tape is off");
+    }
+    Carve carve{static_cast<char *>(p)};
+    next.alloc = p;
+    next.data = carve.take<double>(ring);
+    next.weights = carve.take<double>(maps);
+    carve_front(carve, plan, next);
+    next.planes = carve.take<ProjTapePlane>(desc);
+    next.items = carve.take<ProjTapeItem>(list);
+    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
+    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<ProjTapePlane> host_planes;
+    std::vector<ProjTapeItem> host_items;
+    for (size_t q = 0; q < distinct.size(); ++q) {
+        const int id = distinct[q].first, level = distinct[q].second;
+        const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
+        ProjTapePlane d{};
+        d.slab_plane = slab_plane[var->first_plane + static_cast<size_t>(level)];
+        d.src = id == 6 ? static_cast<const void *>(m->pa.precnv) : id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
+        d.unit = kStatsCatalogue[id].unit;
+        d.first = static_cast<int>(host_items.size());
+        for (size_t k = 0; k < E; ++k)
+            if (plane_of[k] == static_cast<int>(q)) host_items.push_back({entries[k].pattern, static_cast<int>(k)});
+        d.count = static_cast<int>(host_items.size()) - d.first;
+        host_planes.push_back(d);
+    }
+    if (e == hipSuccess) e = hipMemcpy(next.weights, weights, static_cast<size_t>(n_patterns) * NG * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(ProjTapePlane), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.items, host_items.data(), host_items.size() * sizeof(ProjTapeItem), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return upload_failed(who, e, p);
+    next.nplanes = static_cast<int>(host_planes.size());
+    next.entries = std::move(entries);
+    next.ring = SampleRing(capacity, 6);
+    next.on = true;
+    pt = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_projtape_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: null model");
+    if (!m->projtape.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_reset: ") + kProjOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: a checked multi-step call is in flight; end it first");
+    m->projtape.ring.clear();
+    m->projtape.validity.clear();
+    return SPD_OK;
+}
+
+int spd_model_projtape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *n_patterns, int *n_entries) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_info: null model");
+    const spd_model::ProjTape &pt = m->projtape;
+    if (!pt.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_info: ") + kProjOff);
+    if (taken) *taken = pt.ring.taken;
+    if (held) *held = static_cast<int>(pt.ring.held());
+    if (capacity) *capacity = pt.ring.capacity;
+    if (every) *every = pt.every;
+    if (n_patterns) *n_patterns = pt.npatterns;
+    if (n_entries) *n_entries = static_cast<int>(pt.entries.size());
+    return SPD_OK;
+}
+
+int spd_model_projtape_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_times: null model");
+    const spd_model::ProjTape &pt = m->projtape;
+    if (!pt.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_times: ") + kProjOff);
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_projtape_times: bad destination");
+    return pt.ring.copy_rows(rows, max_rows);
+}
+
+int spd_model_projtape_read(spd_model_handle m, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_projtape_read";
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    const spd_model::ProjTape &pt = m->projtape;
+    if (int rc = read_allowed(m, who, pt.on, kProjOff, pt.validity, "the projection tape is invalid until spd_model_projtape_reset")) return rc;
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    if (int rc = held_range(who, pt.ring, t0, nt, "sample")) return rc;
+    const size_t per = pt.entries.size();
+    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
+    if (count == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    // (the ring is [slot][M][E] as a spectra ring is [slot][M][per]: the same gather)
+    const hipError_t e = run_spectra_gather(pt.data + static_cast<size_t>(first) * per, static_cast<double *>(dst_device), static_cast<int>(per),
+                                            static_cast<long>(static_cast<size_t>(m->M) * per), count, nt, pt.ring.slot_of_held(t0),
+                                            pt.ring.capacity, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // nudging: relaxation of the spectral state toward target fields (spd_model_nudge_*; kernel: nudge.hip; step loop: step_impl)
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
@@ -4093,6 +4319,9 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
     if (m->wintape.on && m->wintape.plev.mask)
         return m_fail(SPD_E_ARG, std::string(who) + ": the window tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_wintape_configure)");
+    if (m->projtape.on && m->projtape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the projection tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_projtape_configure)");
     spd_model::Plev &pl = m->plev;
     pl.n = n;
     for (int j = 0; j < kPlevMaxLevels; ++j) {

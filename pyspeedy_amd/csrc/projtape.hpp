@@ -1,0 +1,37 @@
+// The projection tape: weighted sums of the state's grid-space fields -- box and band means, global means, station values, any
+// fixed linear functional of one plane -- formed behind the sampled steps of the device loop and kept as scalar time series in a
+// ring in device memory (projtape.hip holds the kernel, model.hip the schedule, the configuration and the C ABI:
+// spd_model_projtape_* of include/pyspeedy_amd.h; the definition is DESIGN section 4j).
+//
+// Definition.  P weight maps w (fp64 [48][96], the layout of one level of a tape sample, shared by all members) and E entries
+// (name, level, pattern).  x[p], p = 96 j + i, is what an fp64 tape of that name holds at that level after the sampled step, in
+// export units.  The result of an entry is one double per member and sample, summed in this order, every product and every sum
+// rounded on its own (no contraction):
+//   lane t of 256:   s_t = w[t] * x[t];  for r = 1 ... 17 in that order  s_t = s_t + w[t + 256 r] * x[t + 256 r]
+//   tree[t] = s_t;   for half = 128, 64, ..., 1:  tree[t] = tree[t] + tree[t + half]  for t < half;   result = tree[0]
+// All 4608 = 18 * 256 terms take part; a zero weight is not skipped.  tests/projtape_reference.py restates it in numpy.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace spd {
+
+// One distinct plane (a level of a name) among the entries, as the kernel sees it.
+struct ProjTapePlane {
+    const void *src;  // physics output of member 0 (slab_plane < 0: precnv / precls, float while the model stores fp32)
+    int slab_plane;   // plane inside a member's slab entries (-1: read `src` directly)
+    int unit;         // 0 as it is, 1 q (kg/kg), 2 phi (m), 3 ps (Pa) -- export_unit.hpp, as TapePlane::unit
+    int first, count; // its entries: items [first, first + count) of the list below
+};
+
+// One entry, in the list sorted by plane: the pattern it projects onto and its column in a member's row of the ring.
+struct ProjTapeItem {
+    int pattern, column;
+};
+
+// One launch for the members [first, first + count), all planes.  weights: [P][4608]; slab: [M][slab_fields][4608] fp64, as the
+// front end left it; store32: the model keeps precnv / precls as float; ring_slot: member 0 of the sample's slot, [M][n_entries].
+hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const ProjTapeItem *items, const double *weights,
+                               const double *slab, int slab_fields, double *ring_slot, int n_entries, int first, int count,
+                               int store32, hipStream_t s);
+
+}  // namespace spd

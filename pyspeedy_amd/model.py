@@ -683,6 +683,81 @@ class EnsembleModel:
                   "spd_model_wintape_read(%s, %s)" % (name, op))
         return out
 
+    # ---- the projection tape: weighted sums of fields as scalar series (spd_model_projtape_*, include/pyspeedy_amd.h) --------
+    def projtape_configure(self, weights, entries, every, capacity):
+        """Record scalar series taken from grid-space fields inside run() / run_checked() calls of any length.  `weights` is
+        array-like [P][48][96] (1 <= P <= 64, finite), weight maps in the layout of one level of a tape sample
+        (pyspeedy_amd.projection_weights builds global means, boxes, bands and station stencils); `entries` is a list of
+        (name, level, pattern): name any of STATS_VARIABLES (the pressure-level ones after plev_configure), level a 0-based level
+        of that name, pattern an index into `weights`.  After every step that leaves current_step at a multiple of `every`, each
+        entry's sum over the 4608 points of weight times the value a float64 tape holds is formed on the device in a fixed,
+        documented order and kept for every member in a ring of the last `capacity` samples.  Empties the
+        ring; an empty list switches the recorder off and frees it.  Synchronises the device."""
+        rows = []
+        for entry in entries:
+            if len(entry) != 3:
+                raise ValueError("an entry is (name, level, pattern), got %r" % (entry,))
+            rows.append((str(entry[0]), int(entry[1]), int(entry[2])))
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if rows and (w.ndim != 3 or w.shape[1:] != (48, 96)):
+            raise ValueError("weights must be [P][48][96], got shape %r" % (w.shape,))
+        n = max(len(rows), 1)
+        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
+        levels = (C.c_int * n)(*[r[1] for r in rows])
+        patterns = (C.c_int * n)(*[r[2] for r in rows])
+        with torch.cuda.device(self.sp.device):
+            rc = self._lib.spd_model_projtape_configure(self._m, w.ctypes.data_as(C.POINTER(C.c_double)), w.shape[0] if rows else 0, names,
+                                                        levels, patterns, len(rows), int(every), int(capacity))
+        if rc != 0:
+            text = (self._lib.spd_last_error() or b"?").decode()
+            if self._lib.spd_model_projtape_info(self._m, None, None, None, None, None, None) != 0:
+                self._projtape_entries = ()  # (refused behind the point where the earlier configuration went)
+            raise _lib.SpeedyHipError("spd_model_projtape_configure failed (%d): %s" % (rc, text))
+        self._projtape_entries = tuple(rows)
+
+    def projtape_reset(self):
+        """Empty the projection tape (no device work); the next sample is the first."""
+        check(self._lib.spd_model_projtape_reset(self._m), "spd_model_projtape_reset")
+
+    @property
+    def projtape_info(self):
+        """dict(taken, held, capacity, every, patterns, entries): samples since the last reset, samples the ring holds (min(taken,
+        capacity)), and the configuration."""
+        taken, held, capacity, every, patterns, entries = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.spd_model_projtape_info(self._m, C.byref(taken), C.byref(held), C.byref(capacity), C.byref(every),
+                                                C.byref(patterns), C.byref(entries)), "spd_model_projtape_info")
+        return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, patterns=patterns.value,
+                    entries=entries.value)
+
+    @property
+    def projtape_entries(self):
+        """The configured entries, a tuple of (name, level, pattern) in the order of the last axis of projtape() (empty: off)."""
+        return getattr(self, "_projtape_entries", ())
+
+    def _projtape_rows(self):
+        return self._ring_rows("spd_model_projtape_times", self.projtape_info["held"], 6)
+
+    def projtape_steps(self):
+        """The model's step counter after each held sample's step, oldest first (numpy int array)."""
+        return self._row_steps(self._projtape_rows())
+
+    def projtape_times(self):
+        """The date of each held sample's state, oldest first (a list of datetime)."""
+        return self._row_times(self._projtape_rows())
+
+    def projtape(self, first=0, count=None, t0=0, nt=None):
+        """Members [first, first + count) and samples [t0, t0 + nt) of the held ones (oldest first) of every entry: a float64
+        tensor [count][nt][E] on the model's device, E in the order of projtape_entries."""
+        first, count = self._range(first, count)
+        info = self.projtape_info
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        out = torch.empty((count, max(nt, 0), info["entries"]), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_projtape_read(self._m, first, count, t0, nt, C.c_void_p(out.data_ptr()), out.numel() * 8,
+                                                    self._stream()), "spd_model_projtape_read")
+        return out
+
     # ---- nudging: relaxation of the spectral state toward target fields (spd_model_nudge_*, include/pyspeedy_amd.h) ---------
     NUDGE_NAMES = ("vor", "div", "t", "tr", "ps")
 

@@ -1,5 +1,5 @@
 // The accumulation tape: window sums, means and extremes of the column physics' 2-D outputs, accumulated behind every step of the
-// device loop and closed into a ring in device memory (acctape.hip holds the kernel, model.hip the configuration and the C ABI:
+// device loop and closed into a ring in device memory (acctape.hip holds the kernel, the configuration and the C ABI:
 // spd_model_acctape_* of include/pyspeedy_amd.h; the definition is DESIGN section 4f).
 #pragma once
 #include <hip/hip_runtime.h>

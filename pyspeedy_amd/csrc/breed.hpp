@@ -1,8 +1,10 @@
 // Breeding: the perturbation of a bred member against its control run is rescaled to a fixed amplitude, inside the device loop
-// or once on the state as it stands (breed.hip holds the kernels, model.hip the schedule, the configuration and the C ABI:
+// or once on the state as it stands (breed.hip holds the kernels, the schedule, the configuration and the C ABI:
 // spd_model_breed_* of include/pyspeedy_amd.h; the definition is DESIGN section 4i).
 #pragma once
 #include <hip/hip_runtime.h>
+
+struct spd_model;
 
 namespace spd {
 
@@ -22,19 +24,9 @@ struct BreedPair {
     int member, control;
 };
 
-// The norm launch for the bred members pairs[0 ... nbred): partial[b][plane] = E(plane) of the difference X_p - X_c on time level 1,
-// summed over the 527 coefficients with m + n <= 31 in an order that depends on nothing but the plane.
-hipError_t run_breed_norm(const BreedPlane *planes, const BreedPair *pairs, int nbred, const double *elm2, double *partial, hipStream_t s);
-
-// The rescale launch behind it.  Every workgroup sums its member's 33 weighted partials in ascending plane order:
-//   A = sqrt(sum weight[plane] * partial[b][plane]),  s = target / A  (s = 1 and the member left alone if A is zero or not finite)
-// and then X_p' = X_c + s * (X_p - X_c) on both time levels for the coefficients with m + n <= 31, each operation rounded on its
-// own.  amplitude / factor: [M] of the ring slot, written at the member's index; either may be null.
-hipError_t run_breed_rescale(const BreedPlane *planes, const BreedPair *pairs, int nbred, const double *partial, double target,
-                             double *amplitude, double *factor, hipStream_t s);
-
-// Amplitudes only, behind run_breed_norm: out[i] = A of member i, 0.0 for a member that is not bred (slot_of[i] < 0: its index in
-// pairs otherwise).  Writes nothing else.
-hipError_t run_breed_amplitude(const BreedPlane *planes, const int *slot_of, int members, const double *partial, double *out, hipStream_t s);
+// The rescale of all bred members on the state as it stands, on stream s: the norm launch, the rescale launch behind it and one
+// slot of the ring.  For the step loop at the end of a segment (model.hip: step_impl) and for spd_model_breed_apply; `who` opens
+// the error text.
+int breed_rescale(spd_model *m, hipStream_t s, const char *who);
 
 }  // namespace spd

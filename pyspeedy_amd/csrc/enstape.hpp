@@ -1,6 +1,6 @@
 // The ensemble tape: a ring in device memory of the last samples of the ensemble mean and of the sum of squared deviations from it
 // (M2) over all members of a model, per grid point, fp64, recorded by the device loop of a multi-step call (enstape.hip holds the
-// kernels, model.hip the configuration and the C ABI: spd_model_enstape_* of include/pyspeedy_amd.h; the definition is DESIGN
+// kernels, the configuration and the C ABI: spd_model_enstape_* of include/pyspeedy_amd.h; the definition is DESIGN
 // section 4e).
 //
 // Members reach a sample in pieces: member groups on up to kEnsTapeGroups concurrent streams, and rounds of block_members one
@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+
+struct spd_model;
 
 namespace spd {
 
@@ -32,16 +34,8 @@ struct EnsTapeCounts {
     int n[kEnsTapeReadSamples][kEnsTapeGroups];
 };
 
-// Fold the sample of the members [first, first + count), in member order, into the partial `partial` (= slot * 4 + group) of every
-// plane: one launch.  n0: members the partial already holds (0: nothing of it is read).  slab: [M][slab_fields][4608] fp64;
-// store32: the physics outputs are stored as fp32.
-hipError_t run_enstape_fold(const EnsTapePlane *planes, int nplanes, const double *slab, int slab_fields, int first, int count,
-                            int partial, int n0, int store32, hipStream_t s);
-// Merge the partials of the samples [0, nt) of one variable (sample t of the read lies in slot (slot0 + t) % capacity; counts: per
-// sample and group, in the read's order) into dst[nt][per] doubles (per = levels * 4608): kind 0 the mean, 1 the unbiased standard
-// deviation sqrt(M2 / (n - 1)) (one member: NaN), 2 M2.  mean / m2: the variable's first plane in partial (slot 0, group 0);
-// nplanes: planes of all variables (the stride between partials is nplanes * 4608 doubles).
-hipError_t run_enstape_read(const double *mean, const double *m2, long per, int nplanes, int kind, int nt, int slot0, int capacity,
-                            const int *counts, double *dst, hipStream_t s);
+// The step loop's sample of the members [first, first + count), number n since the last reset, folded into partial `group` of its
+// slot behind the step just issued on `s`.
+hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s);
 
 }  // namespace spd

@@ -1,6 +1,6 @@
 // The export units of a sampled value, with export_units_kernel's fp32 literals: what the statistics (stats.hip), the tape
 // (tape.hip) and the ensemble tape (enstape.hip) apply to a slab value before they use it.  One function, so that the three hold
-// the same bits.  unit: 0 as it is, 1 q (kg/kg), 2 phi (m), 3 ps (Pa) -- kStatsCatalogue's `unit` (model.hip).
+// the same bits.  unit: 0 as it is, 1 q (kg/kg), 2 phi (m), 3 ps (Pa) -- kStatsCatalogue's `unit` (model_state.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,7 @@
 // Ensemble model object: device-resident state of M members + the step driver (time_stepping.f90:38-147 `step`,
 // tendencies.f90:11-39 `get_tendencies`) built from the hot-path kernels and the dynamics kernels.
-// C ABI: the spd_model_* functions of include/pyspeedy_amd.h.
+// C ABI: the spd_model_* functions of include/pyspeedy_amd.h, but for those of the in-loop features (statistics, tapes, spectra,
+// nudging, breeding, pressure levels), which lie with their kernels in the feature's own file; model_state.hpp is what they share.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -17,27 +18,13 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/pyspeedy_amd.h"
-#include "context.hpp"
-#include "model.hpp"
+#include "model_state.hpp"
 #include "coupler_point.hpp"
 #include "diagnostics_block.hpp"
 #include "bounded_call.hpp"
 #include "launch_events.hpp"
 #include "sppt_point.hpp"
-#include "plev.hpp"
-#include "stats.hpp"
-#include "spectra.hpp"
-#include "tape.hpp"
-#include "enstape.hpp"
-#include "acctape.hpp"
-#include "nudge.hpp"
-#include "breed.hpp"
-#include "wintape.hpp"
-#include "projtape.hpp"
-#include "ring.hpp"
 #include "stream_apart.hpp"
-#include "surface.hpp"
 
 namespace spd {
 hipError_t run_spec2grid_table(const DeviceTables &T, const FieldDesc *table, int nfields, hipStream_t st);
@@ -86,402 +73,12 @@ hipError_t run_vel2vort(const DeviceTables &T, const double *ucos, const double 
 hipError_t run_export_spec_units(double *tr, double *phi, long ncomplex, hipStream_t s);
 }  // namespace spd
 
-using namespace spd;
-
-namespace {
-constexpr int NG = IX * IL;
-constexpr size_t C = 2;  // doubles per complex
-
-struct RegEntry {
-    void *ptr;            // device base
-    size_t bytes_member;  // bytes per member (as fp64: the size the registry and the C boundary speak of)
-    bool f32 = false;     // stored as fp32 (in the first half of the allocation) while the model's physics precision is fp32
-};
-}  // namespace
-
-struct spd_model {
-    spd_context *ctx = nullptr;
-    int M = 0;
-    ModelPtrs P{};
-    const spd_dyn_tables *dyn = nullptr;            // the context's tables of the current time step (nullptr: none set yet)
-    std::unique_ptr<spd_dyn_tables> dyn_private;    // only when the context already holds kMaxDynSteps other time steps
-    DynDeviceTables D{};
-    spd_physics_args pa{};
-    // Device memory of the model: a few large zero-filled blocks the arrays are carved from (arena_alloc).  A model has some 170
-    // arrays and tables; one hipMalloc + hipMemset + hipFree each made creating and closing a state container the most
-    // expensive calls of a host that follows the reference's sequence (1.3 ms and 1.8 ms per one-member model).
-    struct Block {
-        char *base;
-        size_t size, used;
-    };
-    std::vector<Block> blocks;
-    std::map<std::string, RegEntry> reg;
-    FieldDesc *inv_table[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [dynamics time level j2 (0-based)][phi buffer]
-    FieldDesc *inv_table_sppt[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // the same + 8 SPPT pattern transforms per member
-    // ... and both with the physics-only outputs (time-level-1 T, q, phi, ln ps, lowest-level u, v) stored as fp32 (cfg 5)
-    FieldDesc *inv_table32[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *inv_table_sppt32[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    FieldDesc *fwd_table = nullptr;
-    // Geopotential, double-buffered.  spectral_step_kernel ends by computing the geopotential the NEXT step needs (from the
-    // temperature it has just advanced) into the buffer that is not in use; the next step switches to it instead of running
-    // geopotential_kernel.  The registry's "phi" is always the buffer the last step USED (the reference's state%phi after a
-    // step).  phi_ahead is dropped whenever something outside the step may have changed the temperature.
-    double *phi_buf[2] = {nullptr, nullptr};
-    int phi_cur = 0;
-    // fold_geo: on by default for small ensembles (<= 8 members), where the step is bound by launch and dependent-latency
-    // chains and one launch less is worth 1-3 %; at 64 members the longer spectral_step_kernel costs 2 % more than the
-    // geopotential launch it saves (A/B in one session, profiles/).  PYSPEEDY_AMD_FOLD_GEO=0 / 1 overrides.
-    bool phi_ahead = false, fold_geo = true;
-    bool groups_apart = true;  // every group stream created so far was measured to run side by side with the others
-    int *d_err = nullptr;
-    double *d_diag = nullptr;
-    // The quiet rim: one flag per member, armed and established by the device inside a multi-step call (step_impl) and valid in
-    // that call only.  rim_call: the last call of spd_model_step / _step_checked_begin used the flags (option "quiet_rim_members").
-    int *d_rim = nullptr;
-    bool rim_call = false;
-    // asynchronous range check (spd_model_check_begin / _end): two pinned result slots with their events
-    int *h_err[2] = {nullptr, nullptr}, *h_err_sync = nullptr;  // (h_err_sync: pinned staging of the synchronous check)
-    hipEvent_t err_event[2] = {nullptr, nullptr};
-    int next_slot = 0;
-    bool slot_busy[2] = {false, false};  // begun and not yet ended
-    int check_ticket = 0, slot_ticket[2] = {0, 0};  // every range-check launch publishes its codes under a ticket of its own
-    // A check whose launch is put off until the next step (spd_model_check_defer): it then rides in that step's spectral -> grid
-    // launch.  Launched on its own as soon as anything else would look at or change the state first (settle_deferred_check).
-    struct DeferredCheck {
-        bool active = false;
-        int slot = -1, time_level = 2;
-        hipStream_t stream = nullptr;
-    } deferred;
-    hipStream_t slot_stream[2] = {nullptr, nullptr};  // the stream a slot's launch went out on
-    bool slot_rode[2] = {false, false};               // ... inside a step's launch (no completion event of its own)
-    int checks_alone = 0, checks_rode = 0;            // range checks launched on their own / carried by a step's launch
-    double air_absortivity_co2 = 6.0;  // model_state_def.py:320 default
-    // device copies of the dt-dependent tables (re-uploaded by set_time_step)
-    // surface / coupler state, calendar and run control (do_single_step, speedy.f90:20-74)
-    SurfacePtrs S{};
-    Calendar cal;
-    int current_step = 0;
-    bool initialized = false;
-    // SPPT (csrc/sppt.hip): AR(1) spectral pattern [M][8][992] complex, its grid-space image [M][8][NG]
-    bool sppt_on = false, sppt_first = true;
-    unsigned long long sppt_seed = 0;
-    long long sppt_member_base = 0, sppt_step = 0;
-    double *sppt_spec = nullptr, *sppt_grid = nullptr;
-    // Members are stepped in `nchunks` groups on separate HIP streams (spd_model_step): a group's kernels overlap with
-    // the other groups' (different kernels, complementary resources, no idle tail between dependent launches).
-    // spectral -> grid transforms per member and step: 77 = the reference's 91 minus the 14 whose results nothing reads (u, v
-    // above the lowest level at the physics' time level: physics.f90:93-94 computes them, get_surface_fluxes only uses level
-    // kx; every registry variable stays bitwise identical, tests/test_run_gpu.py).  PYSPEEDY_AMD_PRUNE_DEAD=0 restores all 91.
-    int inv_per_member = 77;
-    int nchunks = 1;
-    // Large ensembles in multi-step calls: from 4 x `block_members` members up, spd_model_step(m, n) takes the members in ROUNDS of
-    // nchunks x block_members -- a round through ALL n steps before the next round starts (members never exchange data).  A group's
-    // spectral step is then followed on its stream by the spectral -> grid launch of its own next step, which reads what was just
-    // written while it is still in the 256 MB Infinity Cache, as in a 64-member ensemble; with 128 members per group it is not,
-    // and a member-step costs 5-10 % more (profiles/r05_members_per_gpu.txt).  The host-side state of the step (calendar, step
-    // counter, geopotential buffer, SPPT counter, CO2) is rewound for every round.  0: off (PYSPEEDY_AMD_BLOCK_MEMBERS, option
-    // "block_members").
-    int block_members = 32;
-    hipStream_t cstream[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr}, ev_start = nullptr, ev_offset = nullptr;
-    bool split_dyn_physics = false;  // PYSPEEDY_AMD_SPLIT_DYN=1: separate dynamics and physics launches (for measurements)
-    // spd_model_set_physics_precision (BASELINE cfg 5): column physics arithmetic in fp32 AND fp32 storage of what only the
-    // column physics reads back (RegEntry::f32: its time-level-1 inputs, the persisted radiation state, diagnostics-only outputs)
-    int phys_fp32 = 0;
-    bool phys_store32 = true;  // option physics_storage32 / PYSPEEDY_AMD_PHYS_STORE32: 0 keeps fp64 storage under the fp32 physics
-    bool stored32 = false;     // how the RegEntry::f32 arrays are stored right now (= phys_fp32 && phys_store32)
-    // A change of that storage converts the arrays in place, one by one; a device error in the middle leaves some of them
-    // converted and `stored32` unable to say which.  The model then refuses every call that would read or advance its state.
-    std::string poisoned;
-    // ... and a device error in the middle of a step (some launches of it out, others not; or one member group a step ahead of
-    // another): the STATE is then inconsistent, not the storage -- spd_model_init, which rebuilds every array from the boundary
-    // fields, makes the model usable again; nothing else does.
-    std::string step_poison;
-    int fail_launch_after = -1;  // fault injection for tests (option "fail_launch_after"): the n-th step_range of the next call fails
-    // spd_model_step_checked_begin / _end: the range check of EVERY step of a multi-step call, recorded by the device into pinned
-    // host memory [steps][M] (4 * ticket + flag, as the single checks do) by check blocks that ride in the next step's
-    // spectral -> grid launch; the last step's check is a launch of its own behind the call.
-    int *h_steps_err = nullptr;
-    int steps_cap = 0, steps_pending = 0, steps_ticket = 0;
-    hipEvent_t steps_event = nullptr;
-    std::vector<int32_t> steps_accepted;  // [steps + 1][7]: step counter, y, m, d, h, min, month_idx before the call and after each step
-    // Dead-store elimination inside multi-step calls (PYSPEEDY_AMD_DIAG_EVERY_STEP=1 switches it off): only the LAST step
-    // of a spd_model_step call stores the physics outputs that no later kernel reads -- the host can only look at the
-    // state between calls, and every earlier value would be overwritten before that.
-    bool diag_every_step = false;
-    // The coupler's climatology interpolation is valid for a day (surface.hip): true after a coupling, false after anything
-    // wrote to the state from outside the step
-    bool surf_cache_valid = false;
-    int spectral_early = -1;  // spectral_step_kernel with all loads up front: -1 = for launches of up to 8 members, 0 / 1 = never / always
-    int land_coupling_flag = 1, sst_anomaly_flag = 1, increase_co2 = 0, anom_planes = 3;
-    double ablco2_ref = 6.0;
-    double *corh_t = nullptr, *corh_q = nullptr, *scratch_spec = nullptr;  // [M][NG], [M][NG], [2][M][992] complex
-    double *orog = nullptr, *phi0 = nullptr, *fmask_orig = nullptr, *veg_high = nullptr, *veg_low = nullptr,
-           *soil_wc_l1 = nullptr, *soil_wc_l2 = nullptr, *soil_wc_l3 = nullptr, *bmask_land = nullptr, *bmask_sea = nullptr;
-    // optional profiling with HIP events on the launch stream: level 1 brackets the dominant kernel (the spec2grid table
-    // launch) only, level 2 every kernel of the step (spd_model_profile; kernel ids SPD_K_* of pyspeedy_amd.h)
-    int profile = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-    std::vector<int> prof_fields;  // fields of each profiled launch
-    std::vector<int> prof_kernel;  // kernel id of each profiled launch
-    size_t prof_used = 0;
-    // grid-space copies of the prognostic variables in output units (prognostics.f90:125-219) and their transform tables
-    double *u_grid = nullptr, *v_grid = nullptr, *t_grid = nullptr, *q_grid = nullptr, *phi_grid = nullptr, *ps_grid = nullptr;
-    FieldDesc *exp_inv_table[2] = {nullptr, nullptr}, *exp_fwd_table[2] = {nullptr, nullptr};  // 41 / 40 per member; [phi buffer]
-    // What the front end of a sample (statistics or tape) runs and where it writes: vort2vel when u or v is wanted, the export
-    // transforms over a descriptor table ([phi buffer]) whose destinations are the slab [M][slab_fields][4608], and the
-    // pressure-level kernel (raw = 1) from the slab's transformed planes into its further planes.  The statistics, the tape
-    // and the ensemble tape each own one, in their own allocation.
-    struct SampleFront {
-        bool uv = false, precip = false;
-        // slab_fields: planes of a member in the slab; the first xf_fields of them are written by the export transforms, the
-        // others (pressure-level variables only) by the pressure-level kernel from those
-        int slab_fields = 0, xf_fields = 0;
-        PlevArgs plev{};  // (plev.mask != 0: a pressure-level variable is sampled)
-        double *slab = nullptr;
-        FieldDesc *table[2] = {nullptr, nullptr};
-    };
-    // Running time statistics (spd_model_stats_*): sampled by the step loop after every step that ends on a multiple of `every`,
-    // behind each member group's last launch of that step on the group's stream.  One allocation (own hipMalloc, not the arena:
-    // a reconfiguration frees it): the accumulators [variable][M][levels][4608] (mean, and M2 with variance), the sample slab
-    // [M][slab_fields][4608] the export transforms write instead of the registry's grid arrays, their descriptor tables
-    // ([phi buffer]) and the plane descriptors of the accumulate kernel.
-    struct Stats : SampleFront {
-        struct Var {
-            int id, levels;
-            size_t offset;  // doubles from `mean` / `m2` to member 0 of the variable
-        };
-        bool on = false, variance = false;
-        int every = 1, nplanes = 0;
-        long long samples = 0;
-        Validity validity;
-        std::vector<Var> vars;
-        void *alloc = nullptr;
-        double *mean = nullptr, *m2 = nullptr;
-        StatsPlane *planes = nullptr;
-    } stats;
-    // The tape (spd_model_tape_*): a ring of the last `capacity` samples of chosen fields, taken where the statistics take theirs
-    // (its own `every`, slab and tables).  One allocation of its own (hipMalloc): the ring, per variable [slot][M][levels][4608] in
-    // `dtype`, then slab, tables and the plane descriptors of the store kernel.  Slots, and the step and date of each sample: `ring`
-    // (ring.hpp).
-    struct Tape : SampleFront {
-        struct Var {
-            int id, levels;
-            size_t offset;  // elements from `data` to slot 0, member 0 of the variable
-        };
-        bool on = false;
-        int every = 1, dtype = 0, nplanes = 0;
-        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
-        Validity validity;
-        std::vector<Var> vars;
-        void *alloc = nullptr, *data = nullptr;
-        TapePlane *planes = nullptr;
-    } tape;
-    // Spectra and global means of the spectral state (spd_model_spectra_*): a ring of the last `capacity` samples of the chosen
-    // names, fp64, written by one launch per member group and sample behind the tape's (no transform, no slab: spectra.hip).  One
-    // allocation of its own (hipMalloc): per name [slot][M][per] doubles.  Slots, and the step and date of each sample: `ring`.
-    struct Spectra {
-        bool on = false;
-        int every = 1;
-        unsigned mask = 0;
-        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
-        Validity validity;
-        void *alloc = nullptr;
-        size_t offset[SPECTRA_NNAMES] = {};  // doubles from `alloc` to slot 0, member 0 of a name of the mask
-    } spectra;
-    // The ensemble tape (spd_model_enstape_*): a ring of the last `capacity` samples of the mean over all members and of the sum of
-    // squared deviations from it (M2), per grid point, fp64, taken by the tape's rule (its own `every`, slab and tables) behind the
-    // spectra's sample.  One allocation of its own (hipMalloc): mean and M2 rings, each [slot][4][planes][4608] -- one partial per
-    // group stream, written only from that stream (enstape.hpp) --, then slab, tables and the plane descriptors of the fold kernel.
-    // Slots, and the step and date of each sample: `ring`; the members already folded into each partial of a slot (`counts`) are
-    // kept on the host at issue time as well.
-    struct EnsTape : SampleFront {
-        struct Var {
-            int id, levels;
-            size_t first_plane;  // planes of the variables before this one
-        };
-        bool on = false;
-        int every = 1, nplanes = 0;
-        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
-        Validity validity;
-        std::vector<Var> vars;
-        std::vector<int> counts;  // [capacity][4]: members folded into partial (slot, group)
-        void *alloc = nullptr;
-        double *mean = nullptr, *m2 = nullptr;
-        EnsTapePlane *planes = nullptr;
-    } enstape;
-    // The accumulation tape (spd_model_acctape_*): window sums, means, minima and maxima of the column physics' 2-D outputs.  An
-    // accumulate launch follows EVERY step while it is on (acctape.hip); a window closes by the tape's rule into the slot of
-    // `ring`, which counts the windows closed since the last reset.  No front end: the values are read where the column
-    // kernel stores them.  One allocation of its own (hipMalloc): ring (per entry [slot][M][planes][4608], float or double), the
-    // fp64 accumulators some entry needs ([M][planes][4608] each), the plane descriptors.  The step the open window started at and
-    // the rows of the closed ones (step, date, number of steps) are host state.
-    struct AccTape {
-        struct Entry {
-            int name, op, planes;
-            size_t offset;  // elements from `data` to slot 0, member 0 of the entry
-        };
-        bool on = false;
-        int every = 1, dtype = SPD_TAPE_F32, nplanes = 0;
-        int window_start = -1;  // absolute step counter the open window began at (-1: at the next step that runs)
-        SampleRing ring;        // of closed windows; rows [7]: step after the window, year, month, day, hour, minute of that state, steps in it
-        Validity validity;
-        std::vector<Entry> entries;
-        void *alloc = nullptr, *data = nullptr;
-        AccTapePlane *planes = nullptr;
-    } acctape;
-    // The window tape (spd_model_wintape_*): window sums, means, extremes and threshold counts of the state's grid-space fields.
-    // The tape's front end (its own slab and tables) and an accumulate launch follow every step that samples (the tape's rule
-    // with `sample_every`); a window closes every `every` steps, at midnight or at month ends (wintape_advance) into the slot of
-    // `ring`, which counts the windows closed since the last reset; a closing step that does not sample launches the
-    // kernel alone.  One allocation of its own (hipMalloc): ring (per entry [slot][M][levels][4608], float or double), the fp64
-    // accumulators some entry needs ([M][levels][4608] each), slab, tables, plane descriptors.  The step the open window started
-    // at, its samples so far and the rows of the closed ones are host state.
-    struct WinTape : SampleFront {
-        struct Entry {
-            int name, op, levels;  // name: catalogue id, 14 wspd_grid, 15 wspd_plev
-            double threshold;
-            size_t offset;  // elements from `data` to slot 0, member 0 of the entry
-        };
-        bool on = false;
-        int window = SPD_WINDOW_STEPS, every = 1, sample_every = 1, dtype = SPD_TAPE_F32, nplanes = 0;
-        int window_start = -1;  // absolute step counter the open window began at (-1: at the next step that runs)
-        int samples = 0;        // samples the open window holds
-        SampleRing ring;        // of closed windows; rows [8]: step after the window, year, month, day, hour, minute, samples, steps
-        Validity validity;
-        std::vector<Entry> entries;
-        void *alloc = nullptr, *data = nullptr;
-        WinTapePlane *planes = nullptr;
-    } wintape;
-    // The projection tape (spd_model_projtape_*): weighted sums of single planes of the state's grid-space fields under fixed weight
-    // maps -- one double per entry, member and sample.  Sampled by the tape's rule (its own `every`, slab and tables) behind the
-    // window tape's launch.  One allocation of its own (hipMalloc): the ring [slot][M][E] doubles, the patterns [P][4608], slab,
-    // tables, the descriptors of the distinct planes and the entry list sorted by plane (projtape.hpp).  Slots, and the step and
-    // date of each sample: `ring`.
-    struct ProjTape : SampleFront {
-        struct Entry {
-            int name, level, pattern;  // name: catalogue id
-        };
-        bool on = false;
-        int every = 1, npatterns = 0, nplanes = 0;
-        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
-        Validity validity;
-        std::vector<Entry> entries;
-        void *alloc = nullptr;
-        double *data = nullptr, *weights = nullptr;
-        ProjTapePlane *planes = nullptr;
-        ProjTapeItem *items = nullptr;
-    } projtape;
-    // Nudging (spd_model_nudge_*): relaxation of the spectral state toward target fields, the one thing in the device loop that
-    // WRITES the state.  In the in-loop mode a launch follows the step_range of every member group on the group's stream, in front
-    // of the last step's range check and of every recorder (nudge.hip); spd_model_nudge_apply is the same launch once, on the state
-    // as it stands.  One allocation of its own (hipMalloc): the target slots (per name [capacity][levels][992] complex128, shared by
-    // all members, zero-filled), the gain rows and descriptors of the planes some gain of which is not zero, and the member mask.
-    // The slots in use and their absolute step stamps are host state: the bracketing slots and the interpolation weight of a
-    // step travel by value.
-    struct Nudge {
-        bool on = false, in_loop = false;
-        int capacity = 0, in_use = 0, nplanes = 0;
-        long long applied = 0;       // steps nudged so far: in-loop steps and calls of _apply that launched
-        std::vector<int> names;      // 0 vor, 1 div, 2 t, 3 tr, 4 ps, in the caller's order
-        std::vector<int> stamps;     // [in_use], strictly ascending
-        size_t offset[5] = {};       // doubles from `targets` to slot 0 of a name
-        void *alloc = nullptr;
-        double *targets = nullptr;
-        int *mask = nullptr;         // [M] on the device, or null: every member is nudged
-        NudgePlane *planes = nullptr;
-        bool loops() const { return on && in_loop && nplanes > 0; }  // a launch follows every step of spd_model_step
-    } nudge;
-    // Breeding (spd_model_breed_*): the perturbation of a bred member against its control is rescaled to `target` after every step
-    // that leaves the step counter at a multiple of `every` (breed.hip).  The one operation that couples members across member
-    // groups and rounds: a call with in-loop breeding is issued as segments that end at the rescale steps (step_impl), and the two
-    // launches go out on the caller's stream behind the join of the group streams.  One allocation of its own (hipMalloc): the
-    // plane descriptors with their weights, the compact list of (member, control), each member's index in that list, the partial
-    // norms [bred][33] and the ring [capacity][2][M] of amplitudes and factors (`data`).  Slots, steps and dates of the events: `ring`.
-    struct Breed {
-        bool on = false, in_loop = false;
-        int every = 0, nbred = 0;
-        double target = 0.0;
-        SampleRing ring;        // of events since _configure / _reset; rows [6]: step counter, y, m, d, h, min of an event's state
-        long long applied = 0;  // rescales launched since _configure: in-loop ones and calls of _apply
-        void *alloc = nullptr;
-        BreedPlane *planes = nullptr;
-        BreedPair *pairs = nullptr;
-        int *slot_of = nullptr;
-        double *partial = nullptr, *data = nullptr;
-        bool loops() const { return on && in_loop && nbred > 0; }  // spd_model_step is issued in segments
-    } breed;
-    // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
-    // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
-    struct Plev {
-        int n = 0;
-        double levels[kPlevMaxLevels] = {}, lnp[kPlevMaxLevels] = {};
-        double *out[PLEV_NVARS] = {};
-        int cap[PLEV_NVARS] = {};     // levels the allocation holds
-        bool have[PLEV_NVARS] = {};   // computed since the levels were configured
-    } plev;
-};
-
-// The window tape's schedule: the ONE place that decides whether a step samples and whether it closes the open window, for the step
-// loop (step_impl) and for spd_wintape_plan alike.
-namespace {
-struct WinSchedule {
-    int window, every, sample_every;
-};
-struct WinOpen {
-    int start, samples;  // the step counter the open window began at; the samples it holds
-};
-struct WinDecision {
-    bool sample, close;
-};
-// The step that leaves the counter at `step_after` and the date at `next`: a sample goes into the open window first; a closing
-// step then fills row[8] (spd_model_wintape_times) and opens the next window at step_after.
-WinDecision wintape_advance(const WinSchedule &s, WinOpen &w, int step_after, const spd::Calendar &next, int32_t *row) {
-    WinDecision d;
-    d.sample = step_after % s.sample_every == 0;
-    const bool midnight = next.hour == 0 && next.minute == 0;
-    d.close = s.window == SPD_WINDOW_STEPS ? step_after % s.every == 0 : s.window == SPD_WINDOW_DAY ? midnight : midnight && next.day == 1;
-    if (d.sample) ++w.samples;
-    if (d.close) {
-        stamp_row(row, step_after, next);
-        row[6] = w.samples;
-        row[7] = step_after - w.start;
-        w.start = step_after;
-        w.samples = 0;
-    }
-    return d;
-}
-}  // namespace
-
 namespace spd {
 LaunchEvents &pending_launch_events() {
     static thread_local LaunchEvents ev;
     return ev;
 }
 }  // namespace spd
-
-static int m_fail(int code, const std::string &msg) { return spd_set_error(code, msg); }
-static int usable(const spd_model *m, const char *who, bool about_to_init = false) {
-    if (!m->poisoned.empty()) return m_fail(SPD_E_DEVICE, std::string(who) + ": this model is unusable: " + m->poisoned);
-    if (!about_to_init && !m->step_poison.empty())
-        return m_fail(SPD_E_ARG, std::string(who) + ": this model is unusable until it is initialised again (spd_model_init): " + m->step_poison);
-    return SPD_OK;
-}
-static int apply_storage(spd_model *m, bool want32);  // (with spd_model_set_physics_precision)
-static int settle_deferred_check(spd_model *m);        // (with spd_model_check_defer)
-static int ensure_group_streams(spd_model *m, int G);  // (with spd_model_step)
-static int ensure_steps_record(spd_model *m, int nsteps);
-
-// (A failed runtime call also leaves its code behind as the thread's "last error", and the launch wrappers of the kernels report
-// hipGetLastError(): a hipMalloc that ran out of memory would come back as the "failure" of the next launch of an unrelated model.
-// The code is reported HERE, once, and cleared.)
-#define M_HIP(call)                                                                   \
-    do {                                                                              \
-        hipError_t e_ = (call);                                                       \
-        if (e_ != hipSuccess) {                                                       \
-            (void)hipGetLastError();                                                  \
-            return m_fail(SPD_E_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-        }                                                                             \
-    } while (0)
 
 // `bytes` of zero-filled device memory that lives as long as the model.  Every array starts on a 256-byte boundary.  The first
 // block is sized for everything spd_model_create asks for (18.5 MB per member); whatever comes later -- SST anomalies of a
@@ -515,7 +112,7 @@ static int arena_alloc(spd_model *m, size_t bytes, void **out) {
     return SPD_OK;
 }
 
-static int dalloc(spd_model *m, size_t doubles, double **out, const char *name = nullptr, size_t bytes_member = 0) {
+int spd::dalloc(spd_model *m, size_t doubles, double **out, const char *name, size_t bytes_member) {
     void *p = nullptr;
     if (int rc = arena_alloc(m, doubles * sizeof(double), &p)) return rc;
     *out = static_cast<double *>(p);
@@ -680,41 +277,137 @@ static int build_tables(spd_model *m) {
     return batch.upload(m);
 }
 
-// ---- the in-loop features (statistics, tapes, spectra, nudging, breeding): what every _configure does around its own work.  (Here
-// and not beside the features: a template cannot stand inside the extern "C" block below.)
-namespace {
-// A _configure call, behind its argument checks: the model is there, usable and not inside a checked call ...
-int configure_allowed(const spd_model *m, const char *who) {
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    return SPD_OK;
-}
-// ... and, behind the checks that need the model: the feature as it was configured goes.  It is OFF before anything can fail --
-// here or in the caller below -- so that no later step samples into, or reads, memory whose state is unknown.
-template <class Feature>
-int retire(spd_model *m, Feature &f) {
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipDeviceSynchronize());  // (steps in flight may still use the allocation this one replaces)
-    void *old = f.alloc;
-    f = Feature{};
-    if (old) M_HIP(hipFree(old));
+// ---- the layout of a sample's front end, shared by the statistics and the tape (spd_model::SampleFront) ----
+namespace spd {
+// the list of names of a _configure call -> catalogue ids (the arguments first: nothing here needs the device or a model)
+int sample_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
+    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
+    for (int k = 0; k < n_names; ++k) {
+        const int id = names[k] ? stats_id(names[k]) : -1;
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
+                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
+                                         "q_plev, z_plev, mslp)");
+        if (std::find(ids.begin(), ids.end(), id) != ids.end())
+            return m_fail(SPD_E_ARG, std::string(who) + ": variable '" + names[k] + "' named twice");
+        ids.push_back(id);
+    }
     return SPD_OK;
 }
 
-constexpr size_t kSampleAlign = 256;
-size_t sample_up(size_t b) { return (b + kSampleAlign - 1) / kSampleAlign * kSampleAlign; }
-// the parts of a feature's one allocation, one behind the other, each starting on a kSampleAlign boundary
-struct Carve {
-    char *at;
-    template <class T>
-    T *take(size_t bytes) {
-        T *part = reinterpret_cast<T *>(at);
-        at += sample_up(bytes);
-        return part;
+// the variables `ids` of the model's M members: which planes the slab holds (front.uv, precip, xf_fields, slab_fields, plev.mask)
+// and how large slab and tables are
+void plan_sample(const spd_model *m, const std::vector<int> &ids, spd_model::SampleFront &front, SamplePlan &plan) {
+    int needs = 0, plev_planes = 0;
+    auto levels_of = [&](int id) { return id >= kPlevFirst && id != kPlevFirst + PLEV_MSLP ? m->plev.n : kStatsCatalogue[id].levels; };
+    for (int id : ids) {
+        plan.vars.push_back({id, levels_of(id), plan.planes});
+        plan.planes += static_cast<size_t>(levels_of(id));
+        if (id < 6) plan.xf.push_back(id);
+        front.precip = front.precip || id == 6 || id == 7;
+        if (id >= kPlevFirst) {
+            front.plev.mask |= 1 << (id - kPlevFirst);
+            needs |= kPlevNeeds[id - kPlevFirst];
+            plev_planes += levels_of(id);
+        }
     }
-};
-}  // namespace
+    for (int id = 0; id < 6; ++id)
+        if ((needs >> id & 1) && std::find(plan.xf.begin(), plan.xf.end(), id) == plan.xf.end()) plan.xf.push_back(id);
+    for (int id : plan.xf) {
+        plan.xf_at[id] = front.xf_fields;
+        front.xf_fields += kStatsCatalogue[id].levels;
+        front.uv = front.uv || id < 2;
+    }
+    front.slab_fields = front.xf_fields + plev_planes;
+    const size_t M = static_cast<size_t>(m->M);
+    plan.slab_bytes = sample_up(M * front.slab_fields * NG * sizeof(double));
+    plan.table_bytes = sample_up(M * front.xf_fields * sizeof(FieldDesc));
+}
+
+// front.slab and front.table[] point into the caller's allocation: uploads the export descriptors of spd_model_spectral2grid
+// (build_tables) with the slab as destination, for the chosen variables, and sets up the pressure-level kernel of a sample (from
+// the slab's transformed planes into its further planes).  slab_plane: per plane of plan.vars, in their order, the slab plane the
+// value is read from (-1: precnv / precls, read where the column kernel stores them).
+hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_model::SampleFront &front, std::vector<int> &slab_plane) {
+    const size_t M = static_cast<size_t>(m->M);
+    const ModelPtrs &P = m->P;
+    auto spec = [](double *base, size_t field) { return base + field * NSPEC * C; };
+    const size_t half = M * 16;
+    std::vector<FieldDesc> host_table[2];
+    for (int par = 0; par < 2; ++par) {
+        host_table[par].reserve(M * front.xf_fields);
+        for (size_t i = 0; i < M; ++i) {
+            const size_t w = i * 8, s1 = i * 16;
+            size_t j = 0;
+            for (const int id : plan.xf) {
+                for (int k = 0; k < kStatsCatalogue[id].levels; ++k, ++j) {
+                    double *dst = front.slab + (i * front.slab_fields + j) * NG;
+                    switch (id) {
+                        case 0: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
+                        case 1: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
+                        case 2: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
+                        case 3: host_table[par].push_back({spec(P.tr, s1 + k), dst, 1, 0}); break;
+                        case 4: host_table[par].push_back({spec(m->phi_buf[par], w + k), dst, 1, 0}); break;
+                        default: host_table[par].push_back({spec(P.ps, i * 2), dst, 1, 0}); break;
+                    }
+                }
+            }
+        }
+    }
+    int plev_plane = front.xf_fields;
+    if (front.plev.mask) {
+        PlevArgs &a = front.plev;
+        const long stride = static_cast<long>(front.slab_fields) * NG;
+        for (int x = 0; x < 5; ++x) {
+            a.in[x] = plan.xf_at[x] >= 0 ? front.slab + static_cast<size_t>(plan.xf_at[x]) * NG : nullptr;
+            a.in_stride[x] = stride;
+        }
+        a.ps = front.slab + static_cast<size_t>(plan.xf_at[5]) * NG;
+        a.ps_stride = stride;
+        a.phis0 = m->pa.phis0;
+        a.raw = 1;
+        a.n = m->plev.n;
+        std::copy(m->plev.lnp, m->plev.lnp + kPlevMaxLevels, a.lnp);
+    }
+    slab_plane.clear();
+    for (const auto &v : plan.vars)
+        for (int k = 0; k < v.levels; ++k) {
+            if (v.id < 6) slab_plane.push_back(plan.xf_at[v.id] + k);
+            else if (v.id >= kPlevFirst) {
+                if (k == 0) {
+                    front.plev.out[v.id - kPlevFirst] = front.slab + static_cast<size_t>(plev_plane) * NG;
+                    front.plev.out_stride[v.id - kPlevFirst] = static_cast<long>(front.slab_fields) * NG;
+                }
+                slab_plane.push_back(plev_plane++);
+            } else slab_plane.push_back(-1);
+        }
+    hipError_t e = hipSuccess;
+    if (front.xf_fields > 0) {
+        e = hipMemcpy(front.table[0], host_table[0].data(), host_table[0].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(front.table[1], host_table[1].data(), host_table[1].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
+    }
+    return e;
+}
+
+// the front end of a sample of members [first, first + count) after the step just issued on `s`: what spd_model_spectral2grid
+// would leave in the grid arrays (the same vort2vel into sv, the same transforms), into the slab; then the pressure-level planes
+hipError_t sample_front(spd_model *m, const spd_model::SampleFront &f, int first, int count, hipStream_t s) {
+    const DeviceTables &T = m->ctx->dev;
+    const size_t S = NSPEC * C, half = static_cast<size_t>(m->M) * 16, off = static_cast<size_t>(first) * 16;
+    hipError_t e = hipSuccess;
+    if (f.uv) e = run_vort2vel(T, m->P.vor + off * S, m->P.div + off * S, m->P.sv + off * S, m->P.sv + (half + off) * S, count * 16, s);
+    if (e == hipSuccess && f.xf_fields > 0)
+        e = run_spec2grid_table(T, f.table[m->phi_cur] + static_cast<size_t>(first) * f.xf_fields, count * f.xf_fields, s);
+    if (e == hipSuccess && f.plev.mask) {  // slab -> further slab planes, in export units
+        PlevArgs a = f.plev;
+        a.first = first;
+        e = run_plev(a, count, s);
+    }
+    return e;
+}
+}  // namespace spd
+
 
 extern "C" {
 
@@ -1375,14 +1068,18 @@ static int launch_check(spd_model *m, int slot, int time_level, hipStream_t s, c
     return SPD_OK;
 }
 
+}  // extern "C"
+
 // A deferred check that has not found a step to ride in is launched on its own, now, on the stream it was deferred on.  Called
 // by everything that is about to read or change what the check looks at in another way than the next step of that stream does.
-static int settle_deferred_check(spd_model *m) {
+int spd::settle_deferred_check(spd_model *m) {
     if (!m->deferred.active) return SPD_OK;
     m->deferred.active = false;
     M_HIP(hipSetDevice(m->ctx->device));
     return launch_check(m, m->deferred.slot, m->deferred.time_level, m->deferred.stream, "deferred range check");
 }
+
+extern "C" {
 
 int spd_model_check_begin(spd_model_handle m, int time_level, void *stream) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_check_begin: null model");
@@ -1636,29 +1333,6 @@ static int ensure_group_streams(spd_model *m, int G) {
 // diagnostics.f90 is available separately through spd_model_check (the reference runs it after every step).
 // record: the range check of every step is left in m->h_steps_err[step][member] (spd_model_step_checked_begin) -- the check of step
 // k rides in the spectral -> grid launch of step k + 1 of the same members, the last one is a launch of its own behind the call.
-static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_stats_configure)
-static hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);   // (with spd_model_tape_configure)
-static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_spectra_configure)
-static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s);  // (with spd_model_enstape_configure)
-static hipError_t wintape_step(spd_model *m, int first, int count, int k, int close, int n, int slot, hipStream_t s);  // (with spd_model_wintape_configure)
-static hipError_t projtape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);  // (with spd_model_projtape_configure)
-
-// Nudging: which target the state is relaxed toward when the step counter stands at n -- the slots that bracket n and the weight
-// of the second, a = (n - s0) / (s1 - s0) in fp64.  Before the first stamp the first slot, at or after the last stamp the last
-// one, at a slot's own stamp that slot: s1 == s0 then, and the kernel takes T = T0 without the interpolation line.
-struct NudgeAt {
-    int s0, s1;
-    double a;
-};
-static NudgeAt nudge_at(const std::vector<int> &stamps, int n) {
-    const int last = static_cast<int>(stamps.size()) - 1;
-    if (n <= stamps[0]) return {0, 0, 0.0};
-    if (n >= stamps[last]) return {last, last, 0.0};
-    const int hi = static_cast<int>(std::upper_bound(stamps.begin(), stamps.end(), n) - stamps.begin()), lo = hi - 1;
-    if (n == stamps[lo]) return {lo, lo, 0.0};
-    return {lo, hi, static_cast<double>(static_cast<long long>(n) - stamps[lo]) / static_cast<double>(static_cast<long long>(stamps[hi]) - stamps[lo])};
-}
-
 // One segment of a call: `nsteps` steps for all members, all rounds and member groups, forked from and joined into the caller's
 // stream.  A call without in-loop breeding is one segment (row0 = 0, rows = nsteps); with it, step_impl issues the segments between
 // the rescale steps, and the rows of a checked call (h_steps_err, steps_accepted) of this segment start at row0 of the call's `rows`.
@@ -1992,8 +1666,6 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
     return rc;
 }
 
-static int breed_rescale(spd_model *m, hipStream_t s, const char *who);  // (with spd_model_breed_configure)
-
 // A call of spd_model_step / spd_model_step_checked_begin.  Without in-loop breeding: one segment, the launches it always issued.
 // With it, the control of a bred member may lie in another member group or another round, so the call is cut at the steps that
 // leave the step counter at a multiple of `every`: all rounds and groups finish a segment and join the caller's stream (no host
@@ -2223,53 +1895,6 @@ int spd_model_get_config(spd_model_handle m, int32_t *cfg) {
     return SPD_OK;
 }
 
-int spd_model_get_option(spd_model_handle m, const char *name, int32_t *value) {
-    if (!m || !name || !value) return m_fail(SPD_E_ARG, "spd_model_get_option: null argument");
-    const std::string key(name);
-    if (key == "diag_every_step") *value = m->diag_every_step ? 1 : 0;
-    else if (key == "split_dyn") *value = m->split_dyn_physics ? 1 : 0;
-    else if (key == "spectral_early") *value = m->spectral_early;
-    else if (key == "member_groups") *value = m->nchunks;
-    else if (key == "block_members") *value = m->block_members;
-    else if (key == "physics_storage32") *value = m->phys_store32 ? 1 : 0;
-    else if (key == "quiet_rim_members") {
-        // members whose rim the last multi-step call found quiet (step_impl); -1 when the last call did not look (one step, or
-        // launches that fold the geopotential).  Waits for the device: the call's streams were joined into the caller's.
-        *value = -1;
-        if (m->rim_call) {
-            std::vector<int> flags(static_cast<size_t>(m->M));
-            M_HIP(hipDeviceSynchronize());
-            M_HIP(hipMemcpy(flags.data(), m->d_rim, sizeof(int) * flags.size(), hipMemcpyDeviceToHost));
-            *value = 0;
-            for (int f : flags) *value += f != 0 ? 1 : 0;
-        }
-    }
-    else return m_fail(SPD_E_ARG, "spd_model_get_option: unknown option: " + key);
-    return SPD_OK;
-}
-
-int spd_model_set_option(spd_model_handle m, const char *name, int32_t value) {
-    if (!m || !name) return m_fail(SPD_E_ARG, "spd_model_set_option: null argument");
-    const std::string key(name);
-    const bool flag = value == 0 || value == 1;
-    if (key == "diag_every_step" && flag) m->diag_every_step = value != 0;
-    else if (key == "split_dyn" && flag) m->split_dyn_physics = value != 0;
-    else if (key == "spectral_early" && value >= -1 && value <= 1) m->spectral_early = value;
-    else if (key == "member_groups" && value >= 1 && value <= 4) m->nchunks = value < m->M ? value : m->M;
-    else if (key == "block_members" && value >= 0) m->block_members = value;
-    else if (key == "fail_launch_after" && value >= -1) m->fail_launch_after = value;  // (fault injection: tests)
-    else if (key == "prepare_multi_step" && value == 1) {  // what multi-step calls need once per model, now instead of at the first one
-        if (int rc = ensure_steps_record(m, 360)) return rc;  // (a stretch of the facade's time loops is at most 360 steps long)
-        if (m->nchunks > 1 && !m->split_dyn_physics) return ensure_group_streams(m, m->nchunks);
-    }
-    else if (key == "physics_storage32" && flag) {
-        m->phys_store32 = value != 0;
-        return apply_storage(m, m->phys_fp32 && m->phys_store32);
-    }
-    else return m_fail(SPD_E_ARG, "spd_model_set_option: unknown option or value out of range: " + key);
-    return SPD_OK;
-}
-
 // bring the storage of the RegEntry::f32 arrays in line with what the model's settings ask for
 static int apply_storage(spd_model *m, bool want32) {
     if (want32 == m->stored32) return SPD_OK;
@@ -2317,6 +1942,53 @@ int spd_model_set_physics_precision(spd_model_handle m, int fp32) {
     return apply_storage(m, m->phys_fp32 && m->phys_store32);
 }
 
+int spd_model_get_option(spd_model_handle m, const char *name, int32_t *value) {
+    if (!m || !name || !value) return m_fail(SPD_E_ARG, "spd_model_get_option: null argument");
+    const std::string key(name);
+    if (key == "diag_every_step") *value = m->diag_every_step ? 1 : 0;
+    else if (key == "split_dyn") *value = m->split_dyn_physics ? 1 : 0;
+    else if (key == "spectral_early") *value = m->spectral_early;
+    else if (key == "member_groups") *value = m->nchunks;
+    else if (key == "block_members") *value = m->block_members;
+    else if (key == "physics_storage32") *value = m->phys_store32 ? 1 : 0;
+    else if (key == "quiet_rim_members") {
+        // members whose rim the last multi-step call found quiet (step_impl); -1 when the last call did not look (one step, or
+        // launches that fold the geopotential).  Waits for the device: the call's streams were joined into the caller's.
+        *value = -1;
+        if (m->rim_call) {
+            std::vector<int> flags(static_cast<size_t>(m->M));
+            M_HIP(hipDeviceSynchronize());
+            M_HIP(hipMemcpy(flags.data(), m->d_rim, sizeof(int) * flags.size(), hipMemcpyDeviceToHost));
+            *value = 0;
+            for (int f : flags) *value += f != 0 ? 1 : 0;
+        }
+    }
+    else return m_fail(SPD_E_ARG, "spd_model_get_option: unknown option: " + key);
+    return SPD_OK;
+}
+
+int spd_model_set_option(spd_model_handle m, const char *name, int32_t value) {
+    if (!m || !name) return m_fail(SPD_E_ARG, "spd_model_set_option: null argument");
+    const std::string key(name);
+    const bool flag = value == 0 || value == 1;
+    if (key == "diag_every_step" && flag) m->diag_every_step = value != 0;
+    else if (key == "split_dyn" && flag) m->split_dyn_physics = value != 0;
+    else if (key == "spectral_early" && value >= -1 && value <= 1) m->spectral_early = value;
+    else if (key == "member_groups" && value >= 1 && value <= 4) m->nchunks = value < m->M ? value : m->M;
+    else if (key == "block_members" && value >= 0) m->block_members = value;
+    else if (key == "fail_launch_after" && value >= -1) m->fail_launch_after = value;  // (fault injection: tests)
+    else if (key == "prepare_multi_step" && value == 1) {  // what multi-step calls need once per model, now instead of at the first one
+        if (int rc = ensure_steps_record(m, 360)) return rc;  // (a stretch of the facade's time loops is at most 360 steps long)
+        if (m->nchunks > 1 && !m->split_dyn_physics) return ensure_group_streams(m, m->nchunks);
+    }
+    else if (key == "physics_storage32" && flag) {
+        m->phys_store32 = value != 0;
+        return apply_storage(m, m->phys_fp32 && m->phys_store32);
+    }
+    else return m_fail(SPD_E_ARG, "spd_model_set_option: unknown option or value out of range: " + key);
+    return SPD_OK;
+}
+
 int spd_model_set_flags(spd_model_handle m, int land_coupling_flag, int sst_anomaly_coupling_flag, int increase_co2) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_set_flags: null model");
     m->land_coupling_flag = land_coupling_flag ? 1 : 0;
@@ -2329,12 +2001,6 @@ int spd_model_set_flags(spd_model_handle m, int land_coupling_flag, int sst_anom
 // ---------------------------------------------------------------------------------------------------------------
 // grid-space views of the prognostic state (prognostics.f90:125-219) for members [first, first + count)
 // ---------------------------------------------------------------------------------------------------------------
-static int member_range(spd_model_handle m, int first, int count, const char *who) {
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    return usable(m, who);
-}
-
 // One grid-space registry variable ((ix, il) or (ix, il, kx) per member) of the members [first, first + count) as a NetCDF-3
 // file carries it: float32, BIG-endian, levels bottom-up -- into `dst_device` (count * levels * 4608 * 4 bytes), on `stream`.
 // For hosts that write files: what crosses PCIe afterwards is the file's payload itself.
@@ -2435,1974 +2101,6 @@ int spd_model_set_sppt(spd_model_handle m, int on, uint64_t seed, int64_t first_
     m->sppt_member_base = first_member_id;
     m->sppt_first = true;
     m->sppt_step = 0;
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// time-mean statistics sampled inside multi-step calls (spd_model_stats_*; kernels: stats.hip)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-struct StatsCatalogueEntry {
-    const char *name;
-    int levels, unit;  // unit: as StatsPlane::unit
-};
-// ids 0 ... 5: from the spectral state through the export transforms; 6, 7: the column kernel's precipitation outputs;
-// 8 ... 13: the pressure-level variables (kPlevFirst + PlevVar; levels: the configured target levels, mslp one), written into the
-// slab in export units by the pressure-level kernel
-constexpr StatsCatalogueEntry kStatsCatalogue[] = {{"u_grid", KX, 0},   {"v_grid", KX, 0}, {"t_grid", KX, 0}, {"q_grid", KX, 1},
-                                                   {"phi_grid", KX, 2}, {"ps_grid", 1, 3}, {"precnv", 1, 0}, {"precls", 1, 0},
-                                                   {"u_plev", 0, 0},    {"v_plev", 0, 0},  {"t_plev", 0, 0}, {"q_plev", 0, 0},
-                                                   {"z_plev", 0, 0},    {"mslp", 1, 0}};
-constexpr int kPlevFirst = 8;
-// sigma-level inputs (catalogue ids 0 ... 5, as bits) of each pressure-level variable: ps always; T with Z (both extrapolations)
-constexpr int kPlevNeeds[PLEV_NVARS] = {1 << 0 | 1 << 5, 1 << 1 | 1 << 5, 1 << 2 | 1 << 5, 1 << 3 | 1 << 5, 1 << 2 | 1 << 4 | 1 << 5,
-                                        1 << 2 | 1 << 5};
-constexpr int kStatsCatalogueSize = sizeof(kStatsCatalogue) / sizeof(kStatsCatalogue[0]);
-static int stats_id(const char *name) {
-    for (int v = 0; v < kStatsCatalogueSize; ++v)
-        if (std::strcmp(name, kStatsCatalogue[v].name) == 0) return v;
-    return -1;
-}
-}  // namespace
-
-// ---- the layout of a sample's front end, shared by the statistics and the tape (spd_model::SampleFront) ----
-namespace {
-// the list of names of a _configure call -> catalogue ids (the arguments first: nothing here needs the device or a model)
-int sample_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
-    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
-    for (int k = 0; k < n_names; ++k) {
-        const int id = names[k] ? stats_id(names[k]) : -1;
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                         "q_plev, z_plev, mslp)");
-        if (std::find(ids.begin(), ids.end(), id) != ids.end())
-            return m_fail(SPD_E_ARG, std::string(who) + ": variable '" + names[k] + "' named twice");
-        ids.push_back(id);
-    }
-    return SPD_OK;
-}
-
-struct SamplePlan {
-    struct Var {
-        int id, levels;
-        size_t first_plane;  // planes of the variables before this one (of one member)
-    };
-    std::vector<Var> vars;
-    // what the export transforms write into the slab, in slab order: the sigma-level variables asked for, then those only a
-    // pressure-level variable needs; xf_at[id]: first slab plane of variable id (-1: not transformed)
-    std::vector<int> xf;
-    int xf_at[6] = {-1, -1, -1, -1, -1, -1};
-    size_t planes = 0;                        // planes of all variables of one member
-    size_t slab_bytes = 0, table_bytes = 0;   // of the slab and of ONE descriptor table, rounded up to kSampleAlign
-};
-
-// the variables `ids` of the model's M members: which planes the slab holds (front.uv, precip, xf_fields, slab_fields, plev.mask)
-// and how large slab and tables are
-void plan_sample(const spd_model *m, const std::vector<int> &ids, spd_model::SampleFront &front, SamplePlan &plan) {
-    int needs = 0, plev_planes = 0;
-    auto levels_of = [&](int id) { return id >= kPlevFirst && id != kPlevFirst + PLEV_MSLP ? m->plev.n : kStatsCatalogue[id].levels; };
-    for (int id : ids) {
-        plan.vars.push_back({id, levels_of(id), plan.planes});
-        plan.planes += static_cast<size_t>(levels_of(id));
-        if (id < 6) plan.xf.push_back(id);
-        front.precip = front.precip || id == 6 || id == 7;
-        if (id >= kPlevFirst) {
-            front.plev.mask |= 1 << (id - kPlevFirst);
-            needs |= kPlevNeeds[id - kPlevFirst];
-            plev_planes += levels_of(id);
-        }
-    }
-    for (int id = 0; id < 6; ++id)
-        if ((needs >> id & 1) && std::find(plan.xf.begin(), plan.xf.end(), id) == plan.xf.end()) plan.xf.push_back(id);
-    for (int id : plan.xf) {
-        plan.xf_at[id] = front.xf_fields;
-        front.xf_fields += kStatsCatalogue[id].levels;
-        front.uv = front.uv || id < 2;
-    }
-    front.slab_fields = front.xf_fields + plev_planes;
-    const size_t M = static_cast<size_t>(m->M);
-    plan.slab_bytes = sample_up(M * front.slab_fields * NG * sizeof(double));
-    plan.table_bytes = sample_up(M * front.xf_fields * sizeof(FieldDesc));
-}
-
-// front.slab and front.table[] point into the caller's allocation: uploads the export descriptors of spd_model_spectral2grid
-// (build_tables) with the slab as destination, for the chosen variables, and sets up the pressure-level kernel of a sample (from
-// the slab's transformed planes into its further planes).  slab_plane: per plane of plan.vars, in their order, the slab plane the
-// value is read from (-1: precnv / precls, read where the column kernel stores them).
-hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_model::SampleFront &front, std::vector<int> &slab_plane) {
-    const size_t M = static_cast<size_t>(m->M);
-    const ModelPtrs &P = m->P;
-    auto spec = [](double *base, size_t field) { return base + field * NSPEC * C; };
-    const size_t half = M * 16;
-    std::vector<FieldDesc> host_table[2];
-    for (int par = 0; par < 2; ++par) {
-        host_table[par].reserve(M * front.xf_fields);
-        for (size_t i = 0; i < M; ++i) {
-            const size_t w = i * 8, s1 = i * 16;
-            size_t j = 0;
-            for (const int id : plan.xf) {
-                for (int k = 0; k < kStatsCatalogue[id].levels; ++k, ++j) {
-                    double *dst = front.slab + (i * front.slab_fields + j) * NG;
-                    switch (id) {
-                        case 0: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
-                        case 1: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
-                        case 2: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
-                        case 3: host_table[par].push_back({spec(P.tr, s1 + k), dst, 1, 0}); break;
-                        case 4: host_table[par].push_back({spec(m->phi_buf[par], w + k), dst, 1, 0}); break;
-                        default: host_table[par].push_back({spec(P.ps, i * 2), dst, 1, 0}); break;
-                    }
-                }
-            }
-        }
-    }
-    int plev_plane = front.xf_fields;
-    if (front.plev.mask) {
-        PlevArgs &a = front.plev;
-        const long stride = static_cast<long>(front.slab_fields) * NG;
-        for (int x = 0; x < 5; ++x) {
-            a.in[x] = plan.xf_at[x] >= 0 ? front.slab + static_cast<size_t>(plan.xf_at[x]) * NG : nullptr;
-            a.in_stride[x] = stride;
-        }
-        a.ps = front.slab + static_cast<size_t>(plan.xf_at[5]) * NG;
-        a.ps_stride = stride;
-        a.phis0 = m->pa.phis0;
-        a.raw = 1;
-        a.n = m->plev.n;
-        std::copy(m->plev.lnp, m->plev.lnp + kPlevMaxLevels, a.lnp);
-    }
-    slab_plane.clear();
-    for (const auto &v : plan.vars)
-        for (int k = 0; k < v.levels; ++k) {
-            if (v.id < 6) slab_plane.push_back(plan.xf_at[v.id] + k);
-            else if (v.id >= kPlevFirst) {
-                if (k == 0) {
-                    front.plev.out[v.id - kPlevFirst] = front.slab + static_cast<size_t>(plev_plane) * NG;
-                    front.plev.out_stride[v.id - kPlevFirst] = static_cast<long>(front.slab_fields) * NG;
-                }
-                slab_plane.push_back(plev_plane++);
-            } else slab_plane.push_back(-1);
-        }
-    hipError_t e = hipSuccess;
-    if (front.xf_fields > 0) {
-        e = hipMemcpy(front.table[0], host_table[0].data(), host_table[0].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(front.table[1], host_table[1].data(), host_table[1].size() * sizeof(FieldDesc), hipMemcpyHostToDevice);
-    }
-    return e;
-}
-
-// the front end of a sample of members [first, first + count) after the step just issued on `s`: what spd_model_spectral2grid
-// would leave in the grid arrays (the same vort2vel into sv, the same transforms), into the slab; then the pressure-level planes
-hipError_t sample_front(spd_model *m, const spd_model::SampleFront &f, int first, int count, hipStream_t s) {
-    const DeviceTables &T = m->ctx->dev;
-    const size_t S = NSPEC * C, half = static_cast<size_t>(m->M) * 16, off = static_cast<size_t>(first) * 16;
-    hipError_t e = hipSuccess;
-    if (f.uv) e = run_vort2vel(T, m->P.vor + off * S, m->P.div + off * S, m->P.sv + off * S, m->P.sv + (half + off) * S, count * 16, s);
-    if (e == hipSuccess && f.xf_fields > 0)
-        e = run_spec2grid_table(T, f.table[m->phi_cur] + static_cast<size_t>(first) * f.xf_fields, count * f.xf_fields, s);
-    if (e == hipSuccess && f.plev.mask) {  // slab -> further slab planes, in export units
-        PlevArgs a = f.plev;
-        a.first = first;
-        e = run_plev(a, count, s);
-    }
-    return e;
-}
-}  // namespace
-
-
-// ---- what every _configure and _read of the in-loop features does around its own work (with configure_allowed, retire, Carve) ----
-namespace {
-// slab | tables[2] of a front end
-void carve_front(Carve &carve, const SamplePlan &plan, spd_model::SampleFront &front) {
-    front.slab = carve.take<double>(plan.slab_bytes);
-    front.table[0] = carve.take<FieldDesc>(plan.table_bytes);
-    front.table[1] = carve.take<FieldDesc>(plan.table_bytes);
-}
-// an upload into the new allocation `p` failed: the feature stays off
-int upload_failed(const char *who, hipError_t e, void *p) {
-    (void)hipGetLastError();
-    (void)hipFree(p);
-    return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-}
-
-// A _read call of a model that is there: usable, the recorder on ("no ... configured (...)"), no checked call in flight, and
-// nothing recorded behind a failed range check ("the ... invalid until spd_model_..._reset")
-int read_allowed(const spd_model *m, const char *who, bool on, const char *off, const Validity &validity, const char *invalid) {
-    if (int rc = usable(m, who)) return rc;
-    if (!on) return m_fail(SPD_E_ARG, std::string(who) + ": " + off);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (!validity.valid) return m_fail(SPD_E_ARG, std::string(who) + ": " + invalid + ": " + validity.why);
-    return SPD_OK;
-}
-// samples (windows, events) [t0, t0 + nt) of those the ring holds
-int held_range(const char *who, const SampleRing &ring, int t0, int nt, const char *unit) {
-    if (t0 < 0 || nt < 0 || static_cast<long long>(t0) + nt > ring.held())
-        return m_fail(SPD_E_ARG, std::string(who) + ": " + unit + " range out of bounds (" + std::to_string(ring.held()) + " " + unit + "s held)");
-    return SPD_OK;
-}
-// `need` bytes into the caller's device buffer
-int destination_fits(const char *who, const void *dst_device, size_t dst_bytes, size_t need, size_t align) {
-    if (!dst_device && need > 0) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (reinterpret_cast<uintptr_t>(dst_device) % align != 0)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the destination must be " + std::to_string(align) + "-byte aligned");
-    return SPD_OK;
-}
-}  // namespace
-
-// the sample of members [first, first + count): the front end, then the moments
-static hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
-    const spd_model::Stats &st = m->stats;
-    hipError_t e = sample_front(m, st, first, count, s);
-    if (e == hipSuccess) e = run_stats_accumulate(st.planes, st.nplanes, st.slab, st.slab_fields, first, count, n, m->stored32 ? 1 : 0, s);
-    return e;
-}
-
-// ... and of the tape: the front end into the tape's own slab, then the store into ring slot (n - 1) % capacity
-static hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
-    const spd_model::Tape &tp = m->tape;
-    hipError_t e = sample_front(m, tp, first, count, s);
-    if (e == hipSuccess)
-        e = run_tape_store(tp.planes, tp.nplanes, tp.slab, tp.slab_fields, first, count, tp.ring.slot(n),
-                           m->stored32 ? 1 : 0, tp.dtype == SPD_TAPE_F64 ? 1 : 0, s);
-    return e;
-}
-
-// ... and of the ensemble tape: the front end into its own slab, then the fold of these members into partial `group` of ring slot
-// (n - 1) % capacity, behind the members the partial already holds (rounds: the same stream, one after the other)
-static hipError_t enstape_sample(spd_model *m, int first, int count, long long n, int group, hipStream_t s) {
-    spd_model::EnsTape &et = m->enstape;
-    const int slot = et.ring.slot(n);
-    int &held = et.counts[static_cast<size_t>(slot) * kEnsTapeGroups + group];
-    hipError_t e = sample_front(m, et, first, count, s);
-    if (e == hipSuccess)
-        e = run_enstape_fold(et.planes, et.nplanes, et.slab, et.slab_fields, first, count, slot * kEnsTapeGroups + group, held,
-                             m->stored32 ? 1 : 0, s);
-    if (e == hipSuccess) held += count;
-    return e;
-}
-
-int spd_model_stats_configure(spd_model_handle m, const char *const *names, int n_names, int every, int with_variance) {
-    const char *who = "spd_model_stats_configure";
-    // (the arguments first: nothing below needs the device)
-    std::vector<int> ids;
-    if (int rc = sample_ids(who, names, n_names, ids)) return rc;
-    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-    if (int rc = configure_allowed(m, who)) return rc;
-    for (size_t k = 0; k < ids.size(); ++k)
-        if (ids[k] >= kPlevFirst && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    spd_model::Stats &st = m->stats;
-    if (int rc = retire(m, st)) return rc;
-    if (n_names == 0) return SPD_OK;  // off
-    spd_model::Stats next;
-    next.every = every;
-    next.variance = with_variance != 0;
-    const size_t M = static_cast<size_t>(m->M);
-    SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    const size_t planes = plan.planes;
-    for (const auto &v : plan.vars) next.vars.push_back({v.id, v.levels, M * v.first_plane * NG});
-    next.nplanes = static_cast<int>(planes);
-    // one allocation: mean | m2 | slab | tables[2] | plane descriptors
-    const size_t acc = sample_up(M * planes * NG * sizeof(double)), desc = sample_up(planes * sizeof(StatsPlane));
-    const size_t total = acc * (next.variance ? 2 : 1) + plan.slab_bytes + 2 * plan.table_bytes + desc;
-    void *p = nullptr;
-    M_HIP(hipMalloc(&p, total));
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.mean = carve.take<double>(acc);
-    if (next.variance) next.m2 = carve.take<double>(acc);
-    carve_front(carve, plan, next);
-    next.planes = carve.take<StatsPlane>(desc);
-    std::vector<int> slab_plane;
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
-    std::vector<StatsPlane> host_planes;
-    for (const auto &v : next.vars)
-        for (int k = 0; k < v.levels; ++k) {
-            StatsPlane d{};
-            d.slab_plane = slab_plane[host_planes.size()];
-            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.unit = kStatsCatalogue[v.id].unit;
-            d.mean = next.mean + v.offset + static_cast<size_t>(k) * NG;
-            d.m2 = next.variance ? next.m2 + v.offset + static_cast<size_t>(k) * NG : nullptr;
-            d.member_stride = static_cast<long>(v.levels) * NG;
-            host_planes.push_back(d);
-        }
-    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(StatsPlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.on = true;
-    st = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_stats_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_stats_reset: null model");
-    if (!m->stats.on) return m_fail(SPD_E_ARG, "spd_model_stats_reset: no statistics configured (spd_model_stats_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_stats_reset: a checked multi-step call is in flight; end it first");
-    m->stats.samples = 0;  // (the next sample overwrites the accumulators instead of reading them: no device work)
-    m->stats.validity.clear();
-    return SPD_OK;
-}
-
-int spd_model_stats_samples(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_stats_samples: null model");
-    if (!m->stats.on) return m_fail(SPD_E_ARG, "spd_model_stats_samples: no statistics configured (spd_model_stats_configure)");
-    return static_cast<int>(m->stats.samples);
-}
-
-// what every read checks; -> the variable's entry
-static int stats_readable(spd_model *m, const char *name, const char *who, const spd_model::Stats::Var **out) {
-    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const spd_model::Stats &st = m->stats;
-    if (int rc = read_allowed(m, who, st.on, "no statistics configured (spd_model_stats_configure)", st.validity,
-                              "the statistics are invalid until spd_model_stats_reset"))
-        return rc;
-    const int id = stats_id(name);
-    for (const auto &v : st.vars)
-        if (v.id == id) {
-            if (st.samples == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no sample taken since the statistics were (re)started");
-            *out = &v;
-            return SPD_OK;
-        }
-    return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
-}
-
-int spd_model_stats_read(spd_model_handle m, const char *name, int kind, int first, int count, void *dst_device, size_t dst_bytes,
-                         void *stream) {
-    const char *who = "spd_model_stats_read";
-    const spd_model::Stats::Var *v = nullptr;
-    if (int rc = stats_readable(m, name, who, &v)) return rc;
-    if (!dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    if (kind != SPD_STATS_MEAN && kind != SPD_STATS_VARIANCE)
-        return m_fail(SPD_E_ARG, std::string(who) + ": kind must be SPD_STATS_MEAN or SPD_STATS_VARIANCE");
-    const spd_model::Stats &st = m->stats;
-    if (kind == SPD_STATS_VARIANCE && !st.variance) return m_fail(SPD_E_ARG, std::string(who) + ": configured without variance");
-    if (kind == SPD_STATS_VARIANCE && st.samples < 2) return m_fail(SPD_E_ARG, std::string(who) + ": the variance needs two samples");
-    const size_t per = static_cast<size_t>(v->levels) * NG, need = static_cast<size_t>(count) * per * sizeof(double);
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (count == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t at = v->offset + static_cast<size_t>(first) * per;
-    if (kind == SPD_STATS_MEAN) {
-        M_HIP(hipMemcpyAsync(dst_device, st.mean + at, need, hipMemcpyDeviceToDevice, s));
-    } else {
-        const hipError_t e = run_stats_variance(st.m2 + at, static_cast<double *>(dst_device), static_cast<long>(count * per), st.samples, s);
-        if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    return SPD_OK;
-}
-
-int spd_model_stats_ensemble(spd_model_handle m, const char *name, int kind, void *dst_device, size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_stats_ensemble";
-    const spd_model::Stats::Var *v = nullptr;
-    if (int rc = stats_readable(m, name, who, &v)) return rc;
-    if (!dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null destination");
-    if (kind != SPD_STATS_MEAN && kind != SPD_STATS_STD) return m_fail(SPD_E_ARG, std::string(who) + ": kind must be SPD_STATS_MEAN or SPD_STATS_STD");
-    const size_t per = static_cast<size_t>(v->levels) * NG, need = per * sizeof(double);
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    M_HIP(hipSetDevice(m->ctx->device));
-    const hipError_t e = run_stats_ensemble(m->stats.mean + v->offset, m->M, static_cast<long>(per), kind == SPD_STATS_STD ? 1 : 0,
-                                            static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the tape: time series of fields recorded inside multi-step calls (spd_model_tape_*; kernels: tape.hip)
-// ---------------------------------------------------------------------------------------------------------------
-int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity, int dtype) {
-    const char *who = "spd_model_tape_configure";
-    // (the arguments first: nothing below needs the device)
-    std::vector<int> ids;
-    if (int rc = sample_ids(who, names, n_names, ids)) return rc;
-    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-    if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-    if (n_names > 0 && dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64)
-        return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
-    if (int rc = configure_allowed(m, who)) return rc;
-    for (size_t k = 0; k < ids.size(); ++k)
-        if (ids[k] >= kPlevFirst && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    spd_model::Tape &tp = m->tape;
-    if (int rc = retire(m, tp)) return rc;
-    if (n_names == 0) return SPD_OK;  // off
-    spd_model::Tape next;
-    next.every = every;
-    next.dtype = dtype;
-    const size_t M = static_cast<size_t>(m->M), elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
-    SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    const size_t slots = static_cast<size_t>(capacity);
-    for (const auto &v : plan.vars) next.vars.push_back({v.id, v.levels, slots * M * v.first_plane * NG});
-    next.nplanes = static_cast<int>(plan.planes);
-    // one allocation: ring | slab | tables[2] | plane descriptors
-    const size_t per_slot = M * plan.planes * NG * elem;
-    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 2) / per_slot)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the tape's size does not fit size_t");
-    const size_t ring = sample_up(slots * per_slot), desc = sample_up(plan.planes * sizeof(TapePlane));
-    const size_t total = ring + plan.slab_bytes + 2 * plan.table_bytes + desc;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // the tape is off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the tape (" + std::to_string(total) + " bytes asked for: " +
-                                        std::to_string(capacity) + " samples of " + std::to_string(per_slot) + " bytes); the tape is off");
-    }
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.data = carve.take<char>(ring);
-    carve_front(carve, plan, next);
-    next.planes = carve.take<TapePlane>(desc);
-    std::vector<int> slab_plane;
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
-    std::vector<TapePlane> host_planes;
-    for (const auto &v : next.vars)
-        for (int k = 0; k < v.levels; ++k) {
-            TapePlane d{};
-            d.slab_plane = slab_plane[host_planes.size()];
-            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.unit = kStatsCatalogue[v.id].unit;
-            d.dst = static_cast<char *>(next.data) + (v.offset + static_cast<size_t>(k) * NG) * elem;
-            d.member_stride = static_cast<long>(v.levels) * NG;
-            d.slot_stride = static_cast<long>(M) * v.levels * NG;
-            host_planes.push_back(d);
-        }
-    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(TapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.ring = SampleRing(capacity, 6);
-    next.on = true;
-    tp = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_tape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_reset: null model");
-    if (!m->tape.on) return m_fail(SPD_E_ARG, "spd_model_tape_reset: no tape configured (spd_model_tape_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_tape_reset: a checked multi-step call is in flight; end it first");
-    m->tape.ring.clear();
-    m->tape.validity.clear();
-    return SPD_OK;
-}
-
-int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *dtype) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_info: null model");
-    const spd_model::Tape &tp = m->tape;
-    if (!tp.on) return m_fail(SPD_E_ARG, "spd_model_tape_info: no tape configured (spd_model_tape_configure)");
-    if (taken) *taken = tp.ring.taken;
-    if (held) *held = static_cast<int>(tp.ring.held());
-    if (capacity) *capacity = tp.ring.capacity;
-    if (every) *every = tp.every;
-    if (dtype) *dtype = tp.dtype;
-    return SPD_OK;
-}
-
-int spd_model_tape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_times: null model");
-    const spd_model::Tape &tp = m->tape;
-    if (!tp.on) return m_fail(SPD_E_ARG, "spd_model_tape_times: no tape configured (spd_model_tape_configure)");
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_tape_times: bad destination");
-    return tp.ring.copy_rows(rows, max_rows);
-}
-
-int spd_model_tape_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
-                        void *stream) {
-    const char *who = "spd_model_tape_read";
-    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const spd_model::Tape &tp = m->tape;
-    if (int rc = read_allowed(m, who, tp.on, "no tape configured (spd_model_tape_configure)", tp.validity, "the tape is invalid until spd_model_tape_reset"))
-        return rc;
-    const int id = stats_id(name);
-    const spd_model::Tape::Var *v = nullptr;
-    for (const auto &x : tp.vars)
-        if (x.id == id) v = &x;
-    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
-    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    if (int rc = held_range(who, tp.ring, t0, nt, "sample")) return rc;
-    const size_t elem = tp.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->levels) * NG;
-    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
-    if (count == 0 || nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    const char *src = static_cast<const char *>(tp.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
-    const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
-                                         static_cast<int>(elem), count, nt, tp.ring.slot_of_held(t0), tp.ring.capacity,
-                                         static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*; kernels: spectra.hip)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-constexpr const char *kSpectraNames[SPECTRA_NNAMES] = {"ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum",
-                                                       "lnps_spectrum",   "t_mean",          "q_mean",     "lnps_mean"};
-int spectra_id(const char *name) {
-    for (int v = 0; name && v < SPECTRA_NNAMES; ++v)
-        if (std::strcmp(name, kSpectraNames[v]) == 0) return v;
-    return -1;
-}
-
-// the list of names of a call -> ids, in the order given (the arguments first: nothing here needs the device or a model)
-int spectra_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
-    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of names");
-    for (int k = 0; k < n_names; ++k) {
-        const int id = spectra_id(names[k]);
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown name '" + (names[k] ? names[k] : "(null)") +
-                                         "' (ke_rot_spectrum, ke_div_spectrum, t_spectrum, q_spectrum, lnps_spectrum, t_mean, q_mean, "
-                                         "lnps_mean)");
-        if (std::find(ids.begin(), ids.end(), id) != ids.end())
-            return m_fail(SPD_E_ARG, std::string(who) + ": name '" + names[k] + "' given twice");
-        ids.push_back(id);
-    }
-    return SPD_OK;
-}
-
-// the kernel's arguments but for the destinations: the members [first, first + count) of the state as it stands
-SpectraArgs spectra_args(const spd_model *m, unsigned mask, int first, int out_first) {
-    SpectraArgs a{};
-    a.vor = m->P.vor, a.div = m->P.div, a.t = m->P.t, a.tr = m->P.tr, a.ps = m->P.ps;
-    a.elm2 = m->ctx->dev.elm2;
-    a.mask = mask, a.first = first, a.out_first = out_first;
-    return a;
-}
-}  // namespace
-
-// a sample: one launch for the group's members, straight into ring slot (n - 1) % capacity
-static hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
-    const spd_model::Spectra &sp = m->spectra;
-    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>(sp.ring.slot(n));
-    SpectraArgs a = spectra_args(m, sp.mask, first, 0);
-    for (int v = 0; v < SPECTRA_NNAMES; ++v)
-        if (sp.mask & (1u << v)) a.out[v] = static_cast<double *>(sp.alloc) + sp.offset[v] + slot * M * spectra_per_member(v);
-    return run_spectra(a, count, s);
-}
-
-int spd_model_spectra_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity) {
-    const char *who = "spd_model_spectra_configure";
-    // (the arguments first: nothing below needs the device)
-    std::vector<int> ids;
-    if (int rc = spectra_ids(who, names, n_names, ids)) return rc;
-    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-    if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-    if (int rc = configure_allowed(m, who)) return rc;
-    spd_model::Spectra &sp = m->spectra;
-    if (int rc = retire(m, sp)) return rc;
-    if (n_names == 0) return SPD_OK;  // off
-    spd_model::Spectra next;
-    next.every = every;
-    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
-    size_t per_slot = 0;  // doubles of a sample
-    for (int id : ids) {
-        next.mask |= 1u << id;
-        per_slot += M * spectra_per_member(id);
-    }
-    if (slots > (static_cast<size_t>(-1) / 2) / (per_slot * sizeof(double)))
-        return m_fail(SPD_E_ARG, std::string(who) + ": the size of the series does not fit size_t");
-    size_t at = 0;
-    for (int v = 0; v < SPECTRA_NNAMES; ++v)
-        if (next.mask & (1u << v)) {
-            next.offset[v] = at;
-            at += slots * M * spectra_per_member(v);
-        }
-    const size_t total = sample_up(at * sizeof(double));
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // the spectra are off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the series (" + std::to_string(total) + " bytes asked for: " +
-                                        std::to_string(capacity) + " samples of " + std::to_string(per_slot * sizeof(double)) +
-                                        " bytes); the spectra are off");
-    }
-    next.alloc = p;
-    next.ring = SampleRing(capacity, 6);
-    next.on = true;
-    sp = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_spectra_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: null model");
-    if (!m->spectra.on) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: no spectra configured (spd_model_spectra_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: a checked multi-step call is in flight; end it first");
-    m->spectra.ring.clear();
-    m->spectra.validity.clear();
-    return SPD_OK;
-}
-
-int spd_model_spectra_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_info: null model");
-    const spd_model::Spectra &sp = m->spectra;
-    if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_info: no spectra configured (spd_model_spectra_configure)");
-    if (taken) *taken = sp.ring.taken;
-    if (held) *held = static_cast<int>(sp.ring.held());
-    if (capacity) *capacity = sp.ring.capacity;
-    if (every) *every = sp.every;
-    return SPD_OK;
-}
-
-int spd_model_spectra_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_times: null model");
-    const spd_model::Spectra &sp = m->spectra;
-    if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_times: no spectra configured (spd_model_spectra_configure)");
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_spectra_times: bad destination");
-    return sp.ring.copy_rows(rows, max_rows);
-}
-
-int spd_model_spectra_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
-                           void *stream) {
-    const char *who = "spd_model_spectra_read";
-    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const spd_model::Spectra &sp = m->spectra;
-    if (int rc = read_allowed(m, who, sp.on, "no spectra configured (spd_model_spectra_configure)", sp.validity,
-                              "the spectra are invalid until spd_model_spectra_reset"))
-        return rc;
-    const int id = spectra_id(name);
-    if (id < 0 || !(sp.mask & (1u << id))) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured names");
-    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    if (int rc = held_range(who, sp.ring, t0, nt, "sample")) return rc;
-    const size_t per = static_cast<size_t>(spectra_per_member(id));
-    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
-    if (count == 0 || nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    const double *src = static_cast<const double *>(sp.alloc) + sp.offset[id] + static_cast<size_t>(first) * per;
-    const hipError_t e = run_spectra_gather(src, static_cast<double *>(dst_device), static_cast<int>(per),
-                                            static_cast<long>(static_cast<size_t>(m->M) * per), count, nt,
-                                            sp.ring.slot_of_held(t0), sp.ring.capacity, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-int spd_model_spectra_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, void *dst_device,
-                              size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_spectra_compute";
-    std::vector<int> ids;
-    if (int rc = spectra_ids(who, names, n_names, ids)) return rc;
-    if (int rc = member_range(m, first, count, who)) return rc;
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    size_t per = 0;
-    for (int id : ids) per += static_cast<size_t>(spectra_per_member(id));
-    const size_t need = static_cast<size_t>(count) * per * sizeof(double);
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
-    if (need == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    SpectraArgs a = spectra_args(m, 0, first, first);
-    double *at = static_cast<double *>(dst_device);
-    for (int id : ids) {  // [count][...] per name, one after the other in the order given
-        a.mask |= 1u << id;
-        a.out[id] = at;
-        at += static_cast<size_t>(count) * spectra_per_member(id);
-    }
-    const hipError_t e = run_spectra(a, count, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the ensemble tape: mean and spread over the members as a time series (spd_model_enstape_*; kernels: enstape.hip)
-// ---------------------------------------------------------------------------------------------------------------
-int spd_model_enstape_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity) {
-    const char *who = "spd_model_enstape_configure";
-    // (the arguments first: nothing below needs the device)
-    std::vector<int> ids;
-    if (int rc = sample_ids(who, names, n_names, ids)) return rc;
-    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-    if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-    if (int rc = configure_allowed(m, who)) return rc;
-    for (size_t k = 0; k < ids.size(); ++k)
-        if (ids[k] >= kPlevFirst && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    spd_model::EnsTape &et = m->enstape;
-    if (int rc = retire(m, et)) return rc;
-    if (n_names == 0) return SPD_OK;  // off
-    spd_model::EnsTape next;
-    next.every = every;
-    SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    const size_t slots = static_cast<size_t>(capacity);
-    for (const auto &v : plan.vars) next.vars.push_back({v.id, v.levels, v.first_plane});
-    next.nplanes = static_cast<int>(plan.planes);
-    // one allocation: mean ring | M2 ring | slab | tables[2] | plane descriptors
-    const size_t per_slot = kEnsTapeGroups * plan.planes * NG * sizeof(double);  // of ONE of the two rings
-    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 4) / per_slot)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape's size does not fit size_t");
-    const size_t ring = sample_up(slots * per_slot), desc = sample_up(plan.planes * sizeof(EnsTapePlane));
-    const size_t total = 2 * ring + plan.slab_bytes + 2 * plan.table_bytes + desc;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // the ensemble tape is off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the ensemble tape (" + std::to_string(total) + " bytes asked for: " +
-                                        std::to_string(capacity) + " samples of " + std::to_string(2 * per_slot) +
-                                        " bytes); the ensemble tape is off");
-    }
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.mean = carve.take<double>(ring);
-    next.m2 = carve.take<double>(ring);
-    carve_front(carve, plan, next);
-    next.planes = carve.take<EnsTapePlane>(desc);
-    std::vector<int> slab_plane;
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
-    std::vector<EnsTapePlane> host_planes;
-    for (const auto &v : next.vars)
-        for (int k = 0; k < v.levels; ++k) {
-            EnsTapePlane d{};
-            d.slab_plane = slab_plane[host_planes.size()];
-            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.unit = kStatsCatalogue[v.id].unit;
-            d.mean = next.mean + (v.first_plane + static_cast<size_t>(k)) * NG;
-            d.m2 = next.m2 + (v.first_plane + static_cast<size_t>(k)) * NG;
-            host_planes.push_back(d);
-        }
-    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(EnsTapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.ring = SampleRing(capacity, 6);
-    next.counts.assign(slots * kEnsTapeGroups, 0);
-    next.on = true;
-    et = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_enstape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: null model");
-    if (!m->enstape.on) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: no ensemble tape configured (spd_model_enstape_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: a checked multi-step call is in flight; end it first");
-    m->enstape.ring.clear();  // (the next sample opens the partials of slot 0 anew)
-    m->enstape.validity.clear();
-    return SPD_OK;
-}
-
-int spd_model_enstape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *members) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_info: null model");
-    const spd_model::EnsTape &et = m->enstape;
-    if (!et.on) return m_fail(SPD_E_ARG, "spd_model_enstape_info: no ensemble tape configured (spd_model_enstape_configure)");
-    if (taken) *taken = et.ring.taken;
-    if (held) *held = static_cast<int>(et.ring.held());
-    if (capacity) *capacity = et.ring.capacity;
-    if (every) *every = et.every;
-    if (members) *members = m->M;
-    return SPD_OK;
-}
-
-int spd_model_enstape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_times: null model");
-    const spd_model::EnsTape &et = m->enstape;
-    if (!et.on) return m_fail(SPD_E_ARG, "spd_model_enstape_times: no ensemble tape configured (spd_model_enstape_configure)");
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_enstape_times: bad destination");
-    return et.ring.copy_rows(rows, max_rows);
-}
-
-int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_enstape_read";
-    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const spd_model::EnsTape &et = m->enstape;
-    if (int rc = read_allowed(m, who, et.on, "no ensemble tape configured (spd_model_enstape_configure)", et.validity,
-                              "the ensemble tape is invalid until spd_model_enstape_reset"))
-        return rc;
-    const int id = stats_id(name);
-    const spd_model::EnsTape::Var *v = nullptr;
-    for (const auto &x : et.vars)
-        if (x.id == id) v = &x;
-    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured variables");
-    if (kind != SPD_ENS_MEAN && kind != SPD_ENS_STD && kind != SPD_ENS_M2)
-        return m_fail(SPD_E_ARG, std::string(who) + ": kind must be SPD_ENS_MEAN, SPD_ENS_STD or SPD_ENS_M2");
-    if (int rc = held_range(who, et.ring, t0, nt, "sample")) return rc;
-    const size_t per = static_cast<size_t>(v->levels) * NG, need = static_cast<size_t>(nt) * per * sizeof(double);
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
-    if (nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    const int slot0 = et.ring.slot_of_held(t0);
-    std::vector<int> counts(static_cast<size_t>(nt) * kEnsTapeGroups);  // of the samples of the read, in its order
-    for (int t = 0; t < nt; ++t)
-        std::memcpy(counts.data() + static_cast<size_t>(t) * kEnsTapeGroups,
-                    et.counts.data() + static_cast<size_t>(et.ring.slot_of_held(t0 + static_cast<long long>(t))) * kEnsTapeGroups,
-                    kEnsTapeGroups * sizeof(int));
-    const size_t var_at = v->first_plane * NG;
-    const hipError_t e = run_enstape_read(et.mean + var_at, et.m2 + var_at, static_cast<long>(per), et.nplanes, kind, nt, slot0, et.ring.capacity,
-                                          counts.data(), static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the accumulation tape: window sums, means and extremes of the physics' 2-D outputs (spd_model_acctape_*; kernel: acctape.hip)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-// The column physics' 2-D outputs of which every plane is stored on every step that runs with diag = 1 (physics.hip).  hfluxn (its
-// third plane is never written) and qcloud_equiv (written on shortwave steps only, and an input of the next steps rather than a
-// flux) are not confirmed and are refused by name.
-struct AccName {
-    const char *name;
-    int planes;
-};
-constexpr AccName kAccNames[] = {{"precnv", 1}, {"precls", 1}, {"cbmf", 1}, {"olr", 1},  {"tsr", 1},  {"ssr", 1},  {"ssrd", 1},
-                                 {"slr", 1},    {"slrd", 1},   {"ustr", 3}, {"vstr", 3}, {"shf", 3}, {"evap", 3}, {"slru", 3}};
-constexpr int kAccNNames = static_cast<int>(sizeof(kAccNames) / sizeof(kAccNames[0]));
-int acc_name_id(const char *name) {
-    for (int v = 0; name && v < kAccNNames; ++v)
-        if (std::strcmp(name, kAccNames[v].name) == 0) return v;
-    return -1;
-}
-const void *acc_source(const spd_model *m, int id) {
-    const spd_physics_args &pa = m->pa;
-    const double *const src[kAccNNames] = {pa.precnv, pa.precls, pa.cbmf, pa.olr, pa.tsr, pa.ssr, pa.ssrd,
-                                           pa.slr,    pa.slrd,   pa.ustr, pa.vstr, pa.shf, pa.evap, pa.slru};
-    return src[id];
-}
-const char *const kAccOff = "no accumulation tape configured (spd_model_acctape_configure)";
-}  // namespace
-
-int spd_model_acctape_configure(spd_model_handle m, const char *const *names, const int *ops, int n_entries, int every, int capacity,
-                                int dtype) {
-    const char *who = "spd_model_acctape_configure";
-    // (the arguments first: nothing below needs the device)
-    if (n_entries < 0 || (n_entries > 0 && (!names || !ops))) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
-    std::vector<spd_model::AccTape::Entry> entries;
-    for (int k = 0; k < n_entries; ++k) {
-        const int id = acc_name_id(names[k]);
-        if (id < 0) {
-            const std::string name = names[k] ? names[k] : "(null)";
-            if (name == "hfluxn" || name == "qcloud_equiv")
-                return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not stored in every plane on every step and cannot be accumulated");
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + name + "'");
-        }
-        if (ops[k] != SPD_ACC_SUM && ops[k] != SPD_ACC_MEAN && ops[k] != SPD_ACC_MIN && ops[k] != SPD_ACC_MAX)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown op " + std::to_string(ops[k]) + " for '" + names[k] +
-                                         "' (SPD_ACC_SUM, SPD_ACC_MEAN, SPD_ACC_MIN or SPD_ACC_MAX)");
-        for (const auto &e : entries)
-            if (e.name == id && e.op == ops[k])
-                return m_fail(SPD_E_ARG, std::string(who) + ": entry ('" + names[k] + "', " + std::to_string(ops[k]) + ") named twice");
-        entries.push_back({id, ops[k], kAccNames[id].planes, 0});
-    }
-    if (n_entries > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-    if (n_entries > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-    if (n_entries > 0 && dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64)
-        return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
-    if (int rc = configure_allowed(m, who)) return rc;
-    spd_model::AccTape &ac = m->acctape;
-    if (int rc = retire(m, ac)) return rc;
-    if (n_entries == 0) return SPD_OK;  // off
-    spd_model::AccTape next;
-    next.every = every;
-    next.dtype = dtype;
-    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
-    const size_t elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
-    // what each name needs: [0] a running sum (sum or mean), [1] a minimum, [2] a maximum
-    bool need[kAccNNames][3] = {};
-    size_t ring_planes = 0, acc_planes = 0, desc_planes = 0;
-    for (auto &e : entries) {
-        e.offset = slots * M * ring_planes * NG;
-        ring_planes += static_cast<size_t>(e.planes);
-        need[e.name][e.op == SPD_ACC_MIN ? 1 : e.op == SPD_ACC_MAX ? 2 : 0] = true;
-    }
-    for (int v = 0; v < kAccNNames; ++v) {
-        const int kinds = (need[v][0] ? 1 : 0) + (need[v][1] ? 1 : 0) + (need[v][2] ? 1 : 0);
-        acc_planes += static_cast<size_t>(kinds) * kAccNames[v].planes;
-        if (kinds) desc_planes += static_cast<size_t>(kAccNames[v].planes);
-    }
-    // one allocation: ring | accumulators | plane descriptors
-    const size_t per_slot = M * ring_planes * NG * elem;
-    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 2) / per_slot)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the accumulation tape's size does not fit size_t");
-    const size_t ring = sample_up(slots * per_slot), accs = sample_up(M * acc_planes * NG * sizeof(double));
-    const size_t desc = sample_up(desc_planes * sizeof(AccTapePlane));
-    const size_t total = ring + accs + desc;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // the accumulation tape is off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the accumulation tape (" + std::to_string(total) +
-                                        " bytes asked for: " + std::to_string(capacity) + " windows of " + std::to_string(per_slot) +
-                                        " bytes and " + std::to_string(accs) + " bytes of accumulators); the accumulation tape is off");
-    }
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.data = carve.take<char>(ring);
-    double *acc_at = carve.take<double>(accs);
-    next.planes = carve.take<AccTapePlane>(desc);
-    std::vector<AccTapePlane> host_planes;
-    for (int v = 0; v < kAccNNames; ++v) {
-        if (!need[v][0] && !need[v][1] && !need[v][2]) continue;
-        const size_t planes = static_cast<size_t>(kAccNames[v].planes), per = planes * NG;
-        double *acc[3] = {nullptr, nullptr, nullptr};
-        for (int a = 0; a < 3; ++a)
-            if (need[v][a]) acc[a] = acc_at, acc_at += M * per;
-        for (size_t k = 0; k < planes; ++k) {
-            AccTapePlane d{};
-            // (plane k in elements: the kernel indexes the source as float or double, as the model stores it at the time of the step)
-            d.src = acc_source(m, v);
-            d.plane = static_cast<int>(k);
-            d.sum = acc[0] ? acc[0] + k * NG : nullptr;
-            d.mn = acc[1] ? acc[1] + k * NG : nullptr;
-            d.mx = acc[2] ? acc[2] + k * NG : nullptr;
-            for (const auto &e : entries)
-                if (e.name == v) d.ring[e.op] = static_cast<char *>(next.data) + (e.offset + k * NG) * elem;
-            d.member_stride = static_cast<long>(per);
-            d.slot_stride = static_cast<long>(M * per);
-            d.narrow = m->reg[kAccNames[v].name].f32 ? 1 : 0;  // (what physics_storage32 keeps as float)
-            host_planes.push_back(d);
-        }
-    }
-    const hipError_t e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(AccTapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.nplanes = static_cast<int>(host_planes.size());
-    next.entries = std::move(entries);
-    next.ring = SampleRing(capacity, 7);
-    next.window_start = -1;  // (the first window starts at the model's current step: step_impl reads the counter when it next runs)
-    next.on = true;
-    ac = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_acctape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: null model");
-    if (!m->acctape.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_reset: ") + kAccOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: a checked multi-step call is in flight; end it first");
-    m->acctape.ring.clear();
-    m->acctape.window_start = -1;  // (the next window starts at the next step, which overwrites the accumulators: no device work)
-    m->acctape.validity.clear();
-    return SPD_OK;
-}
-
-int spd_model_acctape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *dtype) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_info: null model");
-    const spd_model::AccTape &ac = m->acctape;
-    if (!ac.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_info: ") + kAccOff);
-    if (taken) *taken = ac.ring.taken;
-    if (held) *held = static_cast<int>(ac.ring.held());
-    if (capacity) *capacity = ac.ring.capacity;
-    if (every) *every = ac.every;
-    if (dtype) *dtype = ac.dtype;
-    return SPD_OK;
-}
-
-int spd_model_acctape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_times: null model");
-    const spd_model::AccTape &ac = m->acctape;
-    if (!ac.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_times: ") + kAccOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_acctape_times: bad destination");
-    return ac.ring.copy_rows(rows, max_rows);
-}
-
-int spd_model_acctape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
-                           size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_acctape_read";
-    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const spd_model::AccTape &ac = m->acctape;
-    if (int rc = read_allowed(m, who, ac.on, kAccOff, ac.validity, "the accumulation tape is invalid until spd_model_acctape_reset")) return rc;
-    const int id = acc_name_id(name);
-    const spd_model::AccTape::Entry *v = nullptr;
-    for (const auto &x : ac.entries)
-        if (x.name == id && x.op == op) v = &x;
-    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": ('" + name + "', " + std::to_string(op) + ") is not among the configured entries");
-    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    if (int rc = held_range(who, ac.ring, t0, nt, "window")) return rc;
-    const size_t elem = ac.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->planes) * NG;
-    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
-    if (count == 0 || nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    const char *src = static_cast<const char *>(ac.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
-    const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
-                                         static_cast<int>(elem), count, nt, ac.ring.slot_of_held(t0), ac.ring.capacity,
-                                         static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the window tape: window sums, means, extremes and threshold counts of the state's fields (spd_model_wintape_*; kernel: wintape.hip)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-// names: the catalogue's fourteen, then the two wind speeds of this recorder only (u and v: the catalogue ids they are formed from)
-constexpr int kWinWspdGrid = kStatsCatalogueSize, kWinWspdPlev = kStatsCatalogueSize + 1, kWinNNames = kStatsCatalogueSize + 2;
-constexpr int kWinNOps = 6;
-int win_name_id(const char *name) {
-    if (!name) return -1;
-    if (std::strcmp(name, "wspd_grid") == 0) return kWinWspdGrid;
-    if (std::strcmp(name, "wspd_plev") == 0) return kWinWspdPlev;
-    return stats_id(name);
-}
-bool win_needs_levels(int id) { return id == kWinWspdPlev || (id >= kPlevFirst && id < kStatsCatalogueSize); }
-int win_u_id(int id) { return id == kWinWspdGrid ? 0 : kPlevFirst + PLEV_U; }
-const char *const kWinOff = "no window tape configured (spd_model_wintape_configure)";
-const char *const kWinOpNames[kWinNOps] = {"SPD_WIN_SUM", "SPD_WIN_MEAN", "SPD_WIN_MIN", "SPD_WIN_MAX", "SPD_WIN_COUNT_ABOVE", "SPD_WIN_COUNT_BELOW"};
-
-// window kind, `every` and sample_every, as _configure and spd_wintape_plan refuse them
-int win_schedule_check(const char *who, int window, int every, int sample_every) {
-    if (window != SPD_WINDOW_STEPS && window != SPD_WINDOW_DAY && window != SPD_WINDOW_MONTH)
-        return m_fail(SPD_E_ARG, std::string(who) + ": unknown window kind " + std::to_string(window) +
-                                     " (SPD_WINDOW_STEPS, SPD_WINDOW_DAY or SPD_WINDOW_MONTH)");
-    if (window == SPD_WINDOW_STEPS && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1 for SPD_WINDOW_STEPS");
-    if (window != SPD_WINDOW_STEPS && every != 0)
-        return m_fail(SPD_E_ARG, std::string(who) + ": every must be 0 for SPD_WINDOW_DAY and SPD_WINDOW_MONTH");
-    if (sample_every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": sample_every must be at least 1");
-    return SPD_OK;
-}
-}  // namespace
-
-int spd_wintape_plan(int year, int month, int day, int hour, int minute, int step0, int nsteps, int window, int every, int sample_every,
-                     int32_t *rows, int max_rows) {
-    const char *who = "spd_wintape_plan";
-    if (month < 1 || month > 12 || day < 1 || day > 31 || hour < 0 || hour > 23 || minute < 0 || minute > 59)
-        return m_fail(SPD_E_ARG, std::string(who) + ": bad date");
-    if (step0 < 0 || nsteps < 0) return m_fail(SPD_E_ARG, std::string(who) + ": step0 and nsteps must not be negative");
-    if (static_cast<long long>(step0) + nsteps > 2147483647LL) return m_fail(SPD_E_ARG, std::string(who) + ": step0 + nsteps does not fit an int");
-    if (int rc = win_schedule_check(who, window, every, sample_every)) return rc;
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, std::string(who) + ": bad destination");
-    Calendar cal;
-    cal.set(year, month, day, hour, minute);
-    const WinSchedule schedule{window, every, sample_every};
-    WinOpen open{step0, 0};
-    int closed = 0;
-    for (int it = 0; it < nsteps; ++it) {
-        cal.advance();
-        int32_t row[8];
-        if (wintape_advance(schedule, open, step0 + it + 1, cal, row).close) {
-            if (closed < max_rows) std::memcpy(rows + 8 * static_cast<size_t>(closed), row, sizeof(row));
-            ++closed;
-        }
-    }
-    return closed;
-}
-
-// the launches of the members [first, first + count) for a step that samples (k >= 1: the front end into the recorder's own slab,
-// then the kernel) or only closes (k = 0: the kernel alone)
-static hipError_t wintape_step(spd_model *m, int first, int count, int k, int close, int n, int slot, hipStream_t s) {
-    const spd_model::WinTape &wt = m->wintape;
-    hipError_t e = hipSuccess;
-    if (k > 0) e = sample_front(m, wt, first, count, s);
-    if (e == hipSuccess)
-        e = run_wintape_step(wt.planes, wt.nplanes, wt.slab, wt.slab_fields, first, count, k, close, n, slot, m->stored32 ? 1 : 0,
-                             wt.dtype == SPD_TAPE_F64 ? 1 : 0, s);
-    return e;
-}
-
-int spd_model_wintape_configure(spd_model_handle m, const char *const *names, const int *ops, const double *thresholds, int n_entries,
-                                int window, int every, int sample_every, int capacity, int dtype) {
-    const char *who = "spd_model_wintape_configure";
-    // (the arguments first, in the header's order: nothing below needs the device)
-    if (n_entries < 0 || (n_entries > 0 && (!names || !ops))) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
-    std::vector<spd_model::WinTape::Entry> entries;
-    for (int k = 0; k < n_entries; ++k) {
-        const int id = win_name_id(names[k]);
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                         "q_plev, z_plev, mslp, wspd_grid, wspd_plev)");
-        entries.push_back({id, ops[k], 0, 0.0, 0});
-    }
-    for (int k = 0; k < n_entries; ++k)
-        if (ops[k] < 0 || ops[k] >= kWinNOps)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown op " + std::to_string(ops[k]) + " for '" + names[k] +
-                                         "' (SPD_WIN_SUM, SPD_WIN_MEAN, SPD_WIN_MIN, SPD_WIN_MAX, SPD_WIN_COUNT_ABOVE or SPD_WIN_COUNT_BELOW)");
-    for (int k = 0; k < n_entries; ++k)
-        if (ops[k] == SPD_WIN_COUNT_ABOVE || ops[k] == SPD_WIN_COUNT_BELOW) {
-            if (!thresholds || !std::isfinite(thresholds[k]))
-                return m_fail(SPD_E_ARG, std::string(who) + ": " + kWinOpNames[ops[k]] + " of '" + names[k] + "' needs a finite threshold");
-            entries[k].threshold = thresholds[k];
-        }
-    for (int k = 0; k < n_entries; ++k)
-        for (int j = 0; j < k; ++j)
-            if (entries[j].name == entries[k].name && entries[j].op == entries[k].op)
-                return m_fail(SPD_E_ARG, std::string(who) + ": entry ('" + names[k] + "', " + std::to_string(ops[k]) + ") named twice");
-    if (n_entries > 0) {
-        if (int rc = win_schedule_check(who, window, every, sample_every)) return rc;
-        if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-        if (dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64) return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
-    }
-    if (int rc = configure_allowed(m, who)) return rc;
-    for (int k = 0; k < n_entries; ++k)
-        if (win_needs_levels(entries[k].name) && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-    spd_model::WinTape &wt = m->wintape;
-    if (int rc = retire(m, wt)) return rc;
-    if (n_entries == 0) return SPD_OK;  // off
-    spd_model::WinTape next;
-    next.window = window;
-    next.every = every;
-    next.sample_every = sample_every;
-    next.dtype = dtype;
-    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
-    const size_t elem = dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float);
-    // The sample plan: the catalogue names among the entries in the order they first appear, then the u and v a wind speed is
-    // formed from where no entry names them -- planes of the slab without accumulators of their own.
-    std::vector<int> ids;
-    auto want = [&](int id) {
-        if (std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
-    };
-    for (const auto &e : entries)
-        if (e.name < kStatsCatalogueSize) want(e.name);
-    for (const auto &e : entries)
-        if (e.name >= kStatsCatalogueSize) want(win_u_id(e.name)), want(win_u_id(e.name) + 1);
-    SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    auto plan_var = [&](int id) -> const SamplePlan::Var & {
-        return *std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
-    };
-    // what each name needs: [0] a running sum (sum or mean), [1] a minimum, [2] a maximum, [3] / [4] a count above / below
-    bool need[kWinNNames][5] = {};
-    int levels[kWinNNames] = {};
-    size_t ring_planes = 0, acc_planes = 0, desc_planes = 0;
-    for (auto &e : entries) {
-        e.levels = plan_var(e.name < kStatsCatalogueSize ? e.name : win_u_id(e.name)).levels;
-        levels[e.name] = e.levels;
-        e.offset = slots * M * ring_planes * NG;
-        ring_planes += static_cast<size_t>(e.levels);
-        need[e.name][e.op <= SPD_WIN_MEAN ? 0 : e.op - 1] = true;
-    }
-    for (int v = 0; v < kWinNNames; ++v) {
-        int kinds = 0;
-        for (int a = 0; a < 5; ++a) kinds += need[v][a] ? 1 : 0;
-        acc_planes += static_cast<size_t>(kinds) * levels[v];
-        if (kinds) desc_planes += static_cast<size_t>(levels[v]);
-    }
-    // one allocation: ring | accumulators | slab | tables[2] | plane descriptors
-    const size_t per_slot = M * ring_planes * NG * elem;
-    if (per_slot != 0 && slots > (static_cast<size_t>(-1) / 2) / per_slot)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the window tape's size does not fit size_t");
-    const size_t ring = sample_up(slots * per_slot), accs = sample_up(M * acc_planes * NG * sizeof(double));
-    const size_t desc = sample_up(desc_planes * sizeof(WinTapePlane));
-    const size_t total = ring + accs + plan.slab_bytes + 2 * plan.table_bytes + desc;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // the window tape is off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the window tape (" + std::to_string(total) +
-                                        " bytes asked for: " + std::to_string(capacity) + " windows of " + std::to_string(per_slot) +
-                                        " bytes and " + std::to_string(accs) + " bytes of accumulators); the window tape is off");
-    }
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.data = carve.take<char>(ring);
-    double *acc_at = carve.take<double>(accs);
-    carve_front(carve, plan, next);
-    next.planes = carve.take<WinTapePlane>(desc);
-    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
-    std::vector<WinTapePlane> host_planes;
-    for (int v = 0; v < kWinNNames; ++v) {
-        bool any = false;
-        for (int a = 0; a < 5; ++a) any = any || need[v][a];
-        if (!any) continue;
-        const bool wspd = v >= kStatsCatalogueSize;
-        const size_t nlev = static_cast<size_t>(levels[v]), per = nlev * NG;
-        double *acc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        for (int a = 0; a < 5; ++a)
-            if (need[v][a]) acc[a] = acc_at, acc_at += M * per;
-        const size_t plane_a = plan_var(wspd ? win_u_id(v) : v).first_plane;
-        const size_t plane_b = wspd ? plan_var(win_u_id(v) + 1).first_plane : 0;
-        for (size_t k = 0; k < nlev; ++k) {
-            WinTapePlane d{};
-            d.slab_a = slab_plane[plane_a + k];
-            d.slab_b = wspd ? slab_plane[plane_b + k] : -1;
-            d.src = v == 6 ? static_cast<const void *>(m->pa.precnv) : v == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.narrow = (v == 6 || v == 7) && m->reg[kStatsCatalogue[v].name].f32 ? 1 : 0;  // (what physics_storage32 keeps as float)
-            d.unit = wspd ? 0 : kStatsCatalogue[v].unit;
-            d.sum = acc[0] ? acc[0] + k * NG : nullptr;
-            d.mn = acc[1] ? acc[1] + k * NG : nullptr;
-            d.mx = acc[2] ? acc[2] + k * NG : nullptr;
-            d.cnt[0] = acc[3] ? acc[3] + k * NG : nullptr;
-            d.cnt[1] = acc[4] ? acc[4] + k * NG : nullptr;
-            for (const auto &x : entries)
-                if (x.name == v) {
-                    d.ring[x.op] = static_cast<char *>(next.data) + (x.offset + k * NG) * elem;
-                    if (x.op >= SPD_WIN_COUNT_ABOVE) d.thr[x.op - SPD_WIN_COUNT_ABOVE] = x.threshold;
-                }
-            d.member_stride = static_cast<long>(per);
-            d.slot_stride = static_cast<long>(M * per);
-            host_planes.push_back(d);
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(WinTapePlane), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.nplanes = static_cast<int>(host_planes.size());
-    next.entries = std::move(entries);
-    next.ring = SampleRing(capacity, 8);
-    next.window_start = -1;  // (the first window starts at the model's current step: step_impl reads the counter when it next runs)
-    next.on = true;
-    wt = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_wintape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: null model");
-    if (!m->wintape.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_reset: ") + kWinOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: a checked multi-step call is in flight; end it first");
-    m->wintape.ring.clear();
-    m->wintape.window_start = -1;  // (the next window starts at the next step; its first sample overwrites the accumulators: no device work)
-    m->wintape.samples = 0;
-    m->wintape.validity.clear();
-    return SPD_OK;
-}
-
-int spd_model_wintape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *window, int *every, int *sample_every,
-                           int *dtype) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_info: null model");
-    const spd_model::WinTape &wt = m->wintape;
-    if (!wt.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_info: ") + kWinOff);
-    if (taken) *taken = wt.ring.taken;
-    if (held) *held = static_cast<int>(wt.ring.held());
-    if (capacity) *capacity = wt.ring.capacity;
-    if (window) *window = wt.window;
-    if (every) *every = wt.every;
-    if (sample_every) *sample_every = wt.sample_every;
-    if (dtype) *dtype = wt.dtype;
-    return SPD_OK;
-}
-
-int spd_model_wintape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_times: null model");
-    const spd_model::WinTape &wt = m->wintape;
-    if (!wt.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_times: ") + kWinOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_wintape_times: bad destination");
-    return wt.ring.copy_rows(rows, max_rows);
-}
-
-int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,
-                           size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_wintape_read";
-    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const spd_model::WinTape &wt = m->wintape;
-    if (int rc = read_allowed(m, who, wt.on, kWinOff, wt.validity, "the window tape is invalid until spd_model_wintape_reset")) return rc;
-    const int id = win_name_id(name);
-    const spd_model::WinTape::Entry *v = nullptr;
-    for (const auto &x : wt.entries)
-        if (x.name == id && x.op == op) v = &x;
-    if (!v) return m_fail(SPD_E_ARG, std::string(who) + ": ('" + name + "', " + std::to_string(op) + ") is not among the configured entries");
-    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    if (int rc = held_range(who, wt.ring, t0, nt, "window")) return rc;
-    const size_t elem = wt.dtype == SPD_TAPE_F64 ? sizeof(double) : sizeof(float), per = static_cast<size_t>(v->levels) * NG;
-    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * elem;
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, 16)) return rc;
-    if (count == 0 || nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    const char *src = static_cast<const char *>(wt.data) + (v->offset + static_cast<size_t>(first) * per) * elem;
-    const hipError_t e = run_tape_gather(src, dst_device, static_cast<long>(per), static_cast<long>(static_cast<size_t>(m->M) * per),
-                                         static_cast<int>(elem), count, nt, wt.ring.slot_of_held(t0), wt.ring.capacity,
-                                         static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the projection tape: weighted sums of single planes of the state's fields as scalar series (spd_model_projtape_*; kernel: projtape.hip)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-constexpr int kProjMaxPatterns = 64, kProjMaxEntries = 1024;
-const char *const kProjOff = "no projection tape configured (spd_model_projtape_configure)";
-}  // namespace
-
-// the sample of members [first, first + count): the front end into the recorder's own slab, then every entry's sum into ring slot
-// (n - 1) % capacity
-static hipError_t projtape_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
-    const spd_model::ProjTape &pt = m->projtape;
-    const size_t per_slot = static_cast<size_t>(m->M) * pt.entries.size();
-    hipError_t e = sample_front(m, pt, first, count, s);
-    if (e == hipSuccess)
-        e = run_projtape_sample(pt.planes, pt.nplanes, pt.items, pt.weights, pt.slab, pt.slab_fields,
-                                pt.data + static_cast<size_t>(pt.ring.slot(n)) * per_slot, static_cast<int>(pt.entries.size()), first, count,
-                                m->stored32 ? 1 : 0, s);
-    return e;
-}
-
-int spd_model_projtape_configure(spd_model_handle m, const double *weights, int n_patterns, const char *const *names, const int *levels,
-                                 const int *patterns, int n_entries, int every, int capacity) {
-    const char *who = "spd_model_projtape_configure";
-    // (the arguments first, in the header's order: nothing in this block needs the device or a model; n_entries = 0 is "off")
-    std::vector<spd_model::ProjTape::Entry> entries;
-    if (n_entries != 0) {
-        if (every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-        if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-        if (n_patterns < 1 || n_patterns > kProjMaxPatterns)
-            return m_fail(SPD_E_ARG, std::string(who) + ": n_patterns must be 1 ... " + std::to_string(kProjMaxPatterns) + ", got " +
-                                         std::to_string(n_patterns));
-        if (n_entries < 0 || n_entries > kProjMaxEntries)
-            return m_fail(SPD_E_ARG, std::string(who) + ": n_entries must be 0 ... " + std::to_string(kProjMaxEntries) + ", got " +
-                                         std::to_string(n_entries));
-        if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
-        if (!names || !levels || !patterns) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
-        for (int p = 0; p < n_patterns; ++p)
-            for (int q = 0; q < NG; ++q)
-                if (!std::isfinite(weights[static_cast<size_t>(p) * NG + q]))
-                    return m_fail(SPD_E_ARG, std::string(who) + ": weight of pattern " + std::to_string(p) + " at point " + std::to_string(q) +
-                                                 " (row " + std::to_string(q / IX) + ", column " + std::to_string(q % IX) + ") is not finite");
-        for (int k = 0; k < n_entries; ++k) {
-            const int id = names[k] ? stats_id(names[k]) : -1;
-            if (id < 0)
-                return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                             "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                             "q_plev, z_plev, mslp)");
-            entries.push_back({id, levels[k], patterns[k]});
-        }
-        // (a level is checked here against the name's fixed count; a pressure-level name's count is the model's, below)
-        for (int k = 0; k < n_entries; ++k) {
-            const int fixed = kStatsCatalogue[entries[k].name].levels;
-            if (levels[k] < 0 || (fixed > 0 && levels[k] >= fixed))
-                return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
-                                             names[k] + "') is out of range" + (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
-            if (patterns[k] < 0 || patterns[k] >= n_patterns)
-                return m_fail(SPD_E_ARG, std::string(who) + ": pattern " + std::to_string(patterns[k]) + " of entry " + std::to_string(k) + " ('" +
-                                             names[k] + "') is out of range (0 ... " + std::to_string(n_patterns - 1) + ")");
-        }
-    }
-    if (int rc = configure_allowed(m, who)) return rc;
-    for (int k = 0; k < n_entries; ++k) {
-        if (entries[k].name < kPlevFirst) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
-        if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-        if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
-                                         names[k] + "') is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
-    }
-    spd_model::ProjTape &pt = m->projtape;
-    if (int rc = retire(m, pt)) return rc;
-    if (n_entries == 0) return SPD_OK;  // off
-    spd_model::ProjTape next;
-    next.every = every;
-    next.npatterns = n_patterns;
-    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity), E = static_cast<size_t>(n_entries);
-    // the sample plan: the names among the entries in the order they first appear (the front end transforms a name's every level)
-    std::vector<int> ids;
-    for (const auto &e : entries)
-        if (std::find(ids.begin(), ids.end(), e.name) == ids.end()) ids.push_back(e.name);
-    SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    // the distinct planes in the order they first appear, and the entries sorted by plane (stable: the caller's order within a plane)
-    std::vector<std::pair<int, int>> distinct;  // (name, level)
-    std::vector<int> plane_of(E);
-    for (size_t k = 0; k < E; ++k) {
-        const std::pair<int, int> key{entries[k].name, entries[k].level};
-        const auto at = std::find(distinct.begin(), distinct.end(), key);
-        plane_of[k] = static_cast<int>(at - distinct.begin());
-        if (at == distinct.end()) distinct.push_back(key);
-    }
-    // one allocation: ring | patterns | slab | tables[2] | plane descriptors | entry list
-    const size_t per_slot = M * E * sizeof(double);
-    if (slots > (static_cast<size_t>(-1) / 2) / per_slot) return m_fail(SPD_E_ARG, std::string(who) + ": the size of the series does not fit size_t");
-    const size_t ring = sample_up(slots * per_slot), maps = sample_up(static_cast<size_t>(n_patterns) * NG * sizeof(double));
-    const size_t desc = sample_up(distinct.size() * sizeof(ProjTapePlane)), list = sample_up(E * sizeof(ProjTapeItem));
-    const size_t total = ring + maps + plan.slab_bytes + 2 * plan.table_bytes + desc + list;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // the projection tape is off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the projection tape (" + std::to_string(total) +
-                                        " bytes asked for: " + std::to_string(capacity) + " samples of " + std::to_string(per_slot) +
-                                        " bytes); the projection tape is off");
-    }
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.data = carve.take<double>(ring);
-    next.weights = carve.take<double>(maps);
-    carve_front(carve, plan, next);
-    next.planes = carve.take<ProjTapePlane>(desc);
-    next.items = carve.take<ProjTapeItem>(list);
-    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
-    std::vector<ProjTapePlane> host_planes;
-    std::vector<ProjTapeItem> host_items;
-    for (size_t q = 0; q < distinct.size(); ++q) {
-        const int id = distinct[q].first, level = distinct[q].second;
-        const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
-        ProjTapePlane d{};
-        d.slab_plane = slab_plane[var->first_plane + static_cast<size_t>(level)];
-        d.src = id == 6 ? static_cast<const void *>(m->pa.precnv) : id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-        d.unit = kStatsCatalogue[id].unit;
-        d.first = static_cast<int>(host_items.size());
-        for (size_t k = 0; k < E; ++k)
-            if (plane_of[k] == static_cast<int>(q)) host_items.push_back({entries[k].pattern, static_cast<int>(k)});
-        d.count = static_cast<int>(host_items.size()) - d.first;
-        host_planes.push_back(d);
-    }
-    if (e == hipSuccess) e = hipMemcpy(next.weights, weights, static_cast<size_t>(n_patterns) * NG * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(ProjTapePlane), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(next.items, host_items.data(), host_items.size() * sizeof(ProjTapeItem), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.nplanes = static_cast<int>(host_planes.size());
-    next.entries = std::move(entries);
-    next.ring = SampleRing(capacity, 6);
-    next.on = true;
-    pt = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_projtape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: null model");
-    if (!m->projtape.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_reset: ") + kProjOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: a checked multi-step call is in flight; end it first");
-    m->projtape.ring.clear();
-    m->projtape.validity.clear();
-    return SPD_OK;
-}
-
-int spd_model_projtape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *n_patterns, int *n_entries) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_info: null model");
-    const spd_model::ProjTape &pt = m->projtape;
-    if (!pt.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_info: ") + kProjOff);
-    if (taken) *taken = pt.ring.taken;
-    if (held) *held = static_cast<int>(pt.ring.held());
-    if (capacity) *capacity = pt.ring.capacity;
-    if (every) *every = pt.every;
-    if (n_patterns) *n_patterns = pt.npatterns;
-    if (n_entries) *n_entries = static_cast<int>(pt.entries.size());
-    return SPD_OK;
-}
-
-int spd_model_projtape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_times: null model");
-    const spd_model::ProjTape &pt = m->projtape;
-    if (!pt.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_times: ") + kProjOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_projtape_times: bad destination");
-    return pt.ring.copy_rows(rows, max_rows);
-}
-
-int spd_model_projtape_read(spd_model_handle m, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_projtape_read";
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    const spd_model::ProjTape &pt = m->projtape;
-    if (int rc = read_allowed(m, who, pt.on, kProjOff, pt.validity, "the projection tape is invalid until spd_model_projtape_reset")) return rc;
-    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
-    if (int rc = held_range(who, pt.ring, t0, nt, "sample")) return rc;
-    const size_t per = pt.entries.size();
-    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
-    if (count == 0 || nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    // (the ring is [slot][M][E] as a spectra ring is [slot][M][per]: the same gather)
-    const hipError_t e = run_spectra_gather(pt.data + static_cast<size_t>(first) * per, static_cast<double *>(dst_device), static_cast<int>(per),
-                                            static_cast<long>(static_cast<size_t>(m->M) * per), count, nt, pt.ring.slot_of_held(t0),
-                                            pt.ring.capacity, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// nudging: relaxation of the spectral state toward target fields (spd_model_nudge_*; kernel: nudge.hip; step loop: step_impl)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-constexpr int kNudgeNames = 5, kNudgeGains = 32, kNudgeRows = 8;  // gains: [n_names][8][32]; ps reads row 0 of its eight
-const char *const kNudgeName[kNudgeNames] = {"vor", "div", "t", "tr", "ps"};
-const char *const kNudgeOff = "no nudging configured (spd_model_nudge_configure)";
-int nudge_name_id(const char *name) {
-    for (int v = 0; name && v < kNudgeNames; ++v)
-        if (std::strcmp(name, kNudgeName[v]) == 0) return v;
-    return -1;
-}
-int nudge_levels(int id) { return id == 4 ? 1 : 8; }
-}  // namespace
-
-int spd_model_nudge_configure(spd_model_handle m, const char *const *names, int n_names, const double *gains, const int32_t *member_mask,
-                              int capacity, int in_loop) {
-    const char *who = "spd_model_nudge_configure";
-    // (the arguments first, in the header's order: nothing below needs the device)
-    if (n_names < 0 || n_names > kNudgeNames || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of names");
-    std::vector<int> ids;
-    for (int k = 0; k < n_names; ++k) {
-        const int id = nudge_name_id(names[k]);
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") + "' (vor, div, t, tr, ps)");
-        ids.push_back(id);
-    }
-    for (int k = 0; k < n_names; ++k)
-        for (int j = 0; j < k; ++j)
-            if (ids[j] == ids[k]) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' named twice");
-    if (n_names > 0) {
-        if (!gains) return m_fail(SPD_E_ARG, std::string(who) + ": null gains");
-        for (int k = 0; k < n_names; ++k)
-            for (int lev = 0; lev < nudge_levels(ids[k]); ++lev)
-                for (int l = 0; l < kNudgeGains; ++l) {
-                    const double g = gains[(static_cast<size_t>(k) * kNudgeRows + lev) * kNudgeGains + l];
-                    if (!std::isfinite(g) || g < 0.0 || g > 1.0)
-                        return m_fail(SPD_E_ARG, std::string(who) + ": the gain of '" + names[k] + "' at level " + std::to_string(lev) +
-                                                     ", wavenumber " + std::to_string(l) + " is not a finite number in [0, 1]");
-                }
-        if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-        if (in_loop != 0 && in_loop != 1) return m_fail(SPD_E_ARG, std::string(who) + ": in_loop must be 0 or 1");
-    }
-    if (int rc = configure_allowed(m, who)) return rc;
-    for (int i = 0; n_names > 0 && member_mask && i < m->M; ++i)
-        if (member_mask[i] != 0 && member_mask[i] != 1)
-            return m_fail(SPD_E_ARG, std::string(who) + ": the mask entry of member " + std::to_string(i) + " is neither 0 nor 1");
-    spd_model::Nudge &nd = m->nudge;
-    if (int rc = retire(m, nd)) return rc;
-    if (n_names == 0) return SPD_OK;  // off
-    spd_model::Nudge next;
-    next.capacity = capacity;
-    next.in_loop = in_loop != 0;
-    next.names = ids;
-    // the planes some gain of which is not zero: [name in the caller's order][level]
-    struct Row {
-        int id, lev;
-        const double *gain;
-    };
-    std::vector<Row> rows;
-    size_t target_doubles = 0;
-    for (int k = 0; k < n_names; ++k) {
-        next.offset[ids[k]] = target_doubles;
-        const size_t per_slot = static_cast<size_t>(nudge_levels(ids[k])) * NSPEC * C;
-        if (static_cast<size_t>(capacity) > (static_cast<size_t>(-1) / 16) / per_slot)
-            return m_fail(SPD_E_ARG, std::string(who) + ": the target slots' size does not fit size_t");
-        target_doubles += static_cast<size_t>(capacity) * per_slot;
-        for (int lev = 0; lev < nudge_levels(ids[k]); ++lev) {
-            const double *g = gains + (static_cast<size_t>(k) * kNudgeRows + lev) * kNudgeGains;
-            if (std::any_of(g, g + kNudgeGains, [](double x) { return x != 0.0; })) rows.push_back({ids[k], lev, g});
-        }
-    }
-    // one allocation: target slots | gain rows | plane descriptors | member mask
-    const size_t targets = sample_up(target_doubles * sizeof(double)), gain_bytes = sample_up(rows.size() * kNudgeGains * sizeof(double));
-    const size_t desc = sample_up(rows.size() * sizeof(NudgePlane)), mask_bytes = member_mask ? sample_up(sizeof(int) * m->M) : 0;
-    const size_t total = targets + gain_bytes + desc + mask_bytes;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // nudging is off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the target slots (" + std::to_string(total) + " bytes asked for: " +
-                                        std::to_string(capacity) + " slots); nudging is off");
-    }
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.targets = carve.take<double>(targets);
-    double *gain_dev = carve.take<double>(gain_bytes);
-    next.planes = carve.take<NudgePlane>(desc);
-    next.mask = member_mask ? carve.take<int>(mask_bytes) : nullptr;
-    std::vector<NudgePlane> host_planes;
-    std::vector<double> host_gains;
-    double *const base[kNudgeNames] = {m->P.vor, m->P.div, m->P.t, m->P.tr, m->P.ps};
-    for (const Row &r : rows) {
-        const size_t levels = static_cast<size_t>(nudge_levels(r.id)), plane = static_cast<size_t>(r.lev) * NSPEC * C;
-        NudgePlane d{};
-        d.state = base[r.id] + plane;
-        d.target = next.targets + next.offset[r.id] + plane;
-        d.gain = gain_dev + host_gains.size();
-        d.member_stride = static_cast<long>(2 * levels * NSPEC * C);
-        d.level_stride = static_cast<long>(levels * NSPEC * C);
-        d.slot_stride = static_cast<long>(levels * NSPEC * C);
-        host_planes.push_back(d);
-        host_gains.insert(host_gains.end(), r.gain, r.gain + kNudgeGains);
-    }
-    hipError_t e = hipMemset(next.targets, 0, targets);
-    if (e == hipSuccess && !rows.empty()) e = hipMemcpy(gain_dev, host_gains.data(), host_gains.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !rows.empty()) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(NudgePlane), hipMemcpyHostToDevice);
-    if (e == hipSuccess && member_mask) e = hipMemcpy(next.mask, member_mask, sizeof(int) * m->M, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.nplanes = static_cast<int>(host_planes.size());
-    next.on = true;
-    nd = std::move(next);
-    return SPD_OK;
-}
-
-int spd_model_nudge_set_times(spd_model_handle m, const int32_t *steps, int n) {
-    const char *who = "spd_model_nudge_set_times";
-    if (n < 0 || (n > 0 && !steps)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of steps");
-    for (int k = 1; k < n; ++k)
-        if (steps[k] <= steps[k - 1]) return m_fail(SPD_E_ARG, std::string(who) + ": the stamps must be strictly ascending (slot " + std::to_string(k) + ")");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    spd_model::Nudge &nd = m->nudge;
-    if (!nd.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kNudgeOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (n > nd.capacity)
-        return m_fail(SPD_E_ARG, std::string(who) + ": " + std::to_string(n) + " stamps for " + std::to_string(nd.capacity) + " slots");
-    nd.stamps.assign(steps, steps + n);  // (host state only: the steps already issued carry their slots and weight by value)
-    nd.in_use = n;
-    return SPD_OK;
-}
-
-int spd_model_nudge_set_target(spd_model_handle m, int slot, const char *name, const void *host, size_t bytes) {
-    const char *who = "spd_model_nudge_set_target";
-    if (!name || !host) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const int id = nudge_name_id(name);
-    if (id < 0) return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + name + "' (vor, div, t, tr, ps)");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    const spd_model::Nudge &nd = m->nudge;
-    if (!nd.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kNudgeOff);
-    if (std::find(nd.names.begin(), nd.names.end(), id) == nd.names.end())
-        return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured names");
-    if (slot < 0 || slot >= nd.capacity)
-        return m_fail(SPD_E_ARG, std::string(who) + ": slot " + std::to_string(slot) + " of " + std::to_string(nd.capacity));
-    const size_t need = static_cast<size_t>(nudge_levels(id)) * NSPEC * C * sizeof(double);
-    if (bytes != need) return m_fail(SPD_E_SIZE, std::string(who) + ": a slot of '" + name + "' needs exactly " + std::to_string(need) + " bytes");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    // a blocking copy on the null stream, which does not order against the streams the steps were issued on (as spd_model_set)
-    M_HIP(hipDeviceSynchronize());
-    M_HIP(hipMemcpy(nd.targets + nd.offset[id] + static_cast<size_t>(slot) * (need / sizeof(double)), host, need, hipMemcpyHostToDevice));
-    return SPD_OK;
-}
-
-int spd_model_nudge_apply(spd_model_handle m, int first, int count, void *stream) {
-    const char *who = "spd_model_nudge_apply";
-    if (int rc = member_range(m, first, count, who)) return rc;
-    spd_model::Nudge &nd = m->nudge;
-    if (!nd.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kNudgeOff);
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (nd.in_use == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target slot is in use (spd_model_nudge_set_times)");
-    M_HIP(hipSetDevice(m->ctx->device));
-    if (int rc = settle_deferred_check(m)) return rc;  // (a range check that was put off looks at the state as it is NOW)
-    if (nd.nplanes == 0 || count == 0) return SPD_OK;
-    m->phi_ahead = false;  // the temperature changes under the look-ahead geopotential; phi itself is the next step's to recompute
-    const NudgeAt at = nudge_at(nd.stamps, m->current_step);
-    const hipError_t e = run_nudge(nd.planes, nd.nplanes, nd.mask, first, count, at.s0, at.s1, at.a, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    ++nd.applied;
-    return SPD_OK;
-}
-
-int spd_model_nudge_info(spd_model_handle m, int *n_names, int *capacity, int *in_use, int *in_loop, long long *applied) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_nudge_info: null model");
-    const spd_model::Nudge &nd = m->nudge;  // (a model without nudging: all zero)
-    if (n_names) *n_names = static_cast<int>(nd.names.size());
-    if (capacity) *capacity = nd.capacity;
-    if (in_use) *in_use = nd.in_use;
-    if (in_loop) *in_loop = nd.in_loop ? 1 : 0;
-    if (applied) *applied = nd.applied;
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// breeding: the perturbation of a bred member against its control rescaled to a fixed amplitude (spd_model_breed_*; kernels:
-// breed.hip; segments of a call: step_impl)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-constexpr int kBreedNames = 5, kBreedRows = 8;  // weights: [5][8] for vor, div, t, tr, ps; ps reads entry 0 of its row
-const char *const kBreedName[kBreedNames] = {"vor", "div", "t", "tr", "ps"};
-const char *const kBreedOff = "no breeding configured (spd_model_breed_configure)";
-int breed_levels(int id) { return id == 4 ? 1 : 8; }
-}  // namespace
-
-int spd_breed_check(const int32_t *control, int members, const double *weights, double target, int every, int capacity, int in_loop) {
-    const char *who = "spd_model_breed_configure";
-    for (int i = 0; control && i < members; ++i) {
-        const int c = control[i];
-        if (c == -1) continue;
-        if (c < -1 || c >= members)
-            return m_fail(SPD_E_ARG, std::string(who) + ": the control of member " + std::to_string(i) + " (" + std::to_string(c) + ") is out of range (-1 ... " +
-                                         std::to_string(members - 1) + ")");
-        if (c == i) return m_fail(SPD_E_ARG, std::string(who) + ": member " + std::to_string(i) + " is its own control");
-        if (control[c] != -1)
-            return m_fail(SPD_E_ARG, std::string(who) + ": the control of member " + std::to_string(i) + " (" + std::to_string(c) +
-                                         ") is itself bred: a control must have -1 (no chains)");
-    }
-    if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
-    bool some = false;
-    for (int v = 0; v < kBreedNames; ++v)
-        for (int k = 0; k < breed_levels(v); ++k) {
-            const double w = weights[v * kBreedRows + k];
-            if (!std::isfinite(w) || w < 0.0)
-                return m_fail(SPD_E_ARG, std::string(who) + ": the weight of '" + kBreedName[v] + "' at level " + std::to_string(k) +
-                                             " is not a finite number >= 0");
-            some = some || w > 0.0;
-        }
-    if (!some) return m_fail(SPD_E_ARG, std::string(who) + ": all weights are zero");
-    if (!std::isfinite(target) || !(target > 0.0)) return m_fail(SPD_E_ARG, std::string(who) + ": target must be a finite number > 0");
-    if (every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
-    if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
-    if (in_loop != 0 && in_loop != 1) return m_fail(SPD_E_ARG, std::string(who) + ": in_loop must be 0 or 1");
-    return SPD_OK;
-}
-
-int spd_model_breed_configure(spd_model_handle m, const int32_t *control, const double *weights, double target, int every, int capacity,
-                              int in_loop) {
-    const char *who = "spd_model_breed_configure";
-    // (the arguments first: what does not need the member count, then the model, then the controls)
-    if (control)
-        if (int rc = spd_breed_check(nullptr, 0, weights, target, every, capacity, in_loop)) return rc;
-    if (int rc = configure_allowed(m, who)) return rc;
-    if (control)
-        if (int rc = spd_breed_check(control, m->M, weights, target, every, capacity, in_loop)) return rc;
-    spd_model::Breed &br = m->breed;
-    if (int rc = retire(m, br)) return rc;
-    if (!control) return SPD_OK;  // off
-    spd_model::Breed next;
-    next.in_loop = in_loop != 0;
-    next.every = every;
-    next.target = target;
-    const size_t M = static_cast<size_t>(m->M);
-    std::vector<BreedPair> pairs;
-    std::vector<int> slot_of(M, -1);
-    for (int i = 0; i < m->M; ++i)
-        if (control[i] >= 0) {
-            slot_of[i] = static_cast<int>(pairs.size());
-            pairs.push_back({i, control[i]});
-        }
-    next.nbred = static_cast<int>(pairs.size());
-    if (static_cast<size_t>(capacity) > (static_cast<size_t>(-1) / 64) / M)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the ring's size does not fit size_t");
-    std::vector<BreedPlane> planes;
-    double *const base[kBreedNames] = {m->P.vor, m->P.div, m->P.t, m->P.tr, m->P.ps};
-    for (int v = 0; v < kBreedNames; ++v)
-        for (int k = 0; k < breed_levels(v); ++k) {
-            const size_t levels = static_cast<size_t>(breed_levels(v));
-            BreedPlane d{};
-            d.state = base[v] + static_cast<size_t>(k) * NSPEC * C;
-            d.member_stride = static_cast<long>(2 * levels * NSPEC * C);
-            d.level_stride = static_cast<long>(levels * NSPEC * C);
-            d.weight = weights[v * kBreedRows + k];
-            d.kinetic = v < 2 ? 1 : 0;
-            planes.push_back(d);
-        }
-    // one allocation: plane descriptors | pairs | each member's index among the pairs | partial norms | ring
-    const size_t plane_bytes = sample_up(planes.size() * sizeof(BreedPlane)), pair_bytes = sample_up(std::max<size_t>(pairs.size(), 1) * sizeof(BreedPair));
-    const size_t slot_bytes = sample_up(M * sizeof(int)), partial_bytes = sample_up(std::max<size_t>(pairs.size(), 1) * kBreedPlanes * sizeof(double));
-    const size_t ring_doubles = static_cast<size_t>(capacity) * 2 * M, ring_bytes = sample_up(ring_doubles * sizeof(double));
-    const size_t total = plane_bytes + pair_bytes + slot_bytes + partial_bytes + ring_bytes;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {  // breeding is off; the model is as usable as before
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the ring (" + std::to_string(total) + " bytes asked for: " +
-                                        std::to_string(capacity) + " events); breeding is off");
-    }
-    Carve carve{static_cast<char *>(p)};
-    next.alloc = p;
-    next.planes = carve.take<BreedPlane>(plane_bytes);
-    next.pairs = carve.take<BreedPair>(pair_bytes);
-    next.slot_of = carve.take<int>(slot_bytes);
-    next.partial = carve.take<double>(partial_bytes);
-    next.data = carve.take<double>(ring_bytes);
-    std::vector<double> ring(ring_doubles);  // what a member that is not bred shows: amplitude 0.0, factor 1.0
-    for (size_t slot = 0; slot < static_cast<size_t>(capacity); ++slot) {
-        std::fill(ring.begin() + slot * 2 * M, ring.begin() + slot * 2 * M + M, 0.0);
-        std::fill(ring.begin() + slot * 2 * M + M, ring.begin() + (slot + 1) * 2 * M, 1.0);
-    }
-    hipError_t e = hipMemcpy(next.planes, planes.data(), planes.size() * sizeof(BreedPlane), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !pairs.empty()) e = hipMemcpy(next.pairs, pairs.data(), pairs.size() * sizeof(BreedPair), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(next.slot_of, slot_of.data(), M * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(next.partial, 0, partial_bytes);
-    if (e == hipSuccess) e = hipMemcpy(next.data, ring.data(), ring_doubles * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return upload_failed(who, e, p);
-    next.ring = SampleRing(capacity, 6);
-    next.on = true;
-    br = std::move(next);
-    return SPD_OK;
-}
-
-// The rescale of all bred members on the state as it stands, on stream s: the norm launch, the rescale launch behind it, one slot
-// of the ring.  What the model derived from the state is dropped as spd_model_set drops it (the look-ahead geopotential, the day's
-// interpolated climatologies); a range check that was put off looks at the state as it is now and goes out first.
-static int breed_rescale(spd_model *m, hipStream_t s, const char *who) {
-    spd_model::Breed &br = m->breed;
-    if (br.nbred == 0) return SPD_OK;
-    if (int rc = settle_deferred_check(m)) return rc;
-    m->surf_cache_valid = m->phi_ahead = false;
-    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>(br.ring.slot(br.ring.taken + 1));
-    double *amplitude = br.data + slot * 2 * M;
-    hipError_t e = run_breed_norm(br.planes, br.pairs, br.nbred, m->ctx->dev.elm2, br.partial, s);
-    if (e == hipSuccess) e = run_breed_rescale(br.planes, br.pairs, br.nbred, br.partial, br.target, amplitude, amplitude + M, s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": breeding: " + hipGetErrorString(e));
-    }
-    ++br.ring.taken;
-    br.ring.stamp(br.ring.taken, m->current_step, m->cal);
-    ++br.applied;
-    return SPD_OK;
-}
-
-int spd_model_breed_apply(spd_model_handle m, void *stream) {
-    const char *who = "spd_model_breed_apply";
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (!m->breed.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kBreedOff);
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    M_HIP(hipSetDevice(m->ctx->device));
-    return breed_rescale(m, static_cast<hipStream_t>(stream), who);
-}
-
-int spd_model_breed_compute(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_breed_compute";
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    const spd_model::Breed &br = m->breed;
-    if (!br.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kBreedOff);
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    const size_t need = static_cast<size_t>(m->M) * sizeof(double);
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
-    M_HIP(hipSetDevice(m->ctx->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = run_breed_norm(br.planes, br.pairs, br.nbred, m->ctx->dev.elm2, br.partial, s);
-    if (e == hipSuccess) e = run_breed_amplitude(br.planes, br.slot_of, m->M, br.partial, static_cast<double *>(dst_device), s);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    return SPD_OK;
-}
-
-int spd_model_breed_read(spd_model_handle m, int what, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_breed_read";
-    if (what != 0 && what != 1) return m_fail(SPD_E_ARG, std::string(who) + ": what is 0 (amplitude) or 1 (factor)");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    const spd_model::Breed &br = m->breed;
-    if (!br.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kBreedOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    if (int rc = held_range(who, br.ring, t0, nt, "event")) return rc;
-    const size_t M = static_cast<size_t>(m->M), need = static_cast<size_t>(nt) * M * sizeof(double);
-    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
-    if (nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    // (the spectra's gather with one "member" whose entry is the M values of a slot: dst[t][i] = ring[slot(t)][what][i])
-    const hipError_t e = run_spectra_gather(br.data + static_cast<size_t>(what) * M, static_cast<double *>(dst_device), m->M, static_cast<long>(2 * M), 1, nt,
-                                            br.ring.slot_of_held(t0), br.ring.capacity, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
-}
-
-int spd_model_breed_rows(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_rows: null model");
-    const spd_model::Breed &br = m->breed;
-    if (!br.on) return m_fail(SPD_E_ARG, std::string("spd_model_breed_rows: ") + kBreedOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_breed_rows: bad destination");
-    return br.ring.copy_rows(rows, max_rows);
-}
-
-int spd_model_breed_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_reset: null model");
-    if (!m->breed.on) return m_fail(SPD_E_ARG, std::string("spd_model_breed_reset: ") + kBreedOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_breed_reset: a checked multi-step call is in flight; end it first");
-    m->breed.ring.clear();
-    return SPD_OK;
-}
-
-int spd_model_breed_info(spd_model_handle m, int *bred, int *every, int *capacity, long long *taken, int *in_loop, long long *applied) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_info: null model");
-    const spd_model::Breed &br = m->breed;  // (a model without breeding: all zero)
-    if (bred) *bred = br.nbred;
-    if (every) *every = br.every;
-    if (capacity) *capacity = br.ring.capacity;
-    if (taken) *taken = br.ring.taken;
-    if (in_loop) *in_loop = br.in_loop ? 1 : 0;
-    if (applied) *applied = br.applied;
-    return SPD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// pressure-level fields and mean sea-level pressure (spd_model_plev_*; kernel: plev.hip)
-// ---------------------------------------------------------------------------------------------------------------
-static int plev_id(const char *name) {
-    const int id = name ? stats_id(name) : -1;
-    return id >= kPlevFirst ? id - kPlevFirst : -1;
-}
-
-int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n) {
-    const char *who = "spd_model_plev_configure";
-    if (n < 0 || (n > 0 && !levels_pa)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of levels");
-    if (n > kPlevMaxLevels) return m_fail(SPD_E_ARG, std::string(who) + ": at most " + std::to_string(kPlevMaxLevels) + " levels");
-    for (int j = 0; j < n; ++j)
-        if (!(levels_pa[j] > 0.0) || !std::isfinite(levels_pa[j]))
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(j) + " is not a positive pressure (Pa)");
-    bool up = true, down = true;
-    for (int j = 1; j < n; ++j) {
-        up = up && levels_pa[j] > levels_pa[j - 1];
-        down = down && levels_pa[j] < levels_pa[j - 1];
-    }
-    if (!up && !down) return m_fail(SPD_E_ARG, std::string(who) + ": the levels must be strictly increasing or strictly decreasing");
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (m->stats.on && m->stats.plev.mask)
-        return m_fail(SPD_E_ARG, std::string(who) + ": statistics of a pressure-level variable are configured; switch them off first "
-                                                    "(spd_model_stats_configure)");
-    if (m->tape.on && m->tape.plev.mask)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the tape holds a pressure-level variable; switch it off first (spd_model_tape_configure)");
-    if (m->enstape.on && m->enstape.plev.mask)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape holds a pressure-level variable; switch it off first "
-                                                    "(spd_model_enstape_configure)");
-    if (m->wintape.on && m->wintape.plev.mask)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the window tape holds a pressure-level variable; switch it off first "
-                                                    "(spd_model_wintape_configure)");
-    if (m->projtape.on && m->projtape.plev.mask)
-        return m_fail(SPD_E_ARG, std::string(who) + ": the projection tape holds a pressure-level variable; switch it off first "
-                                                    "(spd_model_projtape_configure)");
-    spd_model::Plev &pl = m->plev;
-    pl.n = n;
-    for (int j = 0; j < kPlevMaxLevels; ++j) {
-        pl.levels[j] = j < n ? levels_pa[j] : 0.0;
-        pl.lnp[j] = j < n ? std::log(levels_pa[j]) : 0.0;
-    }
-    for (bool &h : pl.have) h = false;  // (results of the previous levels are not handed out under the new ones)
-    return SPD_OK;
-}
-
-int spd_model_plev_levels(spd_model_handle m, double *out, int cap) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_plev_levels: null model");
-    if (cap < 0 || (cap > 0 && !out)) return m_fail(SPD_E_ARG, "spd_model_plev_levels: bad destination");
-    for (int j = 0; j < m->plev.n && j < cap; ++j) out[j] = m->plev.levels[j];
-    return m->plev.n;
-}
-
-int spd_model_plev_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, int refresh, void *stream) {
-    const char *who = "spd_model_plev_compute";
-    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
-    int mask = n_names == 0 ? (1 << PLEV_NVARS) - 1 : 0;
-    for (int k = 0; k < n_names; ++k) {
-        const int id = plev_id(names[k]);
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_plev, v_plev, t_plev, q_plev, z_plev, mslp)");
-        mask |= 1 << id;
-    }
-    if (int rc = member_range(m, first, count, who)) return rc;
-    spd_model::Plev &pl = m->plev;
-    if (pl.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target levels configured (spd_model_plev_configure)");
-    M_HIP(hipSetDevice(m->ctx->device));
-    const size_t M = static_cast<size_t>(m->M);
-    for (int v = 0; v < PLEV_NVARS; ++v) {
-        const int levels = v == PLEV_MSLP ? 1 : pl.n;
-        if (!(mask >> v & 1) || pl.cap[v] >= levels) continue;
-        if (int rc = dalloc(m, M * levels * NG, &pl.out[v])) return rc;
-        pl.cap[v] = levels;
-    }
-    if (count == 0) return SPD_OK;
-    if (refresh)
-        if (int rc = spd_model_spectral2grid(m, first, count, stream)) return rc;
-    PlevArgs a{};
-    const double *in[5] = {m->u_grid, m->v_grid, m->t_grid, m->q_grid, m->phi_grid};
-    for (int x = 0; x < 5; ++x) {
-        a.in[x] = in[x];
-        a.in_stride[x] = static_cast<long>(KX) * NG;
-    }
-    a.ps = m->ps_grid;
-    a.ps_stride = NG;
-    a.phis0 = m->pa.phis0;
-    for (int v = 0; v < PLEV_NVARS; ++v) {
-        a.out[v] = pl.out[v];
-        a.out_stride[v] = static_cast<long>(v == PLEV_MSLP ? 1 : pl.n) * NG;
-    }
-    a.mask = mask;
-    a.raw = 0;
-    a.n = pl.n;
-    a.first = first;
-    std::copy(pl.lnp, pl.lnp + kPlevMaxLevels, a.lnp);
-    const hipError_t e = run_plev(a, count, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    for (int v = 0; v < PLEV_NVARS; ++v) pl.have[v] = pl.have[v] || (mask >> v & 1);
-    return SPD_OK;
-}
-
-int spd_model_plev_read(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes, void *stream) {
-    const char *who = "spd_model_plev_read";
-    if (!name || !dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
-    const int v = plev_id(name);
-    if (v < 0) return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + name + "' (u_plev, v_plev, t_plev, q_plev, z_plev, mslp)");
-    if (int rc = member_range(m, first, count, who)) return rc;
-    const spd_model::Plev &pl = m->plev;
-    if (pl.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target levels configured (spd_model_plev_configure)");
-    if (!pl.have[v]) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' has not been computed at these levels (spd_model_plev_compute)");
-    const size_t per = static_cast<size_t>(v == PLEV_MSLP ? 1 : pl.n) * NG, need = static_cast<size_t>(count) * per * sizeof(double);
-    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
-    if (count == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    M_HIP(hipMemcpyAsync(dst_device, pl.out[v] + static_cast<size_t>(first) * per, need, hipMemcpyDeviceToDevice,
-                         static_cast<hipStream_t>(stream)));
     return SPD_OK;
 }
 

@@ -1,8 +1,10 @@
 // Nudging: operator-split Newtonian relaxation of the spectral state toward target fields, behind a model step inside the device
-// loop or once on the state as it stands (nudge.hip holds the kernel, model.hip the schedule, the configuration and the C ABI:
+// loop or once on the state as it stands (nudge.hip holds the kernel, the schedule, the configuration and the C ABI:
 // spd_model_nudge_* of include/pyspeedy_amd.h; the definition is DESIGN section 4h).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <vector>
 
 namespace spd {
 
@@ -23,5 +25,14 @@ struct NudgePlane {
 // (1: nudged, 0: left alone) or null for all.
 hipError_t run_nudge(const NudgePlane *planes, int nplanes, const int *mask, int first, int count, int s0, int s1, double a,
                      hipStream_t s);
+
+// Nudging: which target the state is relaxed toward when the step counter stands at n -- the slots that bracket n and the weight
+// of the second, a = (n - s0) / (s1 - s0) in fp64.  Before the first stamp the first slot, at or after the last stamp the last
+// one, at a slot's own stamp that slot: s1 == s0 then, and the kernel takes T = T0 without the interpolation line.
+struct NudgeAt {
+    int s0, s1;
+    double a;
+};
+NudgeAt nudge_at(const std::vector<int> &stamps, int n);
 
 }  // namespace spd

@@ -11,13 +11,13 @@
 
 #include <cmath>
 
+#include "model_state.hpp"
 #include "plev.hpp"
 #include "vertical_consts.hpp"
 
 namespace spd {
 
 namespace {
-constexpr int NG = IX * IL;
 constexpr int kT = 256;
 
 struct LayerRecip {
@@ -120,3 +120,127 @@ hipError_t run_plev(const PlevArgs &args, int count, hipStream_t s) {
 }
 
 }  // namespace spd
+
+// ---- host side: the configuration and the C ABI (spd_model_plev_*) ----
+
+static int plev_id(const char *name) {
+    const int id = name ? stats_id(name) : -1;
+    return id >= kPlevFirst ? id - kPlevFirst : -1;
+}
+
+extern "C" {
+
+int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n) {
+    const char *who = "spd_model_plev_configure";
+    if (n < 0 || (n > 0 && !levels_pa)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of levels");
+    if (n > kPlevMaxLevels) return m_fail(SPD_E_ARG, std::string(who) + ": at most " + std::to_string(kPlevMaxLevels) + " levels");
+    for (int j = 0; j < n; ++j)
+        if (!(levels_pa[j] > 0.0) || !std::isfinite(levels_pa[j]))
+            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(j) + " is not a positive pressure (Pa)");
+    bool up = true, down = true;
+    for (int j = 1; j < n; ++j) {
+        up = up && levels_pa[j] > levels_pa[j - 1];
+        down = down && levels_pa[j] < levels_pa[j - 1];
+    }
+    if (!up && !down) return m_fail(SPD_E_ARG, std::string(who) + ": the levels must be strictly increasing or strictly decreasing");
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (m->stats.on && m->stats.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": statistics of a pressure-level variable are configured; switch them off first "
+                                                    "(spd_model_stats_configure)");
+    if (m->tape.on && m->tape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the tape holds a pressure-level variable; switch it off first (spd_model_tape_configure)");
+    if (m->enstape.on && m->enstape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_enstape_configure)");
+    if (m->wintape.on && m->wintape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the window tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_wintape_configure)");
+    if (m->projtape.on && m->projtape.plev.mask)
+        return m_fail(SPD_E_ARG, std::string(who) + ": the projection tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_projtape_configure)");
+    spd_model::Plev &pl = m->plev;
+    pl.n = n;
+    for (int j = 0; j < kPlevMaxLevels; ++j) {
+        pl.levels[j] = j < n ? levels_pa[j] : 0.0;
+        pl.lnp[j] = j < n ? std::log(levels_pa[j]) : 0.0;
+    }
+    for (bool &h : pl.have) h = false;  // (results of the previous levels are not handed out under the new ones)
+    return SPD_OK;
+}
+
+int spd_model_plev_levels(spd_model_handle m, double *out, int cap) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_plev_levels: null model");
+    if (cap < 0 || (cap > 0 && !out)) return m_fail(SPD_E_ARG, "spd_model_plev_levels: bad destination");
+    for (int j = 0; j < m->plev.n && j < cap; ++j) out[j] = m->plev.levels[j];
+    return m->plev.n;
+}
+
+int spd_model_plev_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, int refresh, void *stream) {
+    const char *who = "spd_model_plev_compute";
+    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
+    int mask = n_names == 0 ? (1 << PLEV_NVARS) - 1 : 0;
+    for (int k = 0; k < n_names; ++k) {
+        const int id = plev_id(names[k]);
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
+                                         "' (u_plev, v_plev, t_plev, q_plev, z_plev, mslp)");
+        mask |= 1 << id;
+    }
+    if (int rc = member_range(m, first, count, who)) return rc;
+    spd_model::Plev &pl = m->plev;
+    if (pl.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target levels configured (spd_model_plev_configure)");
+    M_HIP(hipSetDevice(m->ctx->device));
+    const size_t M = static_cast<size_t>(m->M);
+    for (int v = 0; v < PLEV_NVARS; ++v) {
+        const int levels = v == PLEV_MSLP ? 1 : pl.n;
+        if (!(mask >> v & 1) || pl.cap[v] >= levels) continue;
+        if (int rc = dalloc(m, M * levels * NG, &pl.out[v])) return rc;
+        pl.cap[v] = levels;
+    }
+    if (count == 0) return SPD_OK;
+    if (refresh)
+        if (int rc = spd_model_spectral2grid(m, first, count, stream)) return rc;
+    PlevArgs a{};
+    const double *in[5] = {m->u_grid, m->v_grid, m->t_grid, m->q_grid, m->phi_grid};
+    for (int x = 0; x < 5; ++x) {
+        a.in[x] = in[x];
+        a.in_stride[x] = static_cast<long>(KX) * NG;
+    }
+    a.ps = m->ps_grid;
+    a.ps_stride = NG;
+    a.phis0 = m->pa.phis0;
+    for (int v = 0; v < PLEV_NVARS; ++v) {
+        a.out[v] = pl.out[v];
+        a.out_stride[v] = static_cast<long>(v == PLEV_MSLP ? 1 : pl.n) * NG;
+    }
+    a.mask = mask;
+    a.raw = 0;
+    a.n = pl.n;
+    a.first = first;
+    std::copy(pl.lnp, pl.lnp + kPlevMaxLevels, a.lnp);
+    const hipError_t e = run_plev(a, count, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    for (int v = 0; v < PLEV_NVARS; ++v) pl.have[v] = pl.have[v] || (mask >> v & 1);
+    return SPD_OK;
+}
+
+int spd_model_plev_read(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_plev_read";
+    if (!name || !dst_device) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    const int v = plev_id(name);
+    if (v < 0) return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + name + "' (u_plev, v_plev, t_plev, q_plev, z_plev, mslp)");
+    if (int rc = member_range(m, first, count, who)) return rc;
+    const spd_model::Plev &pl = m->plev;
+    if (pl.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": no target levels configured (spd_model_plev_configure)");
+    if (!pl.have[v]) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' has not been computed at these levels (spd_model_plev_compute)");
+    const size_t per = static_cast<size_t>(v == PLEV_MSLP ? 1 : pl.n) * NG, need = static_cast<size_t>(count) * per * sizeof(double);
+    if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");
+    if (count == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    M_HIP(hipMemcpyAsync(dst_device, pl.out[v] + static_cast<size_t>(first) * per, need, hipMemcpyDeviceToDevice,
+                         static_cast<hipStream_t>(stream)));
+    return SPD_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Pressure-level fields and mean sea-level pressure from the sigma-level grid fields (plev.hip holds the kernel, model.hip the
+// Pressure-level fields and mean sea-level pressure from the sigma-level grid fields (plev.hip holds the kernel, the
 // configuration and the C ABI: spd_model_plev_* of include/pyspeedy_amd.h; the definition is DESIGN section 4b).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -17,13 +17,13 @@
 #include <hip/hip_runtime.h>
 
 #include "export_unit.hpp"
+#include "model_state.hpp"
 #include "projtape.hpp"
 #include "tables.hpp"
 
 namespace spd {
 
 namespace {
-constexpr int NG = IX * IL;
 constexpr int kT = 256;
 constexpr int kPer = NG / kT;  // 18 points per lane
 constexpr int kBatch = 4;      // entries per barrier: one per wavefront of the workgroup
@@ -89,9 +89,11 @@ __global__ __launch_bounds__(kT) void projtape_kernel(const ProjTapePlane *__res
 }
 }  // namespace
 
-hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const ProjTapeItem *items, const double *weights,
-                               const double *slab, int slab_fields, double *ring_slot, int n_entries, int first, int count,
-                               int store32, hipStream_t s) {
+// One launch for the members [first, first + count), all planes.  weights: [P][4608]; slab: [M][slab_fields][4608] fp64, as the
+// front end left it; store32: the model keeps precnv / precls as float; ring_slot: member 0 of the sample's slot, [M][n_entries].
+static hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const ProjTapeItem *items, const double *weights,
+                                      const double *slab, int slab_fields, double *ring_slot, int n_entries, int first, int count,
+                                      int store32, hipStream_t s) {
     if (nplanes == 0 || count == 0) return hipSuccess;
     hipLaunchKernelGGL(projtape_kernel, dim3(nplanes, count), dim3(kT), 0, s, planes, items, weights, slab, slab_fields, ring_slot,
                        n_entries, first, store32);
@@ -99,3 +101,196 @@ hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const P
 }
 
 }  // namespace spd
+
+// ---- host side: the step loop's sample, the configuration and the C ABI (spd_model_projtape_*) ----
+
+namespace {
+constexpr int kProjMaxPatterns = 64, kProjMaxEntries = 1024;
+const char *const kProjOff = "no projection tape configured (spd_model_projtape_configure)";
+}  // namespace
+
+// the sample of members [first, first + count): the front end into the recorder's own slab, then every entry's sum into ring slot
+// (n - 1) % capacity
+hipError_t spd::projtape_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
+    const spd_model::ProjTape &pt = m->projtape;
+    const size_t per_slot = static_cast<size_t>(m->M) * pt.entries.size();
+    hipError_t e = sample_front(m, pt, first, count, s);
+    if (e == hipSuccess)
+        e = run_projtape_sample(pt.planes, pt.nplanes, pt.items, pt.weights, pt.slab, pt.slab_fields,
+                                pt.data + static_cast<size_t>(pt.ring.slot(n)) * per_slot, static_cast<int>(pt.entries.size()), first, count,
+                                m->stored32 ? 1 : 0, s);
+    return e;
+}
+
+extern "C" {
+
+int spd_model_projtape_configure(spd_model_handle m, const double *weights, int n_patterns, const char *const *names, const int *levels,
+                                 const int *patterns, int n_entries, int every, int capacity) {
+    const char *who = "spd_model_projtape_configure";
+    // (the arguments first, in the header's order: nothing in this block needs the device or a model; n_entries = 0 is "off")
+    std::vector<spd_model::ProjTape::Entry> entries;
+    if (n_entries != 0) {
+        if (every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+        if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+        if (n_patterns < 1 || n_patterns > kProjMaxPatterns)
+            return m_fail(SPD_E_ARG, std::string(who) + ": n_patterns must be 1 ... " + std::to_string(kProjMaxPatterns) + ", got " +
+                                         std::to_string(n_patterns));
+        if (n_entries < 0 || n_entries > kProjMaxEntries)
+            return m_fail(SPD_E_ARG, std::string(who) + ": n_entries must be 0 ... " + std::to_string(kProjMaxEntries) + ", got " +
+                                         std::to_string(n_entries));
+        if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
+        if (!names || !levels || !patterns) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
+        for (int p = 0; p < n_patterns; ++p)
+            for (int q = 0; q < NG; ++q)
+                if (!std::isfinite(weights[static_cast<size_t>(p) * NG + q]))
+                    return m_fail(SPD_E_ARG, std::string(who) + ": weight of pattern " + std::to_string(p) + " at point " + std::to_string(q) +
+                                                 " (row " + std::to_string(q / IX) + ", column " + std::to_string(q % IX) + ") is not finite");
+        for (int k = 0; k < n_entries; ++k) {
+            const int id = names[k] ? stats_id(names[k]) : -1;
+            if (id < 0)
+                return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
+                                             "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
+                                             "q_plev, z_plev, mslp)");
+            entries.push_back({id, levels[k], patterns[k]});
+        }
+        // (a level is checked here against the name's fixed count; a pressure-level name's count is the model's, below)
+        for (int k = 0; k < n_entries; ++k) {
+            const int fixed = kStatsCatalogue[entries[k].name].levels;
+            if (levels[k] < 0 || (fixed > 0 && levels[k] >= fixed))
+                return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
+                                             names[k] + "') is out of range" + (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
+            if (patterns[k] < 0 || patterns[k] >= n_patterns)
+                return m_fail(SPD_E_ARG, std::string(who) + ": pattern " + std::to_string(patterns[k]) + " of entry " + std::to_string(k) + " ('" +
+                                             names[k] + "') is out of range (0 ... " + std::to_string(n_patterns - 1) + ")");
+        }
+    }
+    if (int rc = configure_allowed(m, who)) return rc;
+    for (int k = 0; k < n_entries; ++k) {
+        if (entries[k].name < kPlevFirst) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
+        if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+        if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
+            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
+                                         names[k] + "') is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
+    }
+    spd_model::ProjTape &pt = m->projtape;
+    if (int rc = retire(m, pt)) return rc;
+    if (n_entries == 0) return SPD_OK;  // off
+    spd_model::ProjTape next;
+    next.every = every;
+    next.npatterns = n_patterns;
+    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity), E = static_cast<size_t>(n_entries);
+    // the sample plan: the names among the entries in the order they first appear (the front end transforms a name's every level)
+    std::vector<int> ids;
+    for (const auto &e : entries)
+        if (std::find(ids.begin(), ids.end(), e.name) == ids.end()) ids.push_back(e.name);
+    SamplePlan plan;
+    plan_sample(m, ids, next, plan);
+    // the distinct planes in the order they first appear, and the entries sorted by plane (stable: the caller's order within a plane)
+    std::vector<std::pair<int, int>> distinct;  // (name, level)
+    std::vector<int> plane_of(E);
+    for (size_t k = 0; k < E; ++k) {
+        const std::pair<int, int> key{entries[k].name, entries[k].level};
+        const auto at = std::find(distinct.begin(), distinct.end(), key);
+        plane_of[k] = static_cast<int>(at - distinct.begin());
+        if (at == distinct.end()) distinct.push_back(key);
+    }
+    // one allocation: ring | patterns | slab | tables[2] | plane descriptors | entry list
+    const size_t per_slot = M * E * sizeof(double);
+    if (slots > (static_cast<size_t>(-1) / 2) / per_slot) return m_fail(SPD_E_ARG, std::string(who) + ": the size of the series does not fit size_t");
+    const size_t ring = sample_up(slots * per_slot), maps = sample_up(static_cast<size_t>(n_patterns) * NG * sizeof(double));
+    const size_t desc = sample_up(distinct.size() * sizeof(ProjTapePlane)), list = sample_up(E * sizeof(ProjTapeItem));
+    const size_t total = ring + maps + plan.slab_bytes + 2 * plan.table_bytes + desc + list;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the projection tape is off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the projection tape (" + std::to_string(total) +
+                                        " bytes asked for: " + std::to_string(capacity) + " samples of " + std::to_string(per_slot) +
+                                        " bytes); the projection tape is off");
+    }
+    Carve carve{static_cast<char *>(p)};
+    next.alloc = p;
+    next.data = carve.take<double>(ring);
+    next.weights = carve.take<double>(maps);
+    carve_front(carve, plan, next);
+    next.planes = carve.take<ProjTapePlane>(desc);
+    next.items = carve.take<ProjTapeItem>(list);
+    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
+    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<ProjTapePlane> host_planes;
+    std::vector<ProjTapeItem> host_items;
+    for (size_t q = 0; q < distinct.size(); ++q) {
+        const int id = distinct[q].first, level = distinct[q].second;
+        const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
+        ProjTapePlane d{};
+        d.slab_plane = slab_plane[var->first_plane + static_cast<size_t>(level)];
+        d.src = id == 6 ? static_cast<const void *>(m->pa.precnv) : id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
+        d.unit = kStatsCatalogue[id].unit;
+        d.first = static_cast<int>(host_items.size());
+        for (size_t k = 0; k < E; ++k)
+            if (plane_of[k] == static_cast<int>(q)) host_items.push_back({entries[k].pattern, static_cast<int>(k)});
+        d.count = static_cast<int>(host_items.size()) - d.first;
+        host_planes.push_back(d);
+    }
+    if (e == hipSuccess) e = hipMemcpy(next.weights, weights, static_cast<size_t>(n_patterns) * NG * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(ProjTapePlane), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.items, host_items.data(), host_items.size() * sizeof(ProjTapeItem), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return upload_failed(who, e, p);
+    next.nplanes = static_cast<int>(host_planes.size());
+    next.entries = std::move(entries);
+    next.ring = SampleRing(capacity, 6);
+    next.on = true;
+    pt = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_projtape_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: null model");
+    if (!m->projtape.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_reset: ") + kProjOff);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: a checked multi-step call is in flight; end it first");
+    m->projtape.ring.clear();
+    m->projtape.validity.clear();
+    return SPD_OK;
+}
+
+int spd_model_projtape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *n_patterns, int *n_entries) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_info: null model");
+    const spd_model::ProjTape &pt = m->projtape;
+    if (!pt.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_info: ") + kProjOff);
+    if (taken) *taken = pt.ring.taken;
+    if (held) *held = static_cast<int>(pt.ring.held());
+    if (capacity) *capacity = pt.ring.capacity;
+    if (every) *every = pt.every;
+    if (n_patterns) *n_patterns = pt.npatterns;
+    if (n_entries) *n_entries = static_cast<int>(pt.entries.size());
+    return SPD_OK;
+}
+
+int spd_model_projtape_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_times: null model");
+    const spd_model::ProjTape &pt = m->projtape;
+    if (!pt.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_times: ") + kProjOff);
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_projtape_times: bad destination");
+    return pt.ring.copy_rows(rows, max_rows);
+}
+
+int spd_model_projtape_read(spd_model_handle m, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_projtape_read";
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    const spd_model::ProjTape &pt = m->projtape;
+    if (int rc = read_allowed(m, who, pt.on, kProjOff, pt.validity, "the projection tape is invalid until spd_model_projtape_reset")) return rc;
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    if (int rc = held_range(who, pt.ring, t0, nt, "sample")) return rc;
+    const size_t per = pt.entries.size();
+    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
+    if (count == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    // (the ring is [slot][M][E] as a spectra ring is [slot][M][per]: the same gather)
+    const hipError_t e = run_spectra_gather(pt.data + static_cast<size_t>(first) * per, static_cast<double *>(dst_device), static_cast<int>(per),
+                                            static_cast<long>(static_cast<size_t>(m->M) * per), count, nt, pt.ring.slot_of_held(t0),
+                                            pt.ring.capacity, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // The projection tape: weighted sums of the state's grid-space fields -- box and band means, global means, station values, any
 // fixed linear functional of one plane -- formed behind the sampled steps of the device loop and kept as scalar time series in a
-// ring in device memory (projtape.hip holds the kernel, model.hip the schedule, the configuration and the C ABI:
+// ring in device memory (projtape.hip holds the kernel, the configuration and the C ABI:
 // spd_model_projtape_* of include/pyspeedy_amd.h; the definition is DESIGN section 4j).
 //
 // Definition.  P weight maps w (fp64 [48][96], the layout of one level of a tape sample, shared by all members) and E entries
@@ -12,6 +12,8 @@
 // All 4608 = 18 * 256 terms take part; a zero weight is not skipped.  tests/projtape_reference.py restates it in numpy.
 #pragma once
 #include <hip/hip_runtime.h>
+
+struct spd_model;
 
 namespace spd {
 
@@ -28,10 +30,7 @@ struct ProjTapeItem {
     int pattern, column;
 };
 
-// One launch for the members [first, first + count), all planes.  weights: [P][4608]; slab: [M][slab_fields][4608] fp64, as the
-// front end left it; store32: the model keeps precnv / precls as float; ring_slot: member 0 of the sample's slot, [M][n_entries].
-hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const ProjTapeItem *items, const double *weights,
-                               const double *slab, int slab_fields, double *ring_slot, int n_entries, int first, int count,
-                               int store32, hipStream_t s);
+// The step loop's sample of the members [first, first + count), number n since the last reset, behind the step just issued on `s`.
+hipError_t projtape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);
 
 }  // namespace spd

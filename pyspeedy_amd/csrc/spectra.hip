@@ -16,6 +16,7 @@
 // a group fall on the 16 different 4-bank slots of the bank row: the walk is free of conflicts with the row left at 31 elements.
 #include <hip/hip_runtime.h>
 
+#include "model_state.hpp"
 #include "spectra.hpp"
 #include "tables.hpp"
 
@@ -96,7 +97,8 @@ __global__ __launch_bounds__(256) void spectra_gather_kernel(const double *__res
 }
 }  // namespace
 
-hipError_t run_spectra(const SpectraArgs &args, int count, hipStream_t s) {
+// One launch for the members [first, first + count): every name of the mask.
+static hipError_t run_spectra(const SpectraArgs &args, int count, hipStream_t s) {
     if (count == 0 || args.mask == 0) return hipSuccess;
     hipLaunchKernelGGL(spectra_kernel, dim3(kLevelSlots, count), dim3(kT), 0, s, args);
     return hipGetLastError();
@@ -117,3 +119,175 @@ hipError_t run_spectra_gather(const double *src, double *dst, int per, long slot
 }
 
 }  // namespace spd
+
+// ---- host side: the step loop's sample, the configuration and the C ABI (spd_model_spectra_*) ----
+
+namespace {
+constexpr const char *kSpectraNames[SPECTRA_NNAMES] = {"ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum",
+                                                       "lnps_spectrum",   "t_mean",          "q_mean",     "lnps_mean"};
+int spectra_id(const char *name) {
+    for (int v = 0; name && v < SPECTRA_NNAMES; ++v)
+        if (std::strcmp(name, kSpectraNames[v]) == 0) return v;
+    return -1;
+}
+
+// the list of names of a call -> ids, in the order given (the arguments first: nothing here needs the device or a model)
+int spectra_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
+    if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of names");
+    for (int k = 0; k < n_names; ++k) {
+        const int id = spectra_id(names[k]);
+        if (id < 0)
+            return m_fail(SPD_E_ARG, std::string(who) + ": unknown name '" + (names[k] ? names[k] : "(null)") +
+                                         "' (ke_rot_spectrum, ke_div_spectrum, t_spectrum, q_spectrum, lnps_spectrum, t_mean, q_mean, "
+                                         "lnps_mean)");
+        if (std::find(ids.begin(), ids.end(), id) != ids.end())
+            return m_fail(SPD_E_ARG, std::string(who) + ": name '" + names[k] + "' given twice");
+        ids.push_back(id);
+    }
+    return SPD_OK;
+}
+
+// the kernel's arguments but for the destinations: the members [first, first + count) of the state as it stands
+SpectraArgs spectra_args(const spd_model *m, unsigned mask, int first, int out_first) {
+    SpectraArgs a{};
+    a.vor = m->P.vor, a.div = m->P.div, a.t = m->P.t, a.tr = m->P.tr, a.ps = m->P.ps;
+    a.elm2 = m->ctx->dev.elm2;
+    a.mask = mask, a.first = first, a.out_first = out_first;
+    return a;
+}
+}  // namespace
+
+// a sample: one launch for the group's members, straight into ring slot (n - 1) % capacity
+hipError_t spd::spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s) {
+    const spd_model::Spectra &sp = m->spectra;
+    const size_t M = static_cast<size_t>(m->M), slot = static_cast<size_t>(sp.ring.slot(n));
+    SpectraArgs a = spectra_args(m, sp.mask, first, 0);
+    for (int v = 0; v < SPECTRA_NNAMES; ++v)
+        if (sp.mask & (1u << v)) a.out[v] = static_cast<double *>(sp.alloc) + sp.offset[v] + slot * M * spectra_per_member(v);
+    return run_spectra(a, count, s);
+}
+
+extern "C" {
+
+int spd_model_spectra_configure(spd_model_handle m, const char *const *names, int n_names, int every, int capacity) {
+    const char *who = "spd_model_spectra_configure";
+    // (the arguments first: nothing below needs the device)
+    std::vector<int> ids;
+    if (int rc = spectra_ids(who, names, n_names, ids)) return rc;
+    if (n_names > 0 && every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
+    if (n_names > 0 && capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
+    if (int rc = configure_allowed(m, who)) return rc;
+    spd_model::Spectra &sp = m->spectra;
+    if (int rc = retire(m, sp)) return rc;
+    if (n_names == 0) return SPD_OK;  // off
+    spd_model::Spectra next;
+    next.every = every;
+    const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity);
+    size_t per_slot = 0;  // doubles of a sample
+    for (int id : ids) {
+        next.mask |= 1u << id;
+        per_slot += M * spectra_per_member(id);
+    }
+    if (slots > (static_cast<size_t>(-1) / 2) / (per_slot * sizeof(double)))
+        return m_fail(SPD_E_ARG, std::string(who) + ": the size of the series does not fit size_t");
+    size_t at = 0;
+    for (int v = 0; v < SPECTRA_NNAMES; ++v)
+        if (next.mask & (1u << v)) {
+            next.offset[v] = at;
+            at += slots * M * spectra_per_member(v);
+        }
+    const size_t total = sample_up(at * sizeof(double));
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {  // the spectra are off; the model is as usable as before
+        (void)hipGetLastError();
+        return m_fail(SPD_E_DEVICE, std::string(who) + ": cannot allocate the series (" + std::to_string(total) + " bytes asked for: " +
+                                        std::to_string(capacity) + " samples of " + std::to_string(per_slot * sizeof(double)) +
+                                        " bytes); the spectra are off");
+    }
+    next.alloc = p;
+    next.ring = SampleRing(capacity, 6);
+    next.on = true;
+    sp = std::move(next);
+    return SPD_OK;
+}
+
+int spd_model_spectra_reset(spd_model_handle m) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: null model");
+    if (!m->spectra.on) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: no spectra configured (spd_model_spectra_configure)");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: a checked multi-step call is in flight; end it first");
+    m->spectra.ring.clear();
+    m->spectra.validity.clear();
+    return SPD_OK;
+}
+
+int spd_model_spectra_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_info: null model");
+    const spd_model::Spectra &sp = m->spectra;
+    if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_info: no spectra configured (spd_model_spectra_configure)");
+    if (taken) *taken = sp.ring.taken;
+    if (held) *held = static_cast<int>(sp.ring.held());
+    if (capacity) *capacity = sp.ring.capacity;
+    if (every) *every = sp.every;
+    return SPD_OK;
+}
+
+int spd_model_spectra_times(spd_model_handle m, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_times: null model");
+    const spd_model::Spectra &sp = m->spectra;
+    if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_times: no spectra configured (spd_model_spectra_configure)");
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_spectra_times: bad destination");
+    return sp.ring.copy_rows(rows, max_rows);
+}
+
+int spd_model_spectra_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
+                           void *stream) {
+    const char *who = "spd_model_spectra_read";
+    if (!m || !name) return m_fail(SPD_E_ARG, std::string(who) + ": null argument");
+    const spd_model::Spectra &sp = m->spectra;
+    if (int rc = read_allowed(m, who, sp.on, "no spectra configured (spd_model_spectra_configure)", sp.validity,
+                              "the spectra are invalid until spd_model_spectra_reset"))
+        return rc;
+    const int id = spectra_id(name);
+    if (id < 0 || !(sp.mask & (1u << id))) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' is not among the configured names");
+    if (first < 0 || count < 0 || first + count > m->M) return m_fail(SPD_E_ARG, std::string(who) + ": member range out of bounds");
+    if (int rc = held_range(who, sp.ring, t0, nt, "sample")) return rc;
+    const size_t per = static_cast<size_t>(spectra_per_member(id));
+    const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
+    if (count == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    const double *src = static_cast<const double *>(sp.alloc) + sp.offset[id] + static_cast<size_t>(first) * per;
+    const hipError_t e = run_spectra_gather(src, static_cast<double *>(dst_device), static_cast<int>(per),
+                                            static_cast<long>(static_cast<size_t>(m->M) * per), count, nt,
+                                            sp.ring.slot_of_held(t0), sp.ring.capacity, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+int spd_model_spectra_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, void *dst_device,
+                              size_t dst_bytes, void *stream) {
+    const char *who = "spd_model_spectra_compute";
+    std::vector<int> ids;
+    if (int rc = spectra_ids(who, names, n_names, ids)) return rc;
+    if (int rc = member_range(m, first, count, who)) return rc;
+    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    size_t per = 0;
+    for (int id : ids) per += static_cast<size_t>(spectra_per_member(id));
+    const size_t need = static_cast<size_t>(count) * per * sizeof(double);
+    if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
+    if (need == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    SpectraArgs a = spectra_args(m, 0, first, first);
+    double *at = static_cast<double *>(dst_device);
+    for (int id : ids) {  // [count][...] per name, one after the other in the order given
+        a.mask |= 1u << id;
+        a.out[id] = at;
+        at += static_cast<size_t>(count) * spectra_per_member(id);
+    }
+    const hipError_t e = run_spectra(a, count, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
+}
+
+}  // extern "C"

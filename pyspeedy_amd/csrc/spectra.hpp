@@ -1,8 +1,10 @@
 // Spectra by total wavenumber and global means of the spectral state, recorded by the device loop of a multi-step call or computed
-// on the state as it stands (spectra.hip holds the kernels, model.hip the configuration and the C ABI: spd_model_spectra_* of
+// on the state as it stands (spectra.hip holds the kernels, the configuration and the C ABI: spd_model_spectra_* of
 // include/pyspeedy_amd.h; the definition is DESIGN section 4d).
 #pragma once
 #include <hip/hip_runtime.h>
+
+struct spd_model;
 
 namespace spd {
 
@@ -36,11 +38,12 @@ struct SpectraArgs {
     int first, out_first;
 };
 
-// One launch for the members [first, first + count): every name of the mask.
-hipError_t run_spectra(const SpectraArgs &args, int count, hipStream_t s);
 // Unroll the ring of one name into dst[count][nt][per] doubles: sample t of the read lies in slot (slot0 + t) % capacity; src: slot
 // 0, member `first` of the name; slot_stride in doubles (M * per).
 hipError_t run_spectra_gather(const double *src, double *dst, int per, long slot_stride, int count, int nt, int slot0, int capacity,
                               hipStream_t s);
+
+// The step loop's sample of the members [first, first + count), number n since the last reset, behind the step just issued on `s`.
+hipError_t spectra_sample(spd_model *m, int first, int count, long long n, hipStream_t s);
 
 }  // namespace spd

@@ -1,9 +1,11 @@
 // Per-member running time statistics of grid-space fields, sampled by the device loop of a multi-step call (stats.hip holds the
-// kernels, model.hip the configuration and the C ABI: spd_model_stats_* of include/pyspeedy_amd.h).
+// kernels, the configuration and the C ABI: spd_model_stats_* of include/pyspeedy_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+
+struct spd_model;
 
 namespace spd {
 
@@ -16,13 +18,7 @@ struct StatsPlane {
     long member_stride;    // doubles between two members in mean / m2 (levels * 4608)
 };
 
-// Welford update of mean / M2 for the members [first, first + count), sample number n (1-based; n == 1 starts a period).
-// slab: [M][slab_fields][4608]; store32: the physics outputs are stored as fp32 (first half of their allocations).
-hipError_t run_stats_accumulate(const StatsPlane *planes, int nplanes, const double *slab, int slab_fields, int first, int count,
-                                long long n, int store32, hipStream_t s);
-// out[i] = m2[i] / (n - 1) over `total` doubles
-hipError_t run_stats_variance(const double *m2, double *out, long total, long long n, hipStream_t s);
-// over the M members of one variable's time means ([M][points]): the mean (std = 0) or the unbiased standard deviation (std = 1)
-hipError_t run_stats_ensemble(const double *mean, int M, long points, int std, double *out, hipStream_t s);
+// The step loop's sample of the members [first, first + count), number n since the last reset, behind the step just issued on `s`.
+hipError_t stats_sample(spd_model *m, int first, int count, long long n, hipStream_t s);
 
 }  // namespace spd

@@ -1,10 +1,12 @@
 // The tape: a ring in device memory of the last samples of grid-space fields, recorded by the device loop of a multi-step call
-// (tape.hip holds the kernels, model.hip the configuration and the C ABI: spd_model_tape_* of include/pyspeedy_amd.h; the
+// (tape.hip holds the kernels, the configuration and the C ABI: spd_model_tape_* of include/pyspeedy_amd.h; the
 // definition is DESIGN section 4c).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+
+struct spd_model;
 
 namespace spd {
 
@@ -18,14 +20,12 @@ struct TapePlane {
     long slot_stride;    // elements between two slots of the variable (M * levels * 4608)
 };
 
-// Store the sample of the members [first, first + count) into ring slot `slot`: all planes in one launch.
-// slab: [M][slab_fields][4608] fp64; store32: the physics outputs are stored as fp32; f64: the tape holds doubles (else floats,
-// rounded to nearest).
-hipError_t run_tape_store(const TapePlane *planes, int nplanes, const double *slab, int slab_fields, int first, int count, int slot,
-                          int store32, int f64, hipStream_t s);
 // Unroll the ring of one variable into dst[count][nt][per] (per = levels * 4608 elements of elem_bytes): sample t of the read lies
 // in slot (slot0 + t) % capacity; src: slot 0, member `first` of the variable; slot_stride in elements (M * per).
 hipError_t run_tape_gather(const void *src, void *dst, long per, long slot_stride, int elem_bytes, int count, int nt, int slot0,
                            int capacity, hipStream_t s);
+
+// The step loop's sample of the members [first, first + count), number n since the last reset, behind the step just issued on `s`.
+hipError_t tape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);
 
 }  // namespace spd

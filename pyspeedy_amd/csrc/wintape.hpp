@@ -1,13 +1,18 @@
 // The window tape: window sums, means, extremes and threshold counts of the state's grid-space fields, accumulated behind the
 // sampled steps of the device loop and closed into a ring in device memory every n steps, at midnight or at month ends
-// (wintape.hip holds the kernel, model.hip the schedule, the configuration and the C ABI: spd_model_wintape_* and spd_wintape_plan
+// (wintape.hip holds the kernel, the schedule, the configuration and the C ABI: spd_model_wintape_* and spd_wintape_plan
 // of include/pyspeedy_amd.h; the definition is DESIGN section 4g).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
+
+struct spd_model;
 
 namespace spd {
+
+struct Calendar;
 
 // One plane (a level of a name) of every member, as the accumulate kernel sees it.  Accumulator and ring pointers are those of
 // member 0 at this plane; a member lies member_stride elements further in the accumulators and in a ring slot alike.
@@ -26,13 +31,23 @@ struct WinTapePlane {
     long slot_stride;    // elements between two ring slots of an entry (M * levels * 4608)
 };
 
-// One launch for the members [first, first + count), all planes.  k: number of this launch's sample within its window, from 1
-// (1 overwrites the accumulators and reads none of them); 0: the step is not sampled and the launch only closes.  close: the step
-// ends the window, whose n samples (this one included) give the results that go into ring slot `slot`; n = 0 closes an empty
-// window (sum and counts 0, mean, minimum and maximum quiet NaN) and reads no accumulator.  slab: [M][slab_fields][4608] fp64, as
-// the front end left it; store32: the model keeps the narrow sources as float; f64: the ring holds doubles (else floats, rounded to
-// nearest).
-hipError_t run_wintape_step(const WinTapePlane *planes, int nplanes, const double *slab, int slab_fields, int first, int count, int k,
-                            int close, int n, int slot, int store32, int f64, hipStream_t s);
+// The window tape's schedule: the ONE place that decides whether a step samples and whether it closes the open window, for the step
+// loop (step_impl) and for spd_wintape_plan alike.
+struct WinSchedule {
+    int window, every, sample_every;
+};
+struct WinOpen {
+    int start, samples;  // the step counter the open window began at; the samples it holds
+};
+struct WinDecision {
+    bool sample, close;
+};
+// The step that leaves the counter at `step_after` and the date at `next`: a sample goes into the open window first; a closing
+// step then fills row[8] (spd_model_wintape_times) and opens the next window at step_after.
+WinDecision wintape_advance(const WinSchedule &s, WinOpen &w, int step_after, const Calendar &next, int32_t *row);
+
+// The step loop's launches for the members [first, first + count) on a step that samples (k >= 1: the front end, then the kernel) or
+// only closes (k = 0: the kernel alone); k, close, n and slot as run_wintape_step (wintape.hip) takes them.
+hipError_t wintape_step(spd_model *m, int first, int count, int k, int close, int n, int slot, hipStream_t s);
 
 }  // namespace spd

@@ -780,6 +780,51 @@ int spd_model_breed_read(spd_model_handle m, int what, int t0, int nt, void *dst
 int spd_model_breed_rows(spd_model_handle m, int32_t *rows, int max_rows);
 int spd_model_breed_reset(spd_model_handle m);
 int spd_model_breed_info(spd_model_handle m, int *bred, int *every, int *capacity, long long *taken, int *in_loop, long long *applied);
+/* Orthonormalised breeding: the Gram-Schmidt cycle of the bred members that share a control, inside the same device loop -- the
+ * perturbations stay orthonormal (backward Lyapunov vectors), the ring's growth rates are the leading local Lyapunov exponents,
+ * and the Gram matrix is there to be read (bred-vector dimension).  Off unless switched on; plain breeding keeps its bits.
+ * Definition.  A family is the set of bred members with one control c, in ascending member index p_1 < ... < p_r, r <= 64;
+ * D_j = X_(p_j) - X_c.  Inner product, on time level 1, over the coefficients with m + n <= 31, with the planes, weights, w_m and
+ * elm2 of the breeding configuration:
+ *   B_P(i, j) = f_P sum_k [elm2(l)] w_m (Re D_i Re D_j + Im D_i Im D_j)      f = 1/4 for vor, div (with elm2), 1/2 for t, tr, ps
+ *   G_ij      = sum_P weight_P B_P(i, j)                                      ascending plane order, planes of weight 0 skipped
+ * A term is q = rn(rn(dx_i dx_j) + rn(dy_i dy_j)), times 2 if m != 0, times elm2 if kinetic; per (plane, pair) the terms are added
+ * in the order of the plain amplitude's kernel (a lane's coefficients lane, + 256, + 512, + 768, then the tree 128 ... 1 over the
+ * lanes), whatever the tiling, the family, the launch plan or the call length.  So B_P(j, j) is, bit for bit, the partial that
+ * plain breeding computes, and sqrt(G_11) is _compute's amplitude of p_1.
+ * Factor G = R^T R, R upper triangular, every operation rounded on its own:
+ *   for j = 1 ... r:
+ *       for i = 1 ... j-1:  acc = G_ij;  for k = 1 ... i-1: acc = acc - R_ki R_kj;   R_ij = acc / R_ii
+ *       d = G_jj;  for k = 1 ... j-1: d = d - R_kj R_kj
+ *       if not (d > 0 and d finite): the family BREAKS at j: members p_j ... p_r are left alone (not one bit loaded or stored,
+ *                                    amplitude 0.0 and factor 1.0 in the ring); stop
+ *       R_jj = sqrt(d)
+ * Coefficients C = target R^-1 (upper triangular):
+ *   C_jj = target / R_jj;   for i = j-1 ... 1:  acc = 0;  for k = i+1 ... j: acc = acc + R_ik C_kj;   C_ij = (-acc) / R_ii
+ * Transform, on both time levels with the same C, real and imaginary parts separately, m + n <= 31 only, D of the members as
+ * they stood:
+ *   acc = C_1j D_1;  for i = 2 ... j: acc = acc + C_ij D_i;   X'_(p_j) = X_c + acc
+ * A family of one member is plain breeding, bit for bit.  Ring: amplitude[p_j] = R_jj (the part of the grown perturbation that
+ * is orthogonal to the earlier ones), factor[p_j] = target / R_jj.
+ *   _orthogonalize  on = 1: allowed when breeding is configured and no checked call is in flight; builds the family and pair lists
+ *               and allocates the Gram partials [pairs][33] and C [families][64][64] (one hipMalloc; synchronises the device).
+ *               SPD_E_ARG with the control and the size for a family of more than 64 members.  From then on every rescale
+ *               (in-loop and _apply) issues the Gram, factor and transform launches for the norm and rescale launches; schedule,
+ *               ring slot, stamps and `applied` are as before.  on = 0 frees it; _configure retires it with the rest.
+ *   _compute    keeps its meaning: A is the square root of the Gram matrix's diagonal, not R_jj.
+ *   _gram       fp64 [M][M] into device memory: entry (a, b) is G of the two members if both are bred with the same control, else
+ *               0.0; symmetric; writes neither state nor ring; stream-ordered with orthogonalisation on, and it synchronises with
+ *               it off (its scratch lives for the call).
+ *   spd_breed_family_check  without a model: the checks of a control list (the messages of _configure), then the size of the
+ *               largest family, or -1 with _orthogonalize's message for a family of more than 64.
+ *   spd_breed_factor_host  the factor routine of the device, compiled for the host: gram and coef row-major r x r (gram is read
+ *               at i <= j), rdiag[r] = R's diagonal, *rank = the members transformed; rows and columns from the rank on are 0.0.
+ *   _ortho_info on (0 or 1), the number of families and the size of the largest of the configuration; any pointer may be NULL. */
+int spd_model_breed_orthogonalize(spd_model_handle m, int on);
+int spd_model_breed_gram(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream);
+int spd_breed_family_check(const int32_t *control, int members);
+int spd_breed_factor_host(const double *gram, int r, double target, double *rdiag, double *coef, int *rank);
+int spd_model_breed_ortho_info(spd_model_handle m, int *on, int *families, int *largest);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

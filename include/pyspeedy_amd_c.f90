@@ -12,7 +12,7 @@
 !! the ensemble mean and spread (spd_model_enstape_*), window sums, means and extremes of the physics fluxes (spd_model_acctape_*)
 !! window means, extremes and threshold counts of the state's fields (spd_model_wintape_*, spd_wintape_plan), and nudging of the
 !! spectral state toward target fields inside the device loop (spd_model_nudge_*), and breeding: the rescaling of member
-!! perturbations against their control runs inside the device loop (spd_model_breed_*, spd_breed_check)
+!! perturbations against their control runs inside the device loop (spd_model_breed_*, spd_breed_check), orthonormalised on request
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -491,6 +491,37 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model
             integer(c_int), intent(out) :: bred, every, capacity, in_loop
             integer(c_long_long), intent(out) :: taken, applied
+        end function
+        ! orthonormalised breeding: the Gram-Schmidt cycle of the bred members that share a control (pyspeedy_amd.h:
+        ! spd_model_breed_orthogonalize).  _gram: (members, members) fp64 in device memory; spd_breed_factor_host: gram and coef are
+        ! row-major r x r (in Fortran: the transposes), rdiag(r)
+        integer(c_int) function spd_model_breed_orthogonalize(model, on) bind(C, name="spd_model_breed_orthogonalize")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+            integer(c_int), value :: on
+        end function
+        integer(c_int) function spd_model_breed_gram(model, dst_device, dst_bytes, stream) bind(C, name="spd_model_breed_gram")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_breed_family_check(control, members) bind(C, name="spd_breed_family_check")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: control
+            integer(c_int), value :: members
+        end function
+        integer(c_int) function spd_breed_factor_host(gram, r, target, rdiag, coef, rank) bind(C, name="spd_breed_factor_host")
+            import :: c_int, c_double
+            real(c_double), intent(in) :: gram(*)
+            integer(c_int), value :: r
+            real(c_double), value :: target
+            real(c_double), intent(out) :: rdiag(*), coef(*)
+            integer(c_int), intent(out) :: rank
+        end function
+        integer(c_int) function spd_model_breed_ortho_info(model, on, families, largest) bind(C, name="spd_model_breed_ortho_info")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+            integer(c_int), intent(out) :: on, families, largest
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
         ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for

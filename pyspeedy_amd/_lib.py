@@ -184,6 +184,11 @@ _SIGNATURES = {
     "spd_model_breed_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "spd_model_breed_reset": (C.c_int, [C.c_void_p]),
     "spd_model_breed_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "spd_model_breed_orthogonalize": (C.c_int, [C.c_void_p, C.c_int]),
+    "spd_model_breed_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_breed_family_check": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
+    "spd_breed_factor_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "spd_model_breed_ortho_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),

@@ -24,8 +24,15 @@ struct BreedPair {
     int member, control;
 };
 
-// The rescale of all bred members on the state as it stands, on stream s: the norm launch, the rescale launch behind it and one
-// slot of the ring.  For the step loop at the end of a segment (model.hip: step_impl) and for spd_model_breed_apply; `who` opens
+// Orthonormalised breeding: the bred members that share one control, in ascending member index.
+struct BreedFamily {
+    int control;
+    int first, count;  // its members: members[first ... first + count) of the family member list
+    long pair0;        // its pairs i <= j (positions in the family): Gram partials [pair0 + j (j + 1) / 2 + i][33]
+};
+
+// The rescale of all bred members on the state as it stands, on stream s: the norm launch, the rescale launch behind it (with
+// orthogonalisation on: the Gram, factor and transform launches) and one slot of the ring.  For the step loop at the end of a segment (model.hip: step_impl) and for spd_model_breed_apply; `who` opens
 // the error text.
 int breed_rescale(spd_model *m, hipStream_t s, const char *who);
 

@@ -666,6 +666,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->projtape.alloc) (void)hipFree(m->projtape.alloc);
     if (m->nudge.alloc) (void)hipFree(m->nudge.alloc);
     if (m->breed.alloc) (void)hipFree(m->breed.alloc);
+    if (m->breed.ortho.alloc) (void)hipFree(m->breed.ortho.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);

@@ -353,6 +353,18 @@ struct spd_model {
         BreedPair *pairs = nullptr;
         int *slot_of = nullptr;
         double *partial = nullptr, *data = nullptr;
+        std::vector<BreedPair> host_pairs;  // the pairs as _configure built them (ascending member index)
+        // Orthonormalised breeding (spd_model_breed_orthogonalize): a second allocation with the families, their
+        // member list, each member's (family, position), the Gram partials [pairs][33], C [families][64][64] and the ranks.
+        struct Ortho {
+            bool on = false;
+            int families = 0, largest = 0;
+            long pairs = 0;
+            void *alloc = nullptr;
+            BreedFamily *fams = nullptr;
+            int *members = nullptr, *place = nullptr, *rank = nullptr;
+            double *partial = nullptr, *coef = nullptr;
+        } ortho;
         bool loops() const { return on && in_loop && nbred > 0; }  // spd_model_step is issued in segments
     } breed;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved

@@ -839,7 +839,7 @@ class EnsembleModel:
     # ---- breeding: member perturbations rescaled against their control runs (spd_model_breed_*, include/pyspeedy_amd.h) ------
     BREED_NAMES = ("vor", "div", "t", "tr", "ps")
 
-    def breed_configure(self, control, target, every, weights="kinetic_energy", capacity=64, in_loop=True):
+    def breed_configure(self, control, target, every, weights="kinetic_energy", capacity=64, in_loop=True, orthogonalize=False):
         """Breed perturbations: after every step that leaves current_step at a multiple of `every`, inside run() / run_checked()
         calls of any length (`in_loop`) or only when breed_apply() is called, every bred member p is pulled back to the distance
         `target` from its control c: X_p' = X_c + s (X_p - X_c), s = target / A, on both time levels of vor, div, t, tr, ps for
@@ -847,7 +847,8 @@ class EnsembleModel:
         a member that is not bred (a control must itself have -1).  `weights`: a kind of pyspeedy_amd.breed_weights, or a dict
         name of BREED_NAMES -> (8,) weights >= 0 of the quadratic forms that make A^2 (names left out weigh nothing; ps reads
         entry 0).  Every rescale writes the amplitudes before it and the factors to a ring of `capacity` events (breed()).  Land and
-        sea temperatures are not rescaled.  Synchronises the device."""
+        sea temperatures are not rescaled.  `orthogonalize`: breed_orthogonalize() behind the configuration.  Synchronises the
+        device."""
         from ._lib import breed_weights
         ctl = np.ascontiguousarray(np.asarray(control).astype(np.int32))
         if ctl.shape != (self.nmembers,):
@@ -857,6 +858,31 @@ class EnsembleModel:
             check(self._lib.spd_model_breed_configure(self._m, ctl.ctypes.data_as(C.POINTER(C.c_int32)),
                                                       table.ctypes.data_as(C.POINTER(C.c_double)), float(target), int(every),
                                                       int(capacity), int(bool(in_loop))), "spd_model_breed_configure")
+        if orthogonalize:
+            self.breed_orthogonalize(True)
+
+    def breed_orthogonalize(self, on=True):
+        """Orthonormalised breeding on or off: with it on, every rescale (in-loop and breed_apply()) is the Gram-Schmidt cycle of
+        each family -- the bred members p_1 < ... < p_r (r <= 64) that share a control.  With G the Gram matrix of their
+        differences in the configured norm, G = R^T R and C = target R^-1 (upper triangular), member p_j becomes
+        X_c + sum_{i <= j} C_ij (X_(p_i) - X_c) on both time levels: the perturbations leave orthonormal at `target`.  The ring
+        holds amplitude = R_jj (what grew orthogonally to the earlier members) and factor = target / R_jj, so breed_growth() gives
+        the local Lyapunov exponents, member by member in descending order.  A family breaks at a member whose perturbation has
+        nothing left (or is not finite): that member and the later ones are left alone.  breed_off() and breed_configure() switch
+        it off.  Synchronises the device."""
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_breed_orthogonalize(self._m, int(bool(on))), "spd_model_breed_orthogonalize")
+
+    def breed_gram(self):
+        """The Gram matrix of the perturbations on the state as it stands, in the configured norm: a float64 tensor
+        [members][members] on the model's device; entry (a, b) is the inner product of the two members' differences against their
+        control if both are bred with the same control, else 0.0.  Its diagonal is breed_amplitude() squared.  Writes neither the
+        state nor the ring; works with orthogonalisation on or off."""
+        out = torch.empty((self.nmembers, self.nmembers), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_breed_gram(self._m, C.c_void_p(out.data_ptr()), out.numel() * 8, self._stream()),
+                  "spd_model_breed_gram")
+        return out
 
     @classmethod
     def _breed_table(cls, weights):
@@ -892,13 +918,20 @@ class EnsembleModel:
 
     def breed_info(self):
         """dict(bred, every, capacity, taken, held, in_loop, applied): bred members (all zero: off), the configuration, events
-        since breed_configure / breed_reset and events the ring holds, the mode, and the rescales launched since breed_configure."""
+        since breed_configure / breed_reset and events the ring holds, the mode, and the rescales launched since breed_configure.
+        While orthogonalisation is on the dict also has orthogonalize (True), families and largest_family; a model with plain
+        breeding reports exactly what it always did."""
+        on, families, largest = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.spd_model_breed_ortho_info(self._m, C.byref(on), C.byref(families), C.byref(largest)), "spd_model_breed_ortho_info")
         bred, every, capacity, in_loop = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         taken, applied = C.c_longlong(0), C.c_longlong(0)
         check(self._lib.spd_model_breed_info(self._m, C.byref(bred), C.byref(every), C.byref(capacity), C.byref(taken), C.byref(in_loop),
                                              C.byref(applied)), "spd_model_breed_info")
-        return dict(bred=bred.value, every=every.value, capacity=capacity.value, taken=int(taken.value),
+        info = dict(bred=bred.value, every=every.value, capacity=capacity.value, taken=int(taken.value),
                     held=int(min(taken.value, capacity.value)), in_loop=bool(in_loop.value), applied=int(applied.value))
+        if on.value:
+            info.update(orthogonalize=True, families=families.value, largest_family=largest.value)
+        return info
 
     def breed_reset(self):
         """Empty the ring of breeding events (no device work)."""
@@ -942,6 +975,16 @@ class EnsembleModel:
             with np.errstate(divide="ignore", invalid="ignore"):
                 out[1:] = np.log(a[1:] / (a[:-1] * s[:-1])) / dt
         return out
+
+    def breed_exponents(self, skip=1):
+        """The time mean of breed_growth() over the held events but the first `skip`, per member, in 1/day: with orthogonalisation
+        on, the leading Lyapunov exponents of the control's trajectory (the first member of a family carries the largest).  Host
+        arithmetic; events without a growth rate (NaN) are left out, a member without any gives NaN."""
+        g = self.breed_growth()[max(int(skip), 0):]
+        ok = np.isfinite(g)
+        n = ok.sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 86400.0 * np.where(ok, g, 0.0).sum(axis=0) / np.where(n > 0, n, np.nan)
 
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",

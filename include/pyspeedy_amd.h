@@ -317,7 +317,9 @@ int spd_model_group_streams(spd_model_handle m, int32_t *created, int32_t *apart
  * fields when the model is created; none of them changes the state a step leaves behind):
  *   "diag_every_step"      0 / 1   store the diagnostics-only physics outputs on every step of a multi-step call
  *   "spectral_early"      -1 / 0 / 1   spectral_step_kernel with all loads up front: automatic (up to 8 members) / never / always
- *   "split_dyn"            0 / 1   separate launches for grid-point dynamics and column physics
+ *   "split_dyn"            0 / 1   separate launches for grid-point dynamics and column physics (fp64 physics only; the dynamics kernel
+ *                                  then stores the flux and kinetic-energy products and the forward transforms read them, where
+ *                                  the fused launch leaves them to be formed inside the transforms: same bits)
  *   "member_groups"        1 ... 4 the members are stepped in that many groups on separate HIP streams (default: 1 below 20
  *                                  members, 2 for 20 ... 23 and from 64 up, 3 for 24 ... 63; always 1 while spd_model_profile is on, for calls of a single step and with split_dyn)
  *   "block_members"        0, n    (default 32, PYSPEEDY_AMD_BLOCK_MEMBERS) from 4 n members up a multi-step spd_model_step takes the
@@ -333,7 +335,10 @@ int spd_model_group_streams(spd_model_handle m, int32_t *created, int32_t *apart
  * Returns SPD_E_ARG for an unknown name or a value outside the list.  What is fixed at creation (the pruned transform
  * table, the geopotential fold) is read from the environment only. */
 int spd_model_set_option(spd_model_handle m, const char *name, int32_t value);
-/* ... and read back, by the same names.  One name is read-only:
+/* ... and read back, by the same names.  Two names are read-only:
+ *   "staged_products"      1 when the step's grid -> spectral launch forms the 40 flux / kinetic-energy products of a member itself,
+ *                          from the four grid fields they are products of (the fused column kernel does not store them); 0 when
+ *                          it reads them from memory (split_dyn with the fp64 physics)
  *   "quiet_rim_members"    the number of members whose coefficients beyond the truncation's halo (m + n >= 33) the last call of
  *                          spd_model_step / spd_model_step_checked_begin found to be all-zero bits at its first step, and whose
  *                          dead coefficient blocks its later steps therefore left alone; -1 when that call did not look (a call of

@@ -32,7 +32,9 @@ struct DeviceTables {
 // pre-scale mode (0 none, 1 cosgr, 2 cosgr2).  Spectral->grid entries can ask for the spectral-space operator that feeds the
 // transform to be applied while the coefficients are staged (`mode`), so that u, v and grad ln ps never exist as spectral
 // arrays in memory: 0 = transform src as it is; 1 / 2 = ucos / vcos of vort2vel(vor = src, div = src2)
-// (spectral.f90:190-214); 3 / 4 = x / y component of gradient(src) (spectral.f90:275-296).
+// (spectral.f90:190-214); 3 / 4 = x / y component of gradient(src) (spectral.f90:275-296).  Grid->spectral entries can ask for
+// the field to be formed as a pointwise product of the grid fields src and src2 while the rows are staged (`mode` =
+// kind | level << 8, staged_products.hpp), so that the flux and kinetic-energy products never exist as grid arrays; 0 = src as it is.
 // flag of a spectral -> grid entry: kcos (1: none, 2: rows times 1 / cos(lat)) [| kGridAsFloat: dst receives the field as
 // fp32, 96 x 48 floats from dst on -- fields that only the fp32 column physics of cfg 5 reads].  grid -> spectral: the prescale
 // [| kSpecPacked: dst receives the 528 packed coefficients of triangle.hpp, 8448 B, and not the rectangle -- the tendency

@@ -4,16 +4,18 @@
 #include <hip/hip_runtime.h>
 
 #include "model.hpp"
+#include "staged_products.hpp"
 #include "stream_store.hpp"
 #include "vertical_consts.hpp"
 
 namespace spd {
 
-// Column p (0 .. ix*il-1, latitude row j) of member `mem`.  Stores utend / vtend above the lowest level, the kinetic energy
-// and flux products and the surface-pressure tendency; RETURNS the temperature / tracer tendencies of all levels and the
-// wind tendencies of the lowest level in registers (the physics adds to exactly those) -- or stores them too when STORE_ALL.
-// `before_products` is called once the tendencies are formed, in front of the 40 product stores: the fused kernel issues the
-// loads of its next phase there, so that they travel while the stores are issued (nothing, for the stand-alone kernel).
+// Column p (0 .. ix*il-1, latitude row j) of member `mem`.  Stores utend / vtend above the lowest level and the
+// surface-pressure tendency; RETURNS the temperature / tracer tendencies of all levels and the wind tendencies of the lowest
+// level in registers (the physics adds to exactly those) -- or stores them too, and the 40 kinetic-energy and flux products
+// (staged_products.hpp), when STORE_ALL.
+// `before_products` is called once the tendencies are formed, where the product stores of STORE_ALL begin: the fused kernel
+// issues the loads of its next phase there (nothing, for the stand-alone kernel).
 // (dhs, dhsr, fsgr, tref, tref3: the compile-time tables of vertical_consts.hpp, not D's copies -- see physics.hip: ColTables)
 struct NoPrefetch {
     __device__ void operator()() const {}
@@ -104,14 +106,17 @@ __device__ __forceinline__ void dyn_column(const ModelPtrs &P, const DynDeviceTa
         if (STORE_ALL) stream_store(&P.trtend[o3 + NG * k], trtend[k]);
     }
     before_products();
-    // inputs of the forward transforms (tendencies.f90:247-266)
+    // inputs of the forward transforms (tendencies.f90:247-266): stored by the stand-alone kernel only.  The fused kernel leaves
+    // them to the product mode of the grid -> spectral launch, which forms them from ug2 / vg2 / tg2 / trg2 with the same helper.
+    if (STORE_ALL) {
 #pragma unroll
-    for (int k = 0; k < KX; ++k) {
-        stream_store(&P.keg[o3 + NG * k], 0.5f * (ug[k] * ug[k] + vg[k] * vg[k]));
-        stream_store(&P.utg[o3 + NG * k], -ug[k] * tgg[k]);
-        stream_store(&P.vtg[o3 + NG * k], -vg[k] * tgg[k]);
-        stream_store(&P.uqg[o3 + NG * k], -ug[k] * trg[k]);
-        stream_store(&P.vqg[o3 + NG * k], -vg[k] * trg[k]);
+        for (int k = 0; k < KX; ++k) {
+            stream_store(&P.keg[o3 + NG * k], staged_product(kProdKe, ug[k], vg[k], 0.0));
+            stream_store(&P.utg[o3 + NG * k], staged_product(kProdFluxT, ug[k], tg[k], vc::tref[k]));
+            stream_store(&P.vtg[o3 + NG * k], staged_product(kProdFluxT, vg[k], tg[k], vc::tref[k]));
+            stream_store(&P.uqg[o3 + NG * k], staged_product(kProdFluxQ, ug[k], trg[k], 0.0));
+            stream_store(&P.vqg[o3 + NG * k], staged_product(kProdFluxQ, vg[k], trg[k], 0.0));
+        }
     }
 }
 

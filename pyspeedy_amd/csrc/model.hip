@@ -24,6 +24,7 @@
 #include "bounded_call.hpp"
 #include "launch_events.hpp"
 #include "sppt_point.hpp"
+#include "staged_products.hpp"
 #include "stream_apart.hpp"
 
 namespace spd {
@@ -251,6 +252,34 @@ static int build_tables(spd_model *m) {
         t.push_back({grid(P.psdtg, i), pspec(P.spec_ps, i), pk, 0});
     }
     batch.add(std::move(t), &m->fwd_table);
+    // The same 73 transforms for the fused column kernel, which does not store the 40 flux / kinetic-energy products: their
+    // entries form them from ug2 / vg2 / tg2 / trg2 while the rows are staged (FieldDesc::mode, staged_products.hpp).  Entry order
+    // inside a member is variable-major, level-minor, psdtg last, as in build_inverse_tables: 73 = 1 (mod 8), so entry 8 v + k
+    // of a member has workgroup id = member + k (mod 8), wherever the launch starts -- the five workgroups that read u_k, v_k,
+    // T_k, q_k of a member run on one XCD, are dispatched together (the product entries are adjacent) and share the four
+    // sources through that XCD's L2: measured 75 fields fetched per member of the 113 read (profiles/staged_products_ab.txt).
+    std::vector<FieldDesc> tp;
+    tp.reserve(static_cast<size_t>(M) * 73);
+    auto prod = [](int kind, int k) { return kind | (k << kProdLevelShift); };
+    for (int i = 0; i < M; ++i) {
+        const size_t w = static_cast<size_t>(i) * 8;
+        FieldDesc e[9][8];
+        for (int k = 0; k < 8; ++k) {
+            e[0][k] = {grid(P.utend, w + k), pspec(P.specu, w + k), 1 | pk, 0};
+            e[1][k] = {grid(P.vtend, w + k), pspec(P.specv, w + k), 1 | pk, 0};
+            e[2][k] = {grid(P.ttend, w + k), pspec(P.spec_tt, w + k), pk, 0};
+            e[3][k] = {grid(P.trtend, w + k), pspec(P.spec_tr, w + k), pk, 0};
+            e[4][k] = {grid(P.ug2, w + k), pspec(P.specu, pair + w + k), 1 | pk, prod(kProdFluxT, k), grid(P.tg2, w + k)};
+            e[5][k] = {grid(P.vg2, w + k), pspec(P.specv, pair + w + k), 1 | pk, prod(kProdFluxT, k), grid(P.tg2, w + k)};
+            e[6][k] = {grid(P.ug2, w + k), pspec(P.specu, 2 * pair + w + k), 1 | pk, prod(kProdFluxQ, k), grid(P.trg2, w + k)};
+            e[7][k] = {grid(P.vg2, w + k), pspec(P.specv, 2 * pair + w + k), 1 | pk, prod(kProdFluxQ, k), grid(P.trg2, w + k)};
+            e[8][k] = {grid(P.ug2, w + k), pspec(P.spec_ke, w + k), pk, prod(kProdKe, k), grid(P.vg2, w + k)};
+        }
+        for (int v = 0; v < 9; ++v)
+            for (int k = 0; k < 8; ++k) tp.push_back(e[v][k]);
+        tp.push_back({grid(P.psdtg, i), pspec(P.spec_ps, i), pk, 0});
+    }
+    batch.add(std::move(tp), &m->fwd_table_products);
     // export tables (prognostics.f90:125-219), time level 1.  sv holds ucos | vcos in the [M][2][8] layout of vor / div.
     for (int par = 0; par < 2; ++par) {
         std::vector<FieldDesc> ti, tf;
@@ -883,6 +912,11 @@ static void sppt_advance(spd_model *m) {
     m->sppt_step += 1;
 }
 
+// The fused column kernel stores no flux / kinetic-energy products: the forward transforms of its step form them (the product
+// table of build_tables).  The separate dynamics and physics launches (split_dyn; whole model, fp64 only) store them, and their
+// step uses the plain table.
+static bool staged_products(const spd_model *m) { return !(m->split_dyn_physics && !m->phys_fp32); }
+
 // cpl != nullptr: the coupling that follows the step is part of the last launch
 // ride != nullptr: the range check of the PREVIOUS step of these members rides in this step's spectral -> grid launch
 static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int compute_shortwave, int first, int count, int diag,
@@ -934,7 +968,7 @@ static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int comput
         }
     }
     if (e == hipSuccess) {
-        if (m->split_dyn_physics && !m->phys_fp32) {  // whole model, fp64 only; the default is the fused launch (with SPPT: KEEP)
+        if (!staged_products(m)) {  // whole model, fp64 only; the default is the fused launch (with SPPT: KEEP)
             {
                 ProfScope ps(m, SPD_K_DYN_GRID, M, s);
                 e = run_dyn_grid(m->P, m->D, M, s);                                       // :151-224
@@ -950,7 +984,9 @@ static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int comput
     }
     if (e == hipSuccess) {                                                                // :238-268
         ProfScope ps(m, SPD_K_GRID2SPEC, 73 * count, s);
-        e = run_grid2spec_table(T, m->fwd_table + static_cast<size_t>(first) * 73, 73 * count, s);
+        // the stand-alone dynamics kernel stores the flux / kinetic-energy products; the fused one leaves them to this launch
+        const FieldDesc *fwd = staged_products(m) ? m->fwd_table_products : m->fwd_table;
+        e = run_grid2spec_table(T, fwd + static_cast<size_t>(first) * 73, 73 * count, s);
     }
     if (after_grid2spec && e == hipSuccess) e = hipEventRecord(after_grid2spec, s);
     const double eps = (j1 == 1) ? 0.0 : static_cast<double>(0.05f);                      // rob, time_stepping.f90:130-134
@@ -1952,6 +1988,7 @@ int spd_model_get_option(spd_model_handle m, const char *name, int32_t *value) {
     else if (key == "member_groups") *value = m->nchunks;
     else if (key == "block_members") *value = m->block_members;
     else if (key == "physics_storage32") *value = m->phys_store32 ? 1 : 0;
+    else if (key == "staged_products") *value = staged_products(m) ? 1 : 0;  // (read-only: which forward table the step uses)
     else if (key == "quiet_rim_members") {
         // members whose rim the last multi-step call found quiet (step_impl); -1 when the last call did not look (one step, or
         // launches that fold the geopotential).  Waits for the device: the call's streams were joined into the caller's.

@@ -66,6 +66,7 @@ struct spd_model {
     // ... and both with the physics-only outputs (time-level-1 T, q, phi, ln ps, lowest-level u, v) stored as fp32 (cfg 5)
     FieldDesc *inv_table32[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *inv_table_sppt32[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     FieldDesc *fwd_table = nullptr;
+    FieldDesc *fwd_table_products = nullptr;  // the same transforms, the 40 products formed while staging (fused column kernel)
     // Geopotential, double-buffered.  spectral_step_kernel ends by computing the geopotential the NEXT step needs (from the
     // temperature it has just advanced) into the buffer that is not in use; the next step switches to it instead of running
     // geopotential_kernel.  The registry's "phi" is always the buffer the last step USED (the reference's state%phi after a

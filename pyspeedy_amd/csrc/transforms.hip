@@ -28,14 +28,17 @@
 //     later kernel, and keeping them out of the L2 leaves it to the Legendre table and the shared inputs (measured: +15 %
 //     on the spectral -> grid kernel).  In the model step the spectral -> grid kernel can apply the
 //     spectral operator in front of the transform while it stages the coefficients (FieldDesc::mode: vort2vel, gradient),
-//     so u, v and grad ln ps are never materialised as spectral fields.
+//     so u, v and grad ln ps are never materialised as spectral fields.  The grid -> spectral kernel likewise forms the flux
+//     and kinetic-energy products of u, v, T, q while it stages the rows (stage_product_rows), so they are never grid fields.
 #include <hip/hip_runtime.h>
 
 #include "device_tables.hpp"
 #include "diagnostics_block.hpp"
 #include "launch_events.hpp"
 #include "fft96.hpp"
+#include "staged_products.hpp"
 #include "triangle.hpp"
+#include "vertical_consts.hpp"
 
 namespace spd {
 
@@ -305,13 +308,92 @@ __device__ __forceinline__ void spec2grid_body(const double *__restrict__ src, d
     TRACE_END(0);
 }
 
+// The product mode of the fused grid -> spectral transform (FieldDesc::mode != 0): stages the rows of a field that is a
+// pointwise product of two source fields (staged_products.hpp), which is formed here and never stored.
+__device__ __forceinline__ void stage_product_rows(double *lds, const double *__restrict__ src, const double *__restrict__ src2,
+                                                   const DeviceTables &T, int prescale, int mode) {
+    constexpr int kPairTasks = IY * (IX / 2);                              // 24 latitude pairs x 48 16-byte pieces
+    constexpr int kPairPerLane = (kPairTasks + kThreads - 1) / kThreads;  // 3
+    const int tid = threadIdx.x;
+    double *rows = lds;
+    gd2_in g = (gd2_in)src;
+    const double *ctab = (prescale == 1) ? T.cosgr : T.cosgr2;
+    // A lane has four 16-byte loads per pair-task instead of two: 48 registers of data when all three tasks are in flight, which
+    // they are -- one trip to memory, as in the plain path.  What keeps the kernel at its 64 registers (8 wavefronts per SIMD):
+    // the loads address their field by its base (uniform, in scalar registers) plus a 32-bit lane offset shared by the two
+    // sources, and wt / cosgr, which in the plain path wait in 18 registers, are parked in LDS behind the rows by the
+    // first 72 lanes and read from there while the tasks retire one by one (product, scale, north +- south, store to the rows).
+    // The third task exists for wavefronts 0 and 1 only (1152 tasks over 512 lanes).
+    // Every source is read by the two or three workgroups that need it (same member and level, hence the same XCD and dispatched
+    // together: model.hip build_tables).  The loads carry the streaming hint all the same: measured both ways
+    // (profiles/staged_products_ab.txt), plain loads share the sources perfectly (65 fields fetched per member) but leave them in
+    // the L2 for the spectral step to stumble over; hinted loads still share most of them (75 of the 113 read) and the step is
+    // 1 % faster.
+    gd2_in gb = (gd2_in)src2;
+    // (the two fluxes are one expression: the tracer's has tref = 0)
+    const int kind = (mode & ((1 << kProdLevelShift) - 1)) == kProdKe ? kProdKe : kProdFluxT;
+    const double tref = (mode & ((1 << kProdLevelShift) - 1)) == kProdFluxT ? vc::tref[(mode >> kProdLevelShift) & (KX - 1)] : 0.0;
+    static_assert(kRows * kRowStride + IY + kRows <= kCBufDoubles + 2 * NSPEC, "wt and ctab fit behind the rows");
+    double *tab = lds + kRows * kRowStride;  // wt[24] | ctab[48], in the 352 doubles the FFT rows leave free
+    double tv = 0.0;
+    if (tid < IY)
+        tv = T.wt[tid];
+    else if (tid < IY + kRows)
+        tv = ctab[tid - IY];
+    d2 an[kPairPerLane], as_[kPairPerLane], bn[kPairPerLane], bs[kPairPerLane];
+#pragma unroll
+    for (int it = 0; it < kPairPerLane; ++it) {
+        const unsigned idx = tid + it * kThreads;
+        if (idx < kPairTasks) {
+            const unsigned j = idx / (IX / 2), ip = idx - j * (IX / 2);
+            const unsigned in = (kRows - 1 - j) * (IX / 2) + ip, is = j * (IX / 2) + ip;
+            an[it] = __builtin_nontemporal_load(&g[in]);
+            as_[it] = __builtin_nontemporal_load(&g[is]);
+            bn[it] = __builtin_nontemporal_load(&gb[in]);
+            bs[it] = __builtin_nontemporal_load(&gb[is]);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (tid < IY + kRows) tab[tid] = tv;
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < kPairPerLane; ++it) {
+        const int idx = tid + it * kThreads;
+        if (idx < kPairTasks) {
+            const int j = idx / (IX / 2), ip = idx - j * (IX / 2);
+            const double w = tab[j];
+            const double cn = (prescale != 0) ? tab[IY + kRows - 1 - j] : 1.0, cs = (prescale != 0) ? tab[IY + j] : 1.0;
+            // each product is a value of its own before it meets the prescale or the north +- south sums
+            d2 n, so;
+            n.x = staged_product(kind, an[it].x, bn[it].x, tref);
+            n.y = staged_product(kind, an[it].y, bn[it].y, tref);
+            so.x = staged_product(kind, as_[it].x, bs[it].x, tref);
+            so.y = staged_product(kind, as_[it].y, bs[it].y, tref);
+            if (prescale != 0) {
+                n.x *= cn;
+                n.y *= cn;
+                so.x *= cs;
+                so.y *= cs;
+            }
+            double *rn = rows + (kRows - 1 - j) * kRowStride + 2 * ip, *rs = rows + j * kRowStride + 2 * ip;
+            rn[0] = (n.x + so.x) * w;
+            rn[1] = (n.y + so.y) * w;
+            rs[0] = (n.x - so.x) * w;
+            rs[1] = (n.y - so.y) * w;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // grid -> spec.  prescale: 0 none, 1 multiply rows by cosgr, 2 by cosgr2 (spectral.f90:229-243)
 // [| kSpecPacked, fused form: dst receives the tri::kPacked filled coefficients only (triangle.hpp), not the rectangle]
+// mode (fused form, descriptor-table launches): 0 transforms src; otherwise the field is a product of src and src2
+// (staged_products.hpp: kind | level << 8), formed while the rows are staged.
 // ------------------------------------------------------------------------------------------------
 template <Stage ST>
 __device__ __forceinline__ void grid2spec_body(const double *__restrict__ src, double *__restrict__ dst,
-                                               const DeviceTables &T, int prescale) {
+                                               const DeviceTables &T, int prescale, int mode = 0,
+                                               const double *__restrict__ src2 = nullptr) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *rows = lds;                                    // R[48][97] while the FFT runs
     double *cbuf = lds;                                    // C[48][63] afterwards (aliases R)
@@ -335,39 +417,43 @@ __device__ __forceinline__ void grid2spec_body(const double *__restrict__ src, d
         gd2_in g = (gd2_in)src;
         constexpr int kPairTasks = IY * (IX / 2);                              // 24 latitude pairs x 48 16-byte pieces
         constexpr int kPairPerLane = (kPairTasks + kThreads - 1) / kThreads;  // 3
-        d2 gn[kPairPerLane], gs[kPairPerLane];
-        double wj[kPairPerLane], cn[kPairPerLane], cs[kPairPerLane];
-        const double *ctab = (prescale == 1) ? T.cosgr : T.cosgr2;
+        if (mode != kProdNone) {
+            stage_product_rows(lds, src, src2, T, prescale, mode);
+        } else {
+            d2 gn[kPairPerLane], gs[kPairPerLane];
+            double wj[kPairPerLane], cn[kPairPerLane], cs[kPairPerLane];
+            const double *ctab = (prescale == 1) ? T.cosgr : T.cosgr2;
 #pragma unroll
-        for (int it = 0; it < kPairPerLane; ++it) {
-            const int idx = tid + it * kThreads;
-            if (idx < kPairTasks) {
-                const int j = idx / (IX / 2), ip = idx - j * (IX / 2);
-                gn[it] = __builtin_nontemporal_load(&g[(kRows - 1 - j) * (IX / 2) + ip]);  // read once, by this workgroup only
-                gs[it] = __builtin_nontemporal_load(&g[j * (IX / 2) + ip]);
-                wj[it] = T.wt[j];
-                cn[it] = (prescale != 0) ? ctab[kRows - 1 - j] : 1.0;
-                cs[it] = (prescale != 0) ? ctab[j] : 1.0;
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < kPairPerLane; ++it) {
-            const int idx = tid + it * kThreads;
-            if (idx < kPairTasks) {
-                const int j = idx / (IX / 2), ip = idx - j * (IX / 2);
-                d2 n = gn[it], so = gs[it];
-                if (prescale != 0) {  // rows times cosgr / cosgr2 first (spectral.f90:229-243), then the pair's Gaussian weight
-                    n.x *= cn[it];
-                    n.y *= cn[it];
-                    so.x *= cs[it];
-                    so.y *= cs[it];
+            for (int it = 0; it < kPairPerLane; ++it) {
+                const int idx = tid + it * kThreads;
+                if (idx < kPairTasks) {
+                    const int j = idx / (IX / 2), ip = idx - j * (IX / 2);
+                    gn[it] = __builtin_nontemporal_load(&g[(kRows - 1 - j) * (IX / 2) + ip]);  // read once, by this workgroup only
+                    gs[it] = __builtin_nontemporal_load(&g[j * (IX / 2) + ip]);
+                    wj[it] = T.wt[j];
+                    cn[it] = (prescale != 0) ? ctab[kRows - 1 - j] : 1.0;
+                    cs[it] = (prescale != 0) ? ctab[j] : 1.0;
                 }
-                const double w = wj[it];
-                double *an = rows + (kRows - 1 - j) * kRowStride + 2 * ip, *as = rows + j * kRowStride + 2 * ip;
-                an[0] = (n.x + so.x) * w;
-                an[1] = (n.y + so.y) * w;
-                as[0] = (n.x - so.x) * w;
-                as[1] = (n.y - so.y) * w;
+            }
+#pragma unroll
+            for (int it = 0; it < kPairPerLane; ++it) {
+                const int idx = tid + it * kThreads;
+                if (idx < kPairTasks) {
+                    const int j = idx / (IX / 2), ip = idx - j * (IX / 2);
+                    d2 n = gn[it], so = gs[it];
+                    if (prescale != 0) {  // rows times cosgr / cosgr2 first (spectral.f90:229-243), then the pair's Gaussian weight
+                        n.x *= cn[it];
+                        n.y *= cn[it];
+                        so.x *= cs[it];
+                        so.y *= cs[it];
+                    }
+                    const double w = wj[it];
+                    double *an = rows + (kRows - 1 - j) * kRowStride + 2 * ip, *as = rows + j * kRowStride + 2 * ip;
+                    an[0] = (n.x + so.x) * w;
+                    an[1] = (n.y + so.y) * w;
+                    as[0] = (n.x - so.x) * w;
+                    as[1] = (n.y - so.y) * w;
+                }
             }
         }
     } else if (ST == Stage::FourierOnly) {
@@ -575,7 +661,7 @@ __global__ __launch_bounds__(kThreads, 8) void spec2grid_table_check_kernel(cons
 
 __global__ __launch_bounds__(kThreads) void grid2spec_table_kernel(const FieldDesc *__restrict__ table, DeviceTables T) {
     const FieldDesc e = table[blockIdx.x];
-    grid2spec_body<Stage::Fused>(e.src, e.dst, T, e.flag);
+    grid2spec_body<Stage::Fused>(e.src, e.dst, T, e.flag, e.mode, e.src2);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -264,13 +264,20 @@ class EnsembleModel:
 
     def config(self):
         """How the step is configured: dict(inv_per_member, diag_every_step, chunks, split_dyn, ...) -- spd_model_get_config.
-        The land / sea-ice coupling always rides in spectral_step_kernel: its key is always True."""
+        The land / sea-ice coupling always rides in spectral_step_kernel: its key is always True.  forward_table: "products" when
+        the step's grid -> spectral launch forms the flux and kinetic-energy products itself (the fused column kernel, which does
+        not store them), "plain" when it reads them from memory (split_dyn: the stand-alone dynamics kernel stores them)."""
         cfg = (C.c_int32 * 8)()
         check(self._lib.spd_model_get_config(self._m, cfg), "spd_model_get_config")
         created, apart = C.c_int32(0), C.c_int32(1)
         check(self._lib.spd_model_group_streams(self._m, C.byref(created), C.byref(apart)), "spd_model_group_streams")
         block = C.c_int32(0)
         check(self._lib.spd_model_get_option(self._m, b"block_members", C.byref(block)), "spd_model_get_option")
+        # (a library from before the product table -- PYSPEEDY_AMD_LIB, tools/build_variant.sh -- does not know the name: plain)
+        staged = C.c_int32(0)
+        rc = self._lib.spd_model_get_option(self._m, b"staged_products", C.byref(staged))
+        if rc != _lib.SPD_E_ARG:
+            check(rc, "spd_model_get_option")
         streams, M = cfg[2], self.nmembers
         # (as spd_model_step forms them: rounds of `chunks` x `block_members` members from 4 x block_members members up; not while
         # profiling or with separate dynamics / physics launches, which step everybody as one group)
@@ -280,7 +287,7 @@ class EnsembleModel:
         return dict(inv_per_member=cfg[0], diag_every_step=bool(cfg[1]), chunks=cfg[2], split_dyn=bool(cfg[3]),
                     fold_geo=bool(cfg[4]), coupler_in_spectral=bool(cfg[5]), physics_fp32=bool(cfg[6]),
                     physics_storage32=bool(cfg[7]), group_streams=created.value, group_streams_apart=bool(apart.value),
-                    block_members=block.value, rounds=rounds)
+                    block_members=block.value, rounds=rounds, forward_table="products" if staged.value else "plain")
 
     def set_option(self, name, value):
         """A launch-plan switch of the live model by name (spd_model_set_option: diag_every_step, spectral_early, split_dyn,

@@ -91,7 +91,13 @@ int spd_vort2vel(spd_handle h, const double *vor, const double *div, double *uco
                  void *stream);
 int spd_vel2vort(spd_handle h, const double *ucos, const double *vcos, double *vor, double *div, int nfields,
                  void *stream);
-/* grid_vel2vort: kcos == 2 -> pre-multiply by cosgr, otherwise by cosgr2 (spectral.f90:229-243) */
+/* grid_vel2vort: kcos == 2 -> pre-multiply by cosgr, otherwise by cosgr2 (spectral.f90:229-243)
+ * spd_grid_vel2vort and spd_grid_filter keep their spectral intermediates in ONE scratch buffer per handle, which lives until
+ * spd_destroy and only ever grows.  Calls of either on one handle must therefore be ordered on one stream (or by the caller's
+ * own events): two of them in flight on different streams would share the buffer.  A call with a larger batch than any before
+ * it on that handle frees and reallocates the buffer and synchronises the DEVICE first (hipDeviceSynchronize: it is not
+ * stream-ordered and cannot be captured into a graph); size the buffer beforehand with one call of spd_grid_vel2vort at the
+ * largest batch.  spd_grid_filter may work in place (fg1 == fg2). */
 int spd_grid_vel2vort(spd_handle h, const double *ug, const double *vg, double *vor, double *div, int kcos,
                       int nfields, void *stream);
 int spd_gradient(spd_handle h, const double *psi, double *psdx, double *psdy, int nfields, void *stream);

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from transform_bands import seeded_spectra  # (shared with the band and batch tests)
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-13
@@ -102,17 +104,6 @@ def test_golden_spectral_operators(spectral, gold):
         close(back(di)[0], gold["grid_vel2vort_k1k2"][i][1], what="grid_vel2vort div kcos=%d" % kc)
     for i, b in enumerate((4, 8)):
         close(back(spectral.grid_filter(grid_dev(gold["grid_in"][b][None])))[0], gold["grid_filter"][i], what="grid_filter")
-
-
-def seeded_spectra(n, seed=1234, triangular=True):
-    rng = np.random.default_rng(seed)
-    nn, mm = np.meshgrid(np.arange(32), np.arange(31), indexing="ij")
-    ll = mm + nn
-    s = (rng.standard_normal((n, 32, 31)) + 1j * rng.standard_normal((n, 32, 31))) / (1.0 + ll)
-    if triangular:
-        s[:, ll > 30] = 0.0
-    s[:, :, 0] = s[:, :, 0].real
-    return s
 
 
 @pytest.mark.parametrize("nfields", [1, 2, 3, 8, 64, 513])

@@ -836,6 +836,91 @@ int spd_model_breed_gram(spd_model_handle m, void *dst_device, size_t dst_bytes,
 int spd_breed_family_check(const int32_t *control, int members);
 int spd_breed_factor_host(const double *gram, int r, double target, double *rdiag, double *coef, int *rank);
 int spd_model_breed_ortho_info(spd_model_handle m, int *on, int *families, int *largest);
+/* Assimilation: a serial ensemble square-root filter (EnSRF, Whitaker & Hamill 2002) with at most 64 scalar observations, taken
+ * through projection-tape weight maps, and at most 64 members, computed and applied on the device at scheduled steps inside
+ * spd_model_step / spd_model_step_checked_begin calls of any length (in-loop mode) or once on the state as it stands (_apply); and
+ * the member-mixing transform on its own for a caller's matrix (_transform).  Off unless configured, and a model that never
+ * configures it issues the launches it always issued.
+ * Configuration.  P weight maps, 1 <= P <= 64, fp64 [48][96], finite: the projection tape's layout and rules.  E entries (name,
+ * level, pattern), 1 <= E <= 64; name is one of the projection tape's names but precnv and precls (outputs of the column physics,
+ * not functions of the state); the *_plev names and mslp need spd_model_plev_configure first.  mask[M] (int32, 0 or 1): the members
+ * with mask 1 are a_0 < ... < a_(r-1), 2 <= r <= 64; a member with mask 0 (a nature run) is never loaded nor stored.  every >= 1;
+ * capacity >= 1 slots of the diagnostics ring; inflation rho, finite and >= 1.
+ * Observations.  A host table of n_rows rows: strictly ascending absolute step stamps steps[n_rows], values yo[n_rows][E] (NaN:
+ * missing; an infinite value is refused) and error variances var[n_rows][E] (finite, > 0).  It may be replaced between calls.
+ * Event.  In-loop, after the step that leaves the absolute step counter at n with n % every == 0: if a row is stamped exactly n
+ * the analysis below runs before step n + 1 starts; if not, the event is skipped -- no launch, and `skipped` counts it.  _apply is
+ * the same event once, refused if no row carries the current step.
+ * 1 Observation-space ensemble.  Y[e][i] is the value of entry e for member a_i: exactly the projection tape's result for that
+ *   entry (the same front end, export units, lane order and tree), by the projection tape's kernel into a one-slot ring.
+ * 2 Weights, in fp64, every operation rounded on its own (no fused multiply-add), every sum sequential in ascending index and
+ *   starting from its first term:
+ *     a = (1 - rho) / r;   W[i][j] = a for i != j,   W[i][i] = a + rho                      (rho = 1: the exact identity)
+ *     for e = 0 ... E-1:
+ *       y_j = sum_i Y[e][i] W[i][j];   ybar = (sum_j y_j) / r;   d_j = y_j - ybar;   s = (sum_j d_j d_j) / (r - 1)
+ *       the entry is UNUSED (W as it is) if yo[e] is NaN or s is not a finite number > 0; otherwise
+ *       t = s + var[e];   alpha = 1 / (1 + sqrt(var[e] / t));   v = yo[e] - ybar;   q = (r - 1) t
+ *       g_i = d_i / q;   c_j = v - alpha d_j;   u_k = sum_i W[k][i] g_i;   W[k][j] = W[k][j] + u_k c_j
+ *   In exact arithmetic this is the EnSRF: the mean moves by the Kalman gain, the perturbations by alpha times it, and a later
+ *   observation sees the updated ensemble (its prior is recomputed from Y and W, not carried along).
+ * 3 Transform, for vor, div, t, tr, ps (33 planes), BOTH time levels, every coefficient with m + nn <= 31, real and imaginary part
+ *   separately, X the members' states as they stood before the event:
+ *     X'_(a_j) = (...((W[0][j] X_(a_0)) + W[1][j] X_(a_1)) + ...) + W[r-1][j] X_(a_(r-1))
+ *   Coefficients with m + nn >= 32 are neither loaded nor stored (the quiet rim stays valid); members outside the mask and every
+ *   other registry variable are untouched -- the surface models' prognostic anomalies among them.
+ * 4 Ring: one slot per executed event, [E][4] fp64 = ybar, s, v, used (1.0 / 0.0); v is 0.0 for a missing observation.  The step
+ *   counter and date of an event are kept on the host (_rows: 6 int32 per event, oldest first).  W [64][64] (zero beyond r) and
+ *   Y [E][r] of the last event stay readable (_weights).
+ * A call with in-loop assimilation is issued in segments that end at the multiples of `every`, as a call with in-loop breeding is;
+ * it is bit for bit the host loop  step(k); _apply; step(k); ...  -- checked calls included.  In-loop assimilation and in-loop
+ * breeding together are refused by whichever _configure comes second; nudging inside the segments is unaffected.  While
+ * assimilation loops the geopotential look-ahead of small ensembles is off, as under in-loop nudging.
+ *   _configure  one hipMalloc of its own (synchronises the device); the ring is empty, the observation table empty, `applied` 0.
+ *               SPD_E_ARG, before anything is allocated, in this order: every < 1; capacity < 1; inflation not finite or < 1;
+ *               in_loop neither 0 nor 1; n_patterns outside 1 ... 64; n_entries outside 1 ... 64; null weights; null lists; a
+ *               weight that is not finite (pattern, point, row, column); per entry an unknown name, precnv / precls, a level or
+ *               pattern out of range; a null mask; a null model; a checked call in flight; a mask entry that is not 0 or 1; r
+ *               outside 2 ... 64; a pressure-level name without target levels; in-loop breeding configured.
+ *   spd_assim_check  the same checks without a model, for `members` members (mask may be NULL: only the rest is checked then).
+ *   _off        switches it off and frees everything.
+ *   _set_observations  replaces the table (n_rows = 0 empties it).  SPD_E_ARG, in this order: n_rows < 0; n_entries outside
+ *               1 ... 64; null arrays; stamps not strictly ascending (row named); a variance that is not a finite number > 0, an
+ *               infinite observation (row and entry named); then a null model, a checked call in flight, no configuration,
+ *               n_entries that is not the configuration's E.
+ *   _apply      the event once on the state as it stands, stream-ordered; writes a ring slot; drops the look-ahead geopotential and
+ *               the day's interpolated climatologies as spd_model_set does, and settles a deferred range check first.
+ *   _compute    Y [E][r] (fp64) of the state as it stands into device memory; writes no state and no ring.  It uses the
+ *               configuration's slab: order it against _apply and the steps by the stream.
+ *   _transform  step 3 alone with the caller's finite matrix w[r][r] (row-major, host memory) for the distinct members
+ *               members[r], 1 <= r <= 64, with or without an assimilation configured; the host waits for the stream once while
+ *               its copies of w and members are taken, the launch itself is stream-ordered.
+ *   _read       the events [t0, t0 + nt) of the held ones, oldest first, as [nt][E][4] fp64 into device memory; refused after a
+ *               failed range check of a checked call until _reset or spd_model_init.
+ *   _weights    W [64][64] and Y [E][r] of the last executed event into device memory (stream-ordered copies).
+ *   _reset      empties the ring and `skipped` (no device work).
+ *   _info       r, E, every, capacity, events taken and skipped since _configure / _reset, the mode, and `applied`: the events
+ *               executed since _configure; any pointer may be NULL; all zero without a configuration.
+ *   spd_assim_weights_host  step 2 as the device runs it, compiled for the host: y [E][r], yo[E], var[E] -> w_out [r][r] row-major
+ *               and stats_out [E][4] as a ring slot.
+ * spd_model_init empties the ring.  spd_model_copy_member does not carry the configuration, and the outer boundary
+ * (spd_parallel_step*) does not keep it. */
+int spd_assim_check(const double *weights, int n_patterns, const char *const *names, const int *levels, const int *patterns, int n_entries,
+                    const int32_t *mask, int members, int every, int capacity, double inflation, int in_loop);
+int spd_model_assim_configure(spd_model_handle m, const double *weights, int n_patterns, const char *const *names, const int *levels,
+                              const int *patterns, int n_entries, const int32_t *mask, int every, int capacity, double inflation, int in_loop);
+int spd_model_assim_off(spd_model_handle m);
+int spd_model_assim_set_observations(spd_model_handle m, const int32_t *steps, int n_rows, const double *yo, const double *var, int n_entries);
+int spd_model_assim_apply(spd_model_handle m, void *stream);
+int spd_model_assim_compute(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_assim_transform(spd_model_handle m, const int32_t *members, int r, const double *w, void *stream);
+int spd_model_assim_read(spd_model_handle m, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_assim_weights(spd_model_handle m, void *w_device, size_t w_bytes, void *y_device, size_t y_bytes, void *stream);
+int spd_model_assim_rows(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_assim_reset(spd_model_handle m);
+int spd_model_assim_info(spd_model_handle m, int *r, int *n_entries, int *every, int *capacity, long long *taken, long long *skipped, int *in_loop,
+                         long long *applied);
+int spd_assim_weights_host(const double *y, int n_entries, int r, const double *yo, const double *var, double inflation, double *w_out,
+                           double *stats_out);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

@@ -12,7 +12,8 @@
 !! the ensemble mean and spread (spd_model_enstape_*), window sums, means and extremes of the physics fluxes (spd_model_acctape_*)
 !! window means, extremes and threshold counts of the state's fields (spd_model_wintape_*, spd_wintape_plan), and nudging of the
 !! spectral state toward target fields inside the device loop (spd_model_nudge_*), and breeding: the rescaling of member
-!! perturbations against their control runs inside the device loop (spd_model_breed_*, spd_breed_check), orthonormalised on request
+!! perturbations against their control runs inside the device loop (spd_model_breed_*, spd_breed_check), orthonormalised on request,
+!! and assimilation: an ensemble square-root filter inside the device loop (spd_model_assim_*, spd_assim_check)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -522,6 +523,97 @@ module pyspeedy_amd_c
             import :: c_ptr, c_int
             type(c_ptr), value :: model
             integer(c_int), intent(out) :: on, families, largest
+        end function
+        ! assimilation: a serial ensemble square-root filter whose observations are projection-tape entries, inside the device loop
+        ! (in_loop = 1) or once on the state as it stands (_apply), and the member-mixing transform for a caller's matrix
+        ! (pyspeedy_amd.h: spd_model_assim_*).  weights(96, 48, n_patterns); entries as the projection tape's; mask: one
+        ! integer(c_int32_t) per member (0 or 1), or c_null_ptr for spd_assim_check; yo and var (n_entries, n_rows); _read:
+        ! real(c_double) (4, n_entries, nt) in device memory; _weights: (64, 64) (in Fortran: the transpose) and (r, n_entries);
+        ! _transform: w is row-major r x r (in Fortran: the transpose), members 0-based; rows(6, *)
+        integer(c_int) function spd_assim_check(weights, n_patterns, names, levels, patterns, n_entries, mask, members, every, &
+                capacity, inflation, in_loop) bind(C, name="spd_assim_check")
+            import :: c_ptr, c_int, c_double
+            real(c_double), intent(in) :: weights(*)
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), patterns(*)
+            type(c_ptr), value :: mask
+            real(c_double), value :: inflation
+            integer(c_int), value :: n_patterns, n_entries, members, every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_assim_configure(model, weights, n_patterns, names, levels, patterns, n_entries, mask, &
+                every, capacity, inflation, in_loop) bind(C, name="spd_model_assim_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model, mask
+            real(c_double), intent(in) :: weights(*)
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), patterns(*)
+            real(c_double), value :: inflation
+            integer(c_int), value :: n_patterns, n_entries, every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_assim_off(model) bind(C, name="spd_model_assim_off")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_assim_set_observations(model, steps, n_rows, yo, var, n_entries) &
+                bind(C, name="spd_model_assim_set_observations")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(in) :: steps(*)
+            real(c_double), intent(in) :: yo(*), var(*)
+            integer(c_int), value :: n_rows, n_entries
+        end function
+        integer(c_int) function spd_model_assim_apply(model, stream) bind(C, name="spd_model_assim_apply")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, stream
+        end function
+        integer(c_int) function spd_model_assim_compute(model, dst_device, dst_bytes, stream) bind(C, name="spd_model_assim_compute")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_assim_transform(model, members, r, w, stream) bind(C, name="spd_model_assim_transform")
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: model, stream
+            integer(c_int32_t), intent(in) :: members(*)
+            integer(c_int), value :: r
+            real(c_double), intent(in) :: w(*)
+        end function
+        integer(c_int) function spd_model_assim_read(model, t0, nt, dst_device, dst_bytes, stream) bind(C, name="spd_model_assim_read")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_assim_weights(model, w_device, w_bytes, y_device, y_bytes, stream) &
+                bind(C, name="spd_model_assim_weights")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, w_device, y_device, stream
+            integer(c_size_t), value :: w_bytes, y_bytes
+        end function
+        integer(c_int) function spd_model_assim_rows(model, rows, max_rows) bind(C, name="spd_model_assim_rows")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_assim_reset(model) bind(C, name="spd_model_assim_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_assim_info(model, r, n_entries, every, capacity, taken, skipped, in_loop, applied) &
+                bind(C, name="spd_model_assim_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_int), intent(out) :: r, n_entries, every, capacity, in_loop
+            integer(c_long_long), intent(out) :: taken, skipped, applied
+        end function
+        integer(c_int) function spd_assim_weights_host(y, n_entries, r, yo, var, inflation, w_out, stats_out) &
+                bind(C, name="spd_assim_weights_host")
+            import :: c_int, c_double
+            real(c_double), intent(in) :: y(*), yo(*), var(*)
+            integer(c_int), value :: n_entries, r
+            real(c_double), value :: inflation
+            real(c_double), intent(out) :: w_out(*), stats_out(*)
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
         ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for

@@ -189,6 +189,24 @@ _SIGNATURES = {
     "spd_breed_family_check": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
     "spd_breed_factor_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "spd_model_breed_ortho_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3),
+    "spd_assim_check": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]),
+    "spd_model_assim_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double, C.c_int]),
+    "spd_model_assim_off": (C.c_int, [C.c_void_p]),
+    "spd_model_assim_set_observations": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                   C.c_int]),
+    "spd_model_assim_apply": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "spd_model_assim_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_assim_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.c_void_p]),
+    "spd_model_assim_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_assim_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_assim_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_assim_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_assim_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)] * 2 + [C.POINTER(C.c_int),
+                                                                                                                  C.POINTER(C.c_longlong)]),
+    "spd_assim_weights_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),

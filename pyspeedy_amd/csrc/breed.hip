@@ -574,6 +574,9 @@ int spd_model_breed_configure(spd_model_handle m, const int32_t *control, const 
     if (int rc = configure_allowed(m, who)) return rc;
     if (control)
         if (int rc = spd_breed_check(control, m->M, weights, target, every, capacity, in_loop)) return rc;
+    if (control && in_loop && m->assim.loops())
+        return m_fail(SPD_E_ARG, std::string(who) + ": in-loop breeding cannot be configured while in-loop assimilation (spd_model_assim_configure) is: "
+                                                    "both cut the call at their own steps; switch one of them off or to in_loop = 0");
     spd_model::Breed &br = m->breed;
     void *const ortho = br.ortho.alloc;  // (retired with the rest, behind retire's synchronisation)
     br.ortho.alloc = nullptr;

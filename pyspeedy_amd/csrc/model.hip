@@ -1,7 +1,7 @@
 // Ensemble model object: device-resident state of M members + the step driver (time_stepping.f90:38-147 `step`,
 // tendencies.f90:11-39 `get_tendencies`) built from the hot-path kernels and the dynamics kernels.
 // C ABI: the spd_model_* functions of include/pyspeedy_amd.h, but for those of the in-loop features (statistics, tapes, spectra,
-// nudging, breeding, pressure levels), which lie with their kernels in the feature's own file; model_state.hpp is what they share.
+// nudging, breeding, assimilation, pressure levels), which lie with their kernels in the feature's own file; model_state.hpp is what they share.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -696,6 +696,8 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->nudge.alloc) (void)hipFree(m->nudge.alloc);
     if (m->breed.alloc) (void)hipFree(m->breed.alloc);
     if (m->breed.ortho.alloc) (void)hipFree(m->breed.ortho.alloc);
+    if (m->assim.alloc) (void)hipFree(m->assim.alloc);
+    if (m->assim_xf.alloc) (void)hipFree(m->assim_xf.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -891,8 +893,9 @@ struct ProfScope {
 // Returns whether the stand-alone kernel has to run.  Called once per step (not per member group).
 // Whether the spectral step computes the next step's geopotential.  Not while a nudging launch follows every step: it changes the
 // temperature behind the spectral step, and the look-ahead geopotential would be that of the temperature before it.  The fold
-// comes back when in-loop nudging is switched off.
-static bool folds(const spd_model *m) { return m->fold_geo && !m->nudge.loops(); }
+// comes back when in-loop nudging is switched off.  Not while assimilation loops either, for the same reason: the analysis
+// rewrites the temperature the look-ahead was computed from.
+static bool folds(const spd_model *m) { return m->fold_geo && !m->nudge.loops() && !m->assim.loops(); }
 
 static bool begin_step_geopotential(spd_model *m) {
     const bool fold = folds(m);
@@ -1266,6 +1269,9 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->wintape.validity.clear();
     m->projtape.ring.clear();  // (... and an empty projection tape)
     m->projtape.validity.clear();
+    m->assim.ring.clear();  // (... and no assimilation event)
+    m->assim.validity.clear();
+    m->assim.skipped = 0;
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1710,16 +1716,22 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
 // segment does its own bookkeeping exactly as a call of its own would -- recorder counters, open windows, nudge.applied -- so the
 // call is, bit for bit, the host loop  run(k); breed_apply(); run(k); ...  The last step of a segment carries its own range check
 // in front of the join: the check and every recorder's sample of a rescale step see the state the step left.
+//
+// In-loop assimilation cuts the call the same way at the multiples of its own `every`, and its event
+// (assim_event: skipped without a launch when no row of observations carries the step) goes out where the breeding launches
+// would.  The two cannot loop together: the second _configure is refused.
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
-    if (!m || !m->breed.loops() || nsteps < 1) return step_segment(m, nsteps, stream, record, who, 0, nsteps);
-    const int every = m->breed.every;
+    const bool breeds = m && m->breed.loops(), assimilates = m && !breeds && m->assim.loops();
+    if (!m || (!breeds && !assimilates) || nsteps < 1) return step_segment(m, nsteps, stream, record, who, 0, nsteps);
+    const int every = breeds ? m->breed.every : m->assim.every;
     for (int done = 0; done < nsteps;) {
         const int phase = ((m->current_step % every) + every) % every;
         const int len = std::min(every - phase, nsteps - done);
         if (int rc = step_segment(m, len, stream, record, who, done, nsteps)) return rc;
         done += len;
         if (m->current_step % every == 0)
-            if (int rc = breed_rescale(m, static_cast<hipStream_t>(stream), who)) return rc;
+            if (int rc = breeds ? breed_rescale(m, static_cast<hipStream_t>(stream), who) : assim_event(m, static_cast<hipStream_t>(stream), who, true))
+                return rc;
     }
     return SPD_OK;
 }
@@ -1776,6 +1788,7 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
         if (m->acctape.on && m->acctape.validity.valid) m->acctape.validity.fail(i, *failed);
         if (m->wintape.on && m->wintape.validity.valid) m->wintape.validity.fail(i, *failed);
         if (m->projtape.on && m->projtape.validity.valid) m->projtape.validity.fail(i, *failed);
+        if (m->assim.on && m->assim.validity.valid) m->assim.validity.fail(i, *failed);
     }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)

@@ -2,7 +2,7 @@
 // the carving of an allocation that every in-loop feature's _configure and _read run around their own work; the front end of a
 // sample that the statistics and four of the tapes share (defined in model.hip).  model.hip holds the model's life, its registry,
 // the step loop and the rest of the C ABI; the host code of each in-loop feature lies behind its kernels in the feature's own file
-// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, plev.hip).
+// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, plev.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +26,7 @@
 #include "acctape.hpp"
 #include "nudge.hpp"
 #include "breed.hpp"
+#include "assim.hpp"
 #include "wintape.hpp"
 #include "projtape.hpp"
 #include "ring.hpp"
@@ -368,6 +369,44 @@ struct spd_model {
         } ortho;
         bool loops() const { return on && in_loop && nbred > 0; }  // spd_model_step is issued in segments
     } breed;
+    // Assimilation (spd_model_assim_*): a serial ensemble square-root filter over the masked members, after every step that leaves
+    // the step counter at a multiple of `every` AND carries a row of observations (assim.hip).  Like breeding it couples members
+    // across member groups and rounds, so a call with in-loop assimilation is issued as segments that end at those steps
+    // (step_impl) and the event goes out on the caller's stream behind the join.  One allocation of its own (hipMalloc): the ring
+    // [capacity][E][4] (`data`), the patterns [P][4608], slab, tables, the projection kernel's plane descriptors and entry list,
+    // the one-slot projection ring [M][E] (`yraw`), Y [E][r], W [64][64], the member list and the transform's plane descriptors.
+    // The observation table is host state: the row of an event travels to the weights kernel by value.
+    struct Assim : SampleFront {
+        struct Entry {
+            int name, level, pattern;  // name: catalogue id
+        };
+        bool on = false, in_loop = false;
+        int every = 0, npatterns = 0, nplanes = 0, r = 0;
+        double inflation = 1.0;
+        SampleRing ring;  // of executed events since _configure / _reset; rows [6]: step counter, y, m, d, h, min of an event's state
+        Validity validity;
+        long long applied = 0, skipped = 0;  // events executed since _configure; in-loop events without a row since _configure / _reset
+        std::vector<Entry> entries;
+        std::vector<int> members;                   // a_0 < ... < a_(r-1)
+        std::vector<std::pair<int, int>> ranges;    // the masked members as (first, count) of consecutive indices
+        std::vector<int> obs_steps;                 // [T], strictly ascending
+        std::vector<double> obs_yo, obs_var;        // [T][E]
+        void *alloc = nullptr;
+        double *data = nullptr, *weights = nullptr, *yraw = nullptr, *Y = nullptr, *W = nullptr;
+        int *member_list = nullptr;
+        ProjTapePlane *planes = nullptr;
+        ProjTapeItem *items = nullptr;
+        AssimPlane *xplanes = nullptr;
+        bool loops() const { return on && in_loop; }  // spd_model_step is issued in segments
+    } assim;
+    // spd_model_assim_transform, which works without an assimilation configured: the transform's plane descriptors, a member list
+    // and W [64][64] in a small allocation of their own, made at the first call.
+    struct AssimTransform {
+        void *alloc = nullptr;
+        AssimPlane *xplanes = nullptr;
+        int *member_list = nullptr;
+        double *W = nullptr;
+    } assim_xf;
     // Pressure-level fields (spd_model_plev_*): the target levels and the result arrays [M][n][4608] (mslp: [M][4608]), carved
     // from the arena the first time a variable is computed (and again only if a later configuration has more levels).
     struct Plev {

@@ -91,9 +91,8 @@ __global__ __launch_bounds__(kT) void projtape_kernel(const ProjTapePlane *__res
 
 // One launch for the members [first, first + count), all planes.  weights: [P][4608]; slab: [M][slab_fields][4608] fp64, as the
 // front end left it; store32: the model keeps precnv / precls as float; ring_slot: member 0 of the sample's slot, [M][n_entries].
-static hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const ProjTapeItem *items, const double *weights,
-                                      const double *slab, int slab_fields, double *ring_slot, int n_entries, int first, int count,
-                                      int store32, hipStream_t s) {
+hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const ProjTapeItem *items, const double *weights, const double *slab,
+                               int slab_fields, double *ring_slot, int n_entries, int first, int count, int store32, hipStream_t s) {
     if (nplanes == 0 || count == 0) return hipSuccess;
     hipLaunchKernelGGL(projtape_kernel, dim3(nplanes, count), dim3(kT), 0, s, planes, items, weights, slab, slab_fields, ring_slot,
                        n_entries, first, store32);

@@ -30,6 +30,12 @@ struct ProjTapeItem {
     int pattern, column;
 };
 
+// One launch of the projection kernel for the members [first, first + count), all planes (projtape.hip).  weights: [P][4608];
+// slab: [M][slab_fields][4608] fp64, as the front end left it; store32: the model keeps precnv / precls as float; ring_slot:
+// member 0 of the sample's slot, [M][n_entries].  The assimilation's observation operator is this launch into a one-slot ring.
+hipError_t run_projtape_sample(const ProjTapePlane *planes, int nplanes, const ProjTapeItem *items, const double *weights, const double *slab,
+                               int slab_fields, double *ring_slot, int n_entries, int first, int count, int store32, hipStream_t s);
+
 // The step loop's sample of the members [first, first + count), number n since the last reset, behind the step just issued on `s`.
 hipError_t projtape_sample(spd_model *m, int first, int count, long long n, hipStream_t s);
 

@@ -993,6 +993,134 @@ class EnsembleModel:
         with np.errstate(divide="ignore", invalid="ignore"):
             return 86400.0 * np.where(ok, g, 0.0).sum(axis=0) / np.where(n > 0, n, np.nan)
 
+    # ---- assimilation: a serial ensemble square-root filter in the device loop (spd_model_assim_*, include/pyspeedy_amd.h) ----
+    def assim_configure(self, weights, entries, members, every, capacity=64, inflation=1.0, in_loop=True):
+        """Assimilate observations: after every step that leaves current_step at a multiple of `every` AND for which
+        assim_observations() holds a row, inside run() / run_checked() calls of any length (`in_loop`) or only when assim_apply()
+        is called, the members with mask 1 are corrected by a serial ensemble square-root filter.  `weights`
+        [P][48][96] and `entries` (name, level, pattern) are the projection tape's (pyspeedy_amd.projection_weights; precnv and
+        precls are refused; at most 64 entries): each entry is one scalar observation operator.  `members`: a mask of 0 / 1 (or
+        bools) per member with 2 ... 64 ones; a member with 0 -- a nature run -- is never touched.  `inflation` >= 1 multiplies
+        the prior perturbations.  Every executed event writes the prior mean, prior variance, innovation and a used flag of each
+        entry to a ring of `capacity` events (assim()).  Land and sea temperatures are not updated.  Synchronises the device."""
+        rows = []
+        for entry in entries:
+            if len(entry) != 3:
+                raise ValueError("an entry is (name, level, pattern), got %r" % (entry,))
+            rows.append((str(entry[0]), int(entry[1]), int(entry[2])))
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 3 or w.shape[1:] != (48, 96):
+            raise ValueError("weights must be [P][48][96], got shape %r" % (w.shape,))
+        mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
+        if mask.shape != (self.nmembers,):
+            raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
+        n = max(len(rows), 1)
+        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
+        levels = (C.c_int * n)(*[r[1] for r in rows])
+        patterns = (C.c_int * n)(*[r[2] for r in rows])
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_assim_configure(self._m, w.ctypes.data_as(C.POINTER(C.c_double)), w.shape[0], names, levels, patterns,
+                                                      len(rows), mask.ctypes.data_as(C.POINTER(C.c_int32)), int(every), int(capacity),
+                                                      float(inflation), int(bool(in_loop))), "spd_model_assim_configure")
+
+    def assim_off(self):
+        """Switch assimilation off and free everything it holds."""
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_assim_off(self._m), "spd_model_assim_off")
+
+    def assim_observations(self, steps, values, variances):
+        """Replace the observation table: `steps` strictly ascending absolute step counters (or datetimes, converted with the
+        model's current date and step), `values` [T][E] (NaN: missing) and `variances` [T][E] (finite, > 0; a scalar or [E] is
+        broadcast) in the order of the configured entries.  An event runs only at a step that a row is stamped with."""
+        stamps = np.ascontiguousarray([self._nudge_step(t) for t in steps], dtype=np.int32)
+        entries = self.assim_info()["entries"]
+        yo = np.ascontiguousarray(np.asarray(values, dtype=np.float64))
+        if yo.shape != (len(stamps), entries):
+            raise ValueError("values must be [%d][%d] (rows, configured entries), got shape %r" % (len(stamps), entries, yo.shape))
+        var = np.ascontiguousarray(np.broadcast_to(np.asarray(variances, dtype=np.float64), yo.shape))
+        as_double = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        check(self._lib.spd_model_assim_set_observations(self._m, stamps.ctypes.data_as(C.POINTER(C.c_int32)), len(stamps), as_double(yo),
+                                                         as_double(var), max(entries, 1)), "spd_model_assim_set_observations")
+
+    def assim_apply(self):
+        """The analysis once, on the state as it stands, with the row stamped with current_step (refused if there is none);
+        asynchronous on the current stream; writes a ring slot."""
+        check(self._lib.spd_model_assim_apply(self._m, self._stream()), "spd_model_assim_apply")
+
+    def assim_compute(self):
+        """The observation-space ensemble of the state as it stands: a float64 tensor [E][r] on the model's device, entry e of
+        masked member a_i -- bit for bit what the projection tape records for that entry.  Writes neither the state nor the ring."""
+        info = self.assim_info()
+        out = torch.empty((info["entries"], info["members"]), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_assim_compute(self._m, C.c_void_p(out.data_ptr()), out.numel() * 8, self._stream()),
+                  "spd_model_assim_compute")
+        return out
+
+    def assim_transform(self, members, W):
+        """Mix members with a matrix of the caller's: member members[j] becomes sum_i W[i][j] X_(members[i]) on both time levels of
+        vor, div, t, tr, ps for m + n <= 31, the sum in ascending i, every operation rounded on its own (the transform of the
+        analysis; for a host-side ETKF or a resampling step).  `members`: up to 64 distinct member indices; `W`: finite
+        [r][r].  Works with or without assim_configure().  Waits for the current stream once, then launches on it."""
+        idx = np.ascontiguousarray(np.asarray(members).astype(np.int32))
+        w = np.ascontiguousarray(W, dtype=np.float64)
+        if idx.ndim != 1 or w.shape != (len(idx), len(idx)):
+            raise ValueError("W must be [r][r] for r = len(members) = %d, got shape %r" % (len(idx), w.shape))
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_assim_transform(self._m, idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx),
+                                                      w.ctypes.data_as(C.POINTER(C.c_double)), self._stream()), "spd_model_assim_transform")
+
+    def assim_info(self):
+        """dict(members, entries, every, capacity, taken, held, skipped, in_loop, applied): masked members r (all zero: off), the
+        configuration, events executed since assim_configure / assim_reset and events the ring holds, in-loop events that found
+        no row of observations, the mode, and the events executed since assim_configure."""
+        r, entries, every, capacity, in_loop = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        taken, skipped, applied = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.spd_model_assim_info(self._m, C.byref(r), C.byref(entries), C.byref(every), C.byref(capacity), C.byref(taken),
+                                             C.byref(skipped), C.byref(in_loop), C.byref(applied)), "spd_model_assim_info")
+        return dict(members=r.value, entries=entries.value, every=every.value, capacity=capacity.value, taken=int(taken.value),
+                    held=int(min(taken.value, capacity.value)), skipped=int(skipped.value), in_loop=bool(in_loop.value),
+                    applied=int(applied.value))
+
+    def assim_reset(self):
+        """Empty the ring of assimilation events and the count of skipped ones (no device work)."""
+        check(self._lib.spd_model_assim_reset(self._m), "spd_model_assim_reset")
+
+    def assim(self, t0=0, nt=None):
+        """The events [t0, t0 + nt) of the held ones, oldest first: dict(mean, variance, innovation, used) of float64 tensors
+        [nt][E] on the model's device -- the prior ensemble mean and sample variance of each entry as the serial filter met it,
+        the innovation yo - mean (0.0 for a missing observation) and 1.0 / 0.0 for an entry that was / was not used."""
+        info = self.assim_info()
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        buf = torch.empty((max(nt, 0), info["entries"], 4), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_assim_read(self._m, t0, nt, C.c_void_p(buf.data_ptr()), buf.numel() * 8, self._stream()),
+                  "spd_model_assim_read")
+        return dict(mean=buf[:, :, 0], variance=buf[:, :, 1], innovation=buf[:, :, 2], used=buf[:, :, 3])
+
+    def assim_weights(self):
+        """The last executed event's mixing matrix and observation-space prior: dict(W, Y) of float64 tensors [r][r] and [E][r]
+        on the model's device."""
+        info = self.assim_info()
+        w = torch.empty((64, 64), dtype=torch.float64, device=self.sp.device)
+        y = torch.empty((info["entries"], info["members"]), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_assim_weights(self._m, C.c_void_p(w.data_ptr()), w.numel() * 8, C.c_void_p(y.data_ptr()), y.numel() * 8,
+                                                    self._stream()), "spd_model_assim_weights")
+        return dict(W=w[:info["members"], :info["members"]].contiguous(), Y=y)
+
+    def _assim_rows(self):
+        return self._ring_rows("spd_model_assim_rows", self.assim_info()["held"], 6)
+
+    def assim_steps(self):
+        """The model's step counter at each held event, oldest first (numpy int array)."""
+        return self._row_steps(self._assim_rows())
+
+    def assim_times(self):
+        """The date of each held event's state, oldest first (a list of datetime)."""
+        return self._row_times(self._assim_rows())
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

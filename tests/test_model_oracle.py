@@ -8,7 +8,8 @@ Fortran, bit for bit:
   calendar.npz   leap February 1980, the 1982/83 year end, land_coupling_flag / sst_anomaly_coupling_flag off: the calendar after
                  EVERY step and the state after every day
 
-Every comparison is exact equality of the fp64 bit patterns."""
+Every comparison is exact equality of the fp64 bit patterns.  Developed states of three seasons (1 April, 1 July, 1 October 1982,
+restarted from the reference's own state): tests/test_seasons_oracle.py."""
 import os
 import sys
 

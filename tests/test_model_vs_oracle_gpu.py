@@ -4,7 +4,8 @@ temperature perturbation (numpy default_rng(seed = member)), its own start date 
 of them) and 12 model steps (four shortwave steps, a midnight coupling for the member started at 20:00).  The goldens pin
 unperturbed trajectories; this pins perturbed ones, at other dates and flag settings: every member against an oracle run of its own
 (observed 6.4e-14).  Tolerance 1e-11 of each field's
-max norm (12 steps, fp64; one step is held to 1e-12 in tests/test_step_gpu.py).
+max norm (12 steps, fp64; one step is held to 1e-12 in tests/test_step_gpu.py).  All of these runs start from rest; 12 steps on the
+reference's developed states of 1 April, 1 July and 1 October are held in tests/test_seasons_gpu.py.
 
 On top of that t, tr and ps are held per level, time level and total wavenumber (tests/band_norms.py) after the 12 steps to
 clip(32 nu, 1e-13, 1e-11), nu from 4 more oracle runs of the same case whose temperature is moved by one-ulp factors after `init`.

@@ -335,6 +335,12 @@ int spd_model_group_streams(spd_model_handle m, int32_t *created, int32_t *apart
  *   "physics_storage32"    0 / 1   (default 1, PYSPEEDY_AMD_PHYS_STORE32) with spd_model_set_physics_precision(m, 1): keep the arrays
  *                                  only the column physics reads back as fp32 in memory (1) or as fp64 (0: same arithmetic, same
  *                                  bits in the state, 13 % more bytes in the column kernel); converts the arrays when it changes
+ *   "tau_recompute"        0 / 1 / 2   (default 1, PYSPEEDY_AMD_TAU_RECOMPUTE) inside a multi-step call the fused column kernel hands the
+ *                                  longwave transmissivities from a shortwave step to the next two steps as the ten values per
+ *                                  column they are made of and recomputes them (same bits), and stores rad_tau2 itself on the
+ *                                  call's last shortwave step only -- 1: where 20 members and more step together (the
+ *                                  ensemble, or a round of it), from where the kernel waits on memory; 2: whatever the size; 0: every
+ *                                  shortwave step stores rad_tau2, every other step loads it
  *   "prepare_multi_step"   1       create the streams of the member groups now instead of at the first multi-step call (write-only)
  *   "fail_launch_after"    n, -1   fault injection for tests: the (n + 1)-th launch sequence of a member group from now on fails like a
  *                                  device error (-1: off); spd_model_init clears it (write-only)

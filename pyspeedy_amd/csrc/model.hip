@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -32,7 +33,8 @@ hipError_t run_spec2grid_table(const DeviceTables &T, const FieldDesc *table, in
 hipError_t run_grid2spec_table(const DeviceTables &T, const FieldDesc *table, int nfields, hipStream_t st);
 hipError_t run_physics(const DeviceTables &T, const spd_physics_args &a, int nmembers, int fp32, hipStream_t s);
 hipError_t run_dyn_physics(const ModelPtrs &P, const DynDeviceTables &D, const DeviceTables &T, const spd_physics_args &a,
-                           int first, int nmembers, int fp32, int store32, int diag, hipStream_t s);
+                           int first, int nmembers, int fp32, int store32, int diag, double *tau_rec, int tau_store_record,
+                           int tau_store_array, hipStream_t s);
 hipError_t run_geopotential(const ModelPtrs &P, const DynDeviceTables &D, int first, int count, int tl, const SpptArgs *sppt,
                             int *rim, hipStream_t s);
 hipError_t run_dyn_grid(const ModelPtrs &P, const DynDeviceTables &D, int M, hipStream_t s);
@@ -535,6 +537,7 @@ int spd_model_create(spd_handle h, int nmembers, spd_model_handle *out) {
     m->inv_per_member = 77;
     if (const char *env = getenv("PYSPEEDY_AMD_PRUNE_DEAD")) m->inv_per_member = atoi(env) != 0 ? 77 : 91;
     if (const char *env = getenv("PYSPEEDY_AMD_DIAG_EVERY_STEP")) m->diag_every_step = atoi(env) != 0;
+    if (const char *env = getenv("PYSPEEDY_AMD_TAU_RECOMPUTE")) m->tau_recompute = atoi(env) < 0 || atoi(env) > 2 ? 1 : atoi(env);
     m->fold_geo = nmembers <= 8;
     if (const char *env = getenv("PYSPEEDY_AMD_SPECTRAL_EARLY")) m->spectral_early = atoi(env);
     if (const char *env = getenv("PYSPEEDY_AMD_FOLD_GEO")) m->fold_geo = atoi(env) != 0;
@@ -602,6 +605,7 @@ int spd_model_create(spd_handle h, int nmembers, spd_model_handle *out) {
     PA_IN(tt_rsw, M * G3, "tt_rsw", G3);
     PA_IN(rad_tau2, M * 4 * G3, "rad_tau2", 4 * G3);
     PA_IN(rad_strat_corr, M * 2 * NG, "rad_strat_corr", 2 * NG);
+    A(m->tau_rec, M * 10 * NG, nullptr, 0);  // (the compact record of the column kernel: physics.hip, kTauRecPlanes)
     // surface / coupler arrays under their registry names (model_state_def.py:250-410)
     SurfacePtrs &SF = m->S;
     const size_t G12 = static_cast<size_t>(12) * NG;
@@ -922,9 +926,15 @@ static bool staged_products(const spd_model *m) { return !(m->split_dyn_physics 
 
 // cpl != nullptr: the coupling that follows the step is part of the last launch
 // ride != nullptr: the range check of the PREVIOUS step of these members rides in this step's spectral -> grid launch
+// tau: how the column kernel keeps the longwave transmissivities (step_segment); the default is the array form
+constexpr int kTauFromMembers = 20;  // members of a round from which the compact form is used (step_segment)
+struct TauPlan {
+    bool compact = false;                             // the launch uses the compact record instead of rad_tau2
+    bool store_record = false, store_array = false;  // (compact shortwave steps) what the step leaves behind
+};
 static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int compute_shortwave, int first, int count, int diag,
                              bool run_geo, const CouplerArgs *cpl, hipStream_t s, hipEvent_t after_grid2spec = nullptr,
-                             const CheckArgs *ride = nullptr, int rim_mode = kRimPlain) {
+                             const CheckArgs *ride = nullptr, int rim_mode = kRimPlain, const TauPlan &tau = TauPlan{}) {
     const DeviceTables &T = m->ctx->dev;
     const int M = m->M;
     hipError_t e = hipSuccess;
@@ -982,7 +992,8 @@ static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int comput
             }
         } else {
             ProfScope ps(m, compute_shortwave ? SPD_K_COLUMN_SW : SPD_K_COLUMN, count, s);
-            e = run_dyn_physics(m->P, m->D, T, pa, first, count, m->phys_fp32, m->stored32 ? 1 : 0, diag, s);  // both in one launch
+            e = run_dyn_physics(m->P, m->D, T, pa, first, count, m->phys_fp32, m->stored32 ? 1 : 0, diag, tau.compact ? m->tau_rec : nullptr,
+                                tau.store_record ? 1 : 0, tau.store_array ? 1 : 0, s);  // both in one launch
         }
     }
     if (e == hipSuccess) {                                                                // :238-268
@@ -1467,15 +1478,34 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
     };
     const HostState start{m->cal, m->current_step, m->phi_cur, m->surf_cache_valid, m->phi_ahead, m->sppt_first, m->sppt_step,
                           m->air_absortivity_co2};
-    if (rounds > 1 && m->sst_anomaly_flag) {  // (what can refuse a step is asked for ALL steps before the first round goes out)
+    // The longwave transmissivities of the steps between two shortwave steps (every third step computes them; the reference keeps
+    // them in rad_tau2): inside a segment of two steps or more the fused column kernel hands them on as the compact record they
+    // are made of and recomputes (physics.hip, COMPACT; option tau_recompute).  The schedule is the segment's own -- every round
+    // and member group follows it, and nothing is carried from call to call: a host may have written rad_tau2 in between,
+    // through device views as well.
+    //   a step without shortwave uses the record when a shortwave step of this segment came before it, rad_tau2 otherwise;
+    //   a shortwave step stores the record unless it is the segment's last step (nobody would read it), and
+    //   stores rad_tau2 when no later shortwave step of the segment will overwrite it (or diag_every_step says so):
+    // at the end of every segment rad_tau2 is what the array form leaves, and only there can anybody look at it -- snapshots,
+    // container copies, get(), the physics replay; no recorder can name it (kStatsCatalogue, kAccNames).
+    // A round takes part from kTauFromMembers members up -- the size from which the default plan steps the members in groups whose
+    // launches overlap and the column kernel waits on memory.  Below that it runs at the issue rate of one wavefront per SIMD and
+    // the exponentials cost more than the bytes save: measured +1.9 % per step at one member, +1 % at 8, +1.5 % at 16, against
+    // -0.5 ... -3 % from 20 up (profiles/tau_recompute_ab.txt).  Option value 2: rounds of any size.
+    bool tau_compact = m->tau_recompute != 0 && nsteps > 1 && staged_products(m);
+    if ((rounds > 1 || tau_compact) && m->sst_anomaly_flag) {  // (what can refuse a step is asked for ALL steps before the first round goes out)
         Calendar ahead = m->cal;
         for (int it = 0; it < nsteps; ++it) {
             ahead.advance();
             const TimeInterp w = time_interp(ahead);
-            if (w.a0 < 0 || w.a1 < 0 || w.a0 >= m->anom_planes || w.a1 >= m->anom_planes)
-                return m_fail(SPD_E_ARG, "SST anomaly planes do not cover the simulated period (speedy.py:338-372)");
+            if (w.a0 < 0 || w.a1 < 0 || w.a0 >= m->anom_planes || w.a1 >= m->anom_planes) {
+                if (rounds > 1) return m_fail(SPD_E_ARG, "SST anomaly planes do not cover the simulated period (speedy.py:338-372)");
+                tau_compact = false;  // the segment will be refused half-way without poisoning the model: its steps leave rad_tau2
+            }
         }
     }
+    const int tau_first_sw = ((3 - start.current_step % 3) % 3 + 3) % 3;  // the segment's first shortwave step (0-based)
+    double tau_co2 = 0.0;                                                  // the CO2 absorptivity the record was made with
     int rc = SPD_OK;
     auto note_accepted = [&](int row) {  // (record: what the host side of the model looks like after `row` steps of the call)
         if (!record) return;
@@ -1535,6 +1565,7 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
             m->air_absortivity_co2 = start.co2;
         }
         const int base = round_count / G, extra = round_count % G;
+        const bool tau_round = tau_compact && (m->tau_recompute == 2 || round_count >= kTauFromMembers);
         for (int it = 0; it < nsteps && rc == SPD_OK; ++it) {
             const bool new_day = m->current_step % 36 == 0;
             ZonalDevice zd{};
@@ -1583,6 +1614,16 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
                 rc = m_fail(SPD_E_ARG, "SST anomaly planes do not cover the simulated period (speedy.py:338-372)");
                 break;
             }
+            TauPlan tau;
+            if (tau_round && sw && it != nsteps - 1) {
+                tau.compact = tau.store_record = true;
+                tau.store_array = it + 3 > nsteps - 1 || m->diag_every_step;
+                tau_co2 = m->air_absortivity_co2;
+            } else if (tau_round && !sw && it > tau_first_sw) {
+                tau.compact = true;
+                // (forcing_host changes the absorptivity on the first step of a day only, and that is a shortwave step)
+                assert(m->air_absortivity_co2 == tau_co2);
+            }
             const bool run_geo = begin_step_geopotential(m);
             const bool first_of_call = it == 0 && round == 0;
             for (int g = 0, first = round_first; g < G && rc == SPD_OK; ++g) {
@@ -1606,7 +1647,7 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
                     if (e == hipSuccess)
                         e = step_range(m, 2, 2, 2 * delt, sw, first, count, diag, run_geo, &cpl, gs[g],
                                        (offset && first_of_call && g == 0) ? m->ev_offset : nullptr, record && it > 0 ? &chk : nullptr,
-                                       rim ? (it == 0 ? kRimDetect : kRimSkip) : kRimPlain);
+                                       rim ? (it == 0 ? kRimDetect : kRimSkip) : kRimPlain, tau);
                     check_launch(e, "");
                 }
                 if (rc == SPD_OK && nudge) {  // directly behind the step, on the group's stream: every check and sample sees the nudged state
@@ -2001,6 +2042,7 @@ int spd_model_get_option(spd_model_handle m, const char *name, int32_t *value) {
     else if (key == "member_groups") *value = m->nchunks;
     else if (key == "block_members") *value = m->block_members;
     else if (key == "physics_storage32") *value = m->phys_store32 ? 1 : 0;
+    else if (key == "tau_recompute") *value = m->tau_recompute;
     else if (key == "staged_products") *value = staged_products(m) ? 1 : 0;  // (read-only: which forward table the step uses)
     else if (key == "quiet_rim_members") {
         // members whose rim the last multi-step call found quiet (step_impl); -1 when the last call did not look (one step, or
@@ -2024,6 +2066,7 @@ int spd_model_set_option(spd_model_handle m, const char *name, int32_t value) {
     const bool flag = value == 0 || value == 1;
     if (key == "diag_every_step" && flag) m->diag_every_step = value != 0;
     else if (key == "split_dyn" && flag) m->split_dyn_physics = value != 0;
+    else if (key == "tau_recompute" && value >= 0 && value <= 2) m->tau_recompute = value;
     else if (key == "spectral_early" && value >= -1 && value <= 1) m->spectral_early = value;
     else if (key == "member_groups" && value >= 1 && value <= 4) m->nchunks = value < m->M ? value : m->M;
     else if (key == "block_members" && value >= 0) m->block_members = value;

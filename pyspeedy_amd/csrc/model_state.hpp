@@ -155,6 +155,14 @@ struct spd_model {
     // of a spd_model_step call stores the physics outputs that no later kernel reads -- the host can only look at the
     // state between calls, and every earlier value would be overwritten before that.
     bool diag_every_step = false;
+    // The longwave transmissivities between shortwave steps of a multi-step call (option "tau_recompute", PYSPEEDY_AMD_TAU_RECOMPUTE;
+    // DESIGN section 4): a shortwave step leaves the ten values per column they are made of in `tau_rec` ([M][10][4608], stored
+    // like rad_tau2; scratch that means something only inside a call, not a registry variable) and the next two steps recompute
+    // them; rad_tau2 itself is stored by the last shortwave step of a call only.  0: every shortwave step stores rad_tau2 and
+    // every other step loads it, as the one-step calls and the separate physics launch always do.  1: where 20 members and more
+    // step together (the whole ensemble, or a round of a large one).  2: whatever the size.
+    int tau_recompute = 1;
+    double *tau_rec = nullptr;
     // The coupler's climatology interpolation is valid for a day (surface.hip): true after a coupling, false after anything
     // wrote to the state from outside the step
     bool surf_cache_valid = false;

@@ -115,6 +115,46 @@ ColTables<R> col_tables(const DeviceTables &T) {
     return c;
 }
 
+// Planes of the compact record a shortwave step leaves for the next two steps of the same multi-step call (COMPACT kernels):
+// what the longwave transmissivities are made of, per column.
+constexpr int kTauRecPlanes = 10;  // psa, cloudc, icltop, qa(2:kx)
+
+// longwave transmissivities, shortwave_radiation.f90:170-208: rad_tau2(k, band) from the surface pressure, the clamped humidity
+// of levels 2 ... kx and the cloud state of a SHORTWAVE step (the reference keeps them until the next one) and the CO2
+// absorptivity.  emit(k, band, value), 0-based.  The one expression tree of every kernel form: a shortwave step evaluates it on
+// its live values, a COMPACT step between two shortwave steps on the record -- the same device exp on the same bits, so the same
+// bits (-ffp-contract=on: nothing here is fused across statements).  Bands 3-4 of the top level are the constant 1.
+template <typename R, typename Emit>
+__device__ __forceinline__ void lw_transmissivities(R psa, const R (&qa)[KX], R cloudc, int icltop, R co2, Emit emit) {
+    const R ablwin = 0.3f, ablwv1 = 0.7f, ablwv2 = 50.0f, ablcl1 = 12.0f, ablcl2 = 0.6f;
+    emit(0, 0, rexp(-psa * vert<R>(vc::dhs, 0) * ablwin));
+    emit(0, 1, rexp(-psa * vert<R>(vc::dhs, 0) * co2));
+    emit(0, 2, R(1.0f));
+    emit(0, 3, R(1.0f));
+    const R acloud = cloudc * ablcl2;
+#pragma unroll
+    for (int k = 2; k <= KX; ++k) {
+        R t0, t1, t2, t3;
+        if (k == 2 || k == KX) {
+            t0 = rexp(-psa * vert<R>(vc::dhs, k - 1) * ablwin);
+            t1 = rexp(-psa * vert<R>(vc::dhs, k - 1) * co2);
+            t2 = rexp(-psa * vert<R>(vc::dhs, k - 1) * ablwv1 * qa[k - 1]);
+            t3 = rexp(-psa * vert<R>(vc::dhs, k - 1) * ablwv2 * qa[k - 1]);
+        } else {
+            const R deltap = psa * vert<R>(vc::dhs, k - 1);
+            const R acloud1 = (k < icltop) ? acloud : ablcl1 * cloudc;
+            t0 = rexp(-deltap * (ablwin + acloud1));
+            t1 = rexp(-deltap * co2);
+            t2 = rexp(-deltap * rmax<R>(ablwv1 * qa[k - 1], acloud));
+            t3 = rexp(-deltap * rmax<R>(ablwv2 * qa[k - 1], acloud));
+        }
+        emit(k - 1, 0, t0);
+        emit(k - 1, 1, t1);
+        emit(k - 1, 2, t2);
+        emit(k - 1, 3, t3);
+    }
+}
+
 }  // namespace
 
 // W = minimum waves per SIMD the register allocator must leave room for (launch-bounds hint): 2 for fp64 (256 VGPRs, no
@@ -128,10 +168,21 @@ ColTables<R> col_tables(const DeviceTables &T) {
 // KEEP (FUSED only): the dynamics' temperature tendencies stay in LDS until the end of the kernel -- needed when the result is
 // not simply "dynamics + physics summed in R": mixed precision (R = float) and SPPT both combine the fp64 dynamics
 // tendency with the physics increment at the end.
-template <int W, bool FUSED, bool KEEP, typename R, bool S32 = false>
+// COMPACT (FUSED only; steps of a multi-step call, model option tau_recompute): between shortwave steps the longwave
+// transmissivities travel as the kTauRecPlanes values per column they are made of (tau_rec, [member][plane][column], stored like
+// rad_tau2) instead of as the 32 of rad_tau2.  A shortwave step stores the record when dflags says so (kTauStoreRecord) and
+// rad_tau2 itself only under kTauStoreArray -- where somebody outside the kernel can look at it, the rule of the
+// diagnostics-only outputs --; a step without shortwave loads the record and recomputes (lw_transmissivities).  A template
+// parameter, not a run-time switch: the fp64 kernel sits at the register limit.  Not COMPACT: rad_tau2 is stored by every
+// shortwave step and loaded by every other one.
+// dflags: kDiagStore (the diagnostics-only outputs are stored) | kTauStoreRecord | kTauStoreArray.
+constexpr int kDiagStore = 1, kTauStoreRecord = 2, kTauStoreArray = 4;
+template <int W, bool FUSED, bool KEEP, typename R, bool S32 = false, bool COMPACT = false>
 __global__ __launch_bounds__(kPhysThreads, W) void physics_kernel(spd_physics_args a, ColTables<R> CT, int first, int nmembers,
-                                                                  ModelPtrs MP, DynDeviceTables MD, int diag) {
+                                                                  ModelPtrs MP, DynDeviceTables MD, int dflags, double *tau_rec) {
     using C = PhysConst<R>;
+    static_assert(!COMPACT || FUSED, "the compact record belongs to the steps of a multi-step call");
+    const int diag = dflags & kDiagStore;
     constexpr bool MIXED = !std::is_same<R, double>::value;
     // S32 (the model's cfg 5 step: fp32 arithmetic, fused; model option physics_storage32, default on): what only this kernel ever reads back -- its grid-point inputs at the
     // physics' time level (written by the spectral -> grid launch), the radiation state a shortwave step leaves for the next
@@ -484,8 +535,7 @@ __global__ __launch_bounds__(kPhysThreads, W) void physics_kernel(spd_physics_ar
     if (a.compute_shortwave) {
         const R rhcl1 = 0.30f, rhcl2 = 1.00f, qacl = 0.20f, wpcl = 0.2f, pmaxcl = 10.0f, clsmax = 0.60f,
                      clsminl = 0.15f, gse_s0 = 0.25f, gse_s1 = 0.40f, albcl = 0.43f, albcls = 0.50f, absdry = 0.033f,
-                     absaer = 0.033f, abswv1 = 0.022f, abswv2 = 15.000f, abscl1 = 0.015f, abscl2 = 0.15f,
-                     ablwin = 0.3f, ablwv1 = 0.7f, ablwv2 = 50.0f, ablcl1 = 12.0f, ablcl2 = 0.6f;
+                     absaer = 0.033f, abswv1 = 0.022f, abswv2 = 15.000f, abscl1 = 0.015f, abscl2 = 0.15f;
         const R fmask = R(a.fmask_land[o2]);
         // (the other inputs of the block, requested in the same batch)
         const R zenit = R(a.zenit_correction[o2]), solar = R(a.flux_solar_in[o2]), ozupp = R(a.flux_ozone_upper[o2]);
@@ -589,40 +639,33 @@ __global__ __launch_bounds__(kPhysThreads, W) void physics_kernel(spd_physics_ar
             ttend[k] = ttend[k] + tt_rsw[k];
         }
 
-        // longwave transmissivities, shortwave_radiation.f90:170-208
+        // longwave transmissivities (lw_transmissivities): into LDS for this step's sweeps, and for the next two steps
         const R co2 = a.air_absortivity_co2;
         const size_t NGs = static_cast<size_t>(NG);
-        tau_s[0][lane] = rexp(-psa * vert<R>(vc::dhs, 0) * ablwin);
-        tau_s[KX][lane] = rexp(-psa * vert<R>(vc::dhs, 0) * co2);
-        st_stream(a.rad_tau2, ot + NGs * (0 + KX * 0), tau_s[0][lane]);
-        st_stream(a.rad_tau2, ot + NGs * (0 + KX * 1), tau_s[KX][lane]);
-        st_stream(a.rad_tau2, ot + NGs * (0 + KX * 2), R(1.0f));
-        st_stream(a.rad_tau2, ot + NGs * (0 + KX * 3), R(1.0f));
-        acloud = cloudc * ablcl2;
+        if constexpr (COMPACT) {
+            if (dflags & kTauStoreRecord) {
+                const size_t orec = static_cast<size_t>(mem) * kTauRecPlanes * NG + p;
+                st_stream(tau_rec, orec, psa);
+                st_stream(tau_rec, orec + NGs, cloudc);
+                st_stream(tau_rec, orec + NGs * 2, static_cast<R>(icltop));
 #pragma unroll
-        for (int k = 2; k <= KX; ++k) {
-            R t0, t1, t2, t3;
-            if (k == 2 || k == KX) {
-                t0 = rexp(-psa * vert<R>(vc::dhs, k - 1) * ablwin);
-                t1 = rexp(-psa * vert<R>(vc::dhs, k - 1) * co2);
-                t2 = rexp(-psa * vert<R>(vc::dhs, k - 1) * ablwv1 * qa[k - 1]);
-                t3 = rexp(-psa * vert<R>(vc::dhs, k - 1) * ablwv2 * qa[k - 1]);
-            } else {
-                const R deltap = psa * vert<R>(vc::dhs, k - 1);
-                const R acloud1 = (k < icltop) ? acloud : ablcl1 * cloudc;
-                t0 = rexp(-deltap * (ablwin + acloud1));
-                t1 = rexp(-deltap * co2);
-                t2 = rexp(-deltap * rmax<R>(ablwv1 * qa[k - 1], acloud));
-                t3 = rexp(-deltap * rmax<R>(ablwv2 * qa[k - 1], acloud));
+                for (int k = 1; k < KX; ++k) st_stream(tau_rec, orec + NGs * (2 + k), qa[k]);
             }
-            st_stream(a.rad_tau2, ot + NGs * (k - 1 + KX * 0), t0);
-            st_stream(a.rad_tau2, ot + NGs * (k - 1 + KX * 1), t1);
-            st_stream(a.rad_tau2, ot + NGs * (k - 1 + KX * 2), t2);
-            st_stream(a.rad_tau2, ot + NGs * (k - 1 + KX * 3), t3);
-            tau_s[k - 1 + KX * 0][lane] = t0;
-            tau_s[k - 1 + KX * 1][lane] = t1;
-            tau_s[k - 1 + KX * 2][lane] = t2;
-            tau_s[k - 1 + KX * 3][lane] = t3;
+            lw_transmissivities<R>(psa, qa, cloudc, icltop, co2, [&](int k, int b, R v) {
+                if (k > 0 || b < 2) tau_s[k + KX * b][lane] = v;
+            });
+            if (dflags & kTauStoreArray) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+#pragma unroll
+                    for (int k = 0; k < KX; ++k)
+                        st_stream(a.rad_tau2, ot + NGs * (k + KX * b), (k > 0 || b < 2) ? tau_s[k + KX * b][lane] : R(1.0f));
+            }
+        } else {
+            lw_transmissivities<R>(psa, qa, cloudc, icltop, co2, [&](int k, int b, R v) {
+                st_stream(a.rad_tau2, ot + NGs * (k + KX * b), v);
+                if (k > 0 || b < 2) tau_s[k + KX * b][lane] = v;
+            });
         }
         const R eps1 = C::EPSLW / (vert<R>(vc::dhs, 0) + vert<R>(vc::dhs, 1));
         strat1 = R(a.stratospheric_correction[o2]) * psa;  // (requested here: one more live value above costs the kernel scratch)
@@ -632,11 +675,25 @@ __global__ __launch_bounds__(kPhysThreads, W) void physics_kernel(spd_physics_ar
     } else {
 #pragma unroll
         for (int k = 0; k < KX; ++k) ttend[k] = ttend[k] + R(ld_plain(a.tt_rsw, o3 + NG * k));
+        if constexpr (COMPACT) {  // the record of the shortwave step before this one, and from it that step's transmissivities
+            const size_t orec = static_cast<size_t>(mem) * kTauRecPlanes * NG + p, NGs = static_cast<size_t>(NG);
+            R q_sw[KX];
+            q_sw[0] = R(0.0f);  // (level 1 has no part in them)
+            const R psa_sw = R(ld_plain(tau_rec, orec)), cloudc_sw = R(ld_plain(tau_rec, orec + NGs));
+            const int icltop_sw = static_cast<int>(R(ld_plain(tau_rec, orec + NGs * 2)));
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
+            for (int k = 1; k < KX; ++k) q_sw[k] = R(ld_plain(tau_rec, orec + NGs * (2 + k)));
+            const R co2 = a.air_absortivity_co2;
+            lw_transmissivities<R>(psa_sw, q_sw, cloudc_sw, icltop_sw, co2, [&](int k, int b, R v) {
+                if (k > 0 || b < 2) tau_s[k + KX * b][lane] = v;
+            });
+        } else {
 #pragma unroll
-            for (int k = (b < 2 ? 0 : 1); k < KX; ++k)  // bands 3-4 do not use the top level
-                tau_s[k + KX * b][lane] = R(ld_plain(a.rad_tau2, ot + static_cast<size_t>(NG) * (k + KX * b)));
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int k = (b < 2 ? 0 : 1); k < KX; ++k)  // bands 3-4 do not use the top level
+                    tau_s[k + KX * b][lane] = R(ld_plain(a.rad_tau2, ot + static_cast<size_t>(NG) * (k + KX * b)));
+        }
         ssrd = R(a.ssrd[o2]);
         strat1 = R(ld_plain(a.rad_strat_corr, oc));
         strat2 = R(ld_plain(a.rad_strat_corr, oc + NG));
@@ -883,13 +940,13 @@ static int physics_waves32(int nmembers) {
     return nmembers * (NG / 64) <= 2 * 1024 ? 2 : 3;  // wavefronts of the launch against two per SIMD of the GPU
 }
 
-template <int W, bool FUSED, bool KEEP, typename R, bool S32 = false>
+template <int W, bool FUSED, bool KEEP, typename R, bool S32 = false, bool COMPACT = false>
 static hipError_t launch_physics(const DeviceTables &T, const spd_physics_args &a, int first, int nmembers, const ModelPtrs &P,
-                                 const DynDeviceTables &D, int diag, hipStream_t s) {
+                                 const DynDeviceTables &D, int dflags, double *tau_rec, hipStream_t s) {
     const long total = static_cast<long>(nmembers) * NG;
     const unsigned blocks = static_cast<unsigned>((total + kPhysThreads - 1) / kPhysThreads);
-    launch(physics_kernel<W, FUSED, KEEP, R, S32>, dim3(blocks), dim3(kPhysThreads), 0, s, a, col_tables<R>(T), first,
-                       nmembers, P, D, diag);
+    launch(physics_kernel<W, FUSED, KEEP, R, S32, COMPACT>, dim3(blocks), dim3(kPhysThreads), 0, s, a, col_tables<R>(T), first,
+                       nmembers, P, D, dflags, tau_rec);
     return hipGetLastError();
 }
 
@@ -899,11 +956,19 @@ hipError_t run_physics(const DeviceTables &T, const spd_physics_args &a, int nme
     const DynDeviceTables md{};
     if (fp32) {
         switch (physics_waves32(nmembers)) {
-            case 2: return launch_physics<2, false, false, float>(T, a, 0, nmembers, mp, md, 1, s);
-            default: return launch_physics<3, false, false, float>(T, a, 0, nmembers, mp, md, 1, s);
+            case 2: return launch_physics<2, false, false, float>(T, a, 0, nmembers, mp, md, kDiagStore, nullptr, s);
+            default: return launch_physics<3, false, false, float>(T, a, 0, nmembers, mp, md, kDiagStore, nullptr, s);
         }
     }
-    return launch_physics<2, false, false, double>(T, a, 0, nmembers, mp, md, 1, s);
+    return launch_physics<2, false, false, double>(T, a, 0, nmembers, mp, md, kDiagStore, nullptr, s);
+}
+
+// the fused kernel in its array or its compact form (tau_rec != nullptr)
+template <int W, bool KEEP, typename R, bool S32 = false>
+static hipError_t launch_fused(const DeviceTables &T, const spd_physics_args &a, int first, int nmembers, const ModelPtrs &P,
+                               const DynDeviceTables &D, int dflags, double *tau_rec, hipStream_t s) {
+    if (tau_rec) return launch_physics<W, true, KEEP, R, S32, true>(T, a, first, nmembers, P, D, dflags, tau_rec, s);
+    return launch_physics<W, true, KEEP, R, S32, false>(T, a, first, nmembers, P, D, dflags, nullptr, s);
 }
 
 // grid-point dynamics + physics of every column in one launch (the model step); a.ttend / a.qtend / a.utend / a.vtend must be
@@ -913,22 +978,28 @@ hipError_t run_physics(const DeviceTables &T, const spd_physics_args &a, int nme
 // band / level decompositions, wind stress, the land / average parts of the surface fluxes: 39 doubles per column -- are
 // computed as always but NOT stored (what a shortwave step leaves for the following steps is always stored).  The model passes 0 for every step of a multi-step call except
 // the last one: such a value would be overwritten by the next step before anything could read it (model.hip).
+//
+// tau_rec == nullptr: the array form (rad_tau2 stored by a shortwave step, loaded by the others).  Otherwise the compact form
+// over that record (physics_kernel, COMPACT): a shortwave step stores the record / rad_tau2 as tau_store_record / tau_store_array
+// say, a step without shortwave recomputes from the record.
 hipError_t run_dyn_physics(const ModelPtrs &P, const DynDeviceTables &D, const DeviceTables &T, const spd_physics_args &a,
-                           int first, int nmembers, int fp32, int store32, int diag, hipStream_t s) {
+                           int first, int nmembers, int fp32, int store32, int diag, double *tau_rec, int tau_store_record,
+                           int tau_store_array, hipStream_t s) {
+    const int dflags = (diag ? kDiagStore : 0) | (tau_store_record ? kTauStoreRecord : 0) | (tau_store_array ? kTauStoreArray : 0);
     if (fp32 && store32) {  // cfg 5: fp32 arithmetic, physics-only arrays stored as fp32
         switch (physics_waves32(nmembers)) {
-            case 2: return launch_physics<2, true, true, float, true>(T, a, first, nmembers, P, D, diag, s);
-            default: return launch_physics<3, true, true, float, true>(T, a, first, nmembers, P, D, diag, s);
+            case 2: return launch_fused<2, true, float, true>(T, a, first, nmembers, P, D, dflags, tau_rec, s);
+            default: return launch_fused<3, true, float, true>(T, a, first, nmembers, P, D, dflags, tau_rec, s);
         }
     }
     if (fp32) {  // (model option physics_storage32 = 0: the same arithmetic over fp64 storage, for comparison)
         switch (physics_waves32(nmembers)) {
-            case 2: return launch_physics<2, true, true, float>(T, a, first, nmembers, P, D, diag, s);
-            default: return launch_physics<3, true, true, float>(T, a, first, nmembers, P, D, diag, s);
+            case 2: return launch_fused<2, true, float>(T, a, first, nmembers, P, D, dflags, tau_rec, s);
+            default: return launch_fused<3, true, float>(T, a, first, nmembers, P, D, dflags, tau_rec, s);
         }
     }
-    if (a.sppt_pattern) return launch_physics<2, true, true, double>(T, a, first, nmembers, P, D, diag, s);
-    return launch_physics<2, true, false, double>(T, a, first, nmembers, P, D, diag, s);
+    if (a.sppt_pattern) return launch_fused<2, true, double>(T, a, first, nmembers, P, D, dflags, tau_rec, s);
+    return launch_fused<2, false, double>(T, a, first, nmembers, P, D, dflags, tau_rec, s);
 }
 
 }  // namespace spd

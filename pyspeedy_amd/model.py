@@ -266,7 +266,9 @@ class EnsembleModel:
         """How the step is configured: dict(inv_per_member, diag_every_step, chunks, split_dyn, ...) -- spd_model_get_config.
         The land / sea-ice coupling always rides in spectral_step_kernel: its key is always True.  forward_table: "products" when
         the step's grid -> spectral launch forms the flux and kinetic-energy products itself (the fused column kernel, which does
-        not store them), "plain" when it reads them from memory (split_dyn: the stand-alone dynamics kernel stores them)."""
+        not store them), "plain" when it reads them from memory (split_dyn: the stand-alone dynamics kernel stores them).
+        tau_recompute: 0 / 1 / 2, whether multi-step calls recompute the longwave transmissivities between shortwave steps
+        instead of re-loading rad_tau2 -- never / from 20 members up / whatever the size."""
         cfg = (C.c_int32 * 8)()
         check(self._lib.spd_model_get_config(self._m, cfg), "spd_model_get_config")
         created, apart = C.c_int32(0), C.c_int32(1)
@@ -278,6 +280,11 @@ class EnsembleModel:
         rc = self._lib.spd_model_get_option(self._m, b"staged_products", C.byref(staged))
         if rc != _lib.SPD_E_ARG:
             check(rc, "spd_model_get_option")
+        # (... nor, from before the compact record of the longwave transmissivities, this one: every step uses rad_tau2)
+        tau = C.c_int32(0)
+        rc = self._lib.spd_model_get_option(self._m, b"tau_recompute", C.byref(tau))
+        if rc != _lib.SPD_E_ARG:
+            check(rc, "spd_model_get_option")
         streams, M = cfg[2], self.nmembers
         # (as spd_model_step forms them: rounds of `chunks` x `block_members` members from 4 x block_members members up; not while
         # profiling or with separate dynamics / physics launches, which step everybody as one group)
@@ -287,11 +294,12 @@ class EnsembleModel:
         return dict(inv_per_member=cfg[0], diag_every_step=bool(cfg[1]), chunks=cfg[2], split_dyn=bool(cfg[3]),
                     fold_geo=bool(cfg[4]), coupler_in_spectral=bool(cfg[5]), physics_fp32=bool(cfg[6]),
                     physics_storage32=bool(cfg[7]), group_streams=created.value, group_streams_apart=bool(apart.value),
-                    block_members=block.value, rounds=rounds, forward_table="products" if staged.value else "plain")
+                    block_members=block.value, rounds=rounds, forward_table="products" if staged.value else "plain",
+                    tau_recompute=tau.value)
 
     def set_option(self, name, value):
         """A launch-plan switch of the live model by name (spd_model_set_option: diag_every_step, spectral_early, split_dyn,
-        member_groups, block_members, physics_storage32); none of them changes the state a step leaves behind.
+        member_groups, block_members, physics_storage32, tau_recompute); none of them changes the state a step leaves behind.
         ValueError for an unknown name."""
         rc = self._lib.spd_model_set_option(self._m, name.encode(), int(value))
         if rc == _lib.SPD_E_ARG:

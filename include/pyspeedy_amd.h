@@ -448,6 +448,41 @@ int spd_model_plev_compute(spd_model_handle m, const char *const *names, int n_n
                            void *stream);
 int spd_model_plev_read(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes,
                         void *stream);
+/* Derived fields, computed on the device from the sigma-level grid fields in export units, vorticity, divergence and grad ln ps.
+ * Fourteen names, which the statistics, the tapes, the projection tape and spd_model_assim_configure take next to their own
+ * (a sample then also transforms what a name needs, and the derived-field kernel runs on the group's stream behind the
+ * pressure-level kernel).  With dhs[k], fsg[k] the model's layer thicknesses and full levels (k = 0 top ... 7), g and kappa the
+ * library's, p0 = 1e5 Pa, q in kg/kg and ps in Pa, every sum over k sequential from k = 0:
+ *   vor_grid, div_grid [8]  1/s       the state's vorticity and divergence through the export transform (no kernel)
+ *   omega_grid [8]          Pa/s      the model's own discrete continuity equation on the exported time level: with px, py the
+ *                                     components of grad ln ps as the step transforms them, D = div_grid,
+ *                                       ubar = sum u[k] dhs[k], vbar, Dbar likewise; puv[k] = (u[k] - ubar) px + (v[k] - vbar) py
+ *                                       sd[0] = 0, sd[k+1] = sd[k] - dhs[k] (puv[k] + D[k] - Dbar)    (sd[8] is not forced to 0)
+ *                                       dlnps = -ubar px - vbar py - Dbar
+ *                                       omega[k] = ps (fsg[k] (dlnps + u[k] px + v[k] py) + (sd[k] + sd[k+1]) / 2)
+ *   rh_grid [8]             1         (1000 q) / qsat(T, fsg[k] ps / p0), the model's saturation formula (g/kg); not clipped
+ *   theta_grid [8]          K         T (p0 / (fsg[k] ps))^kappa
+ *   tcwv                    kg/m^2    (ps / g) sum q[k] dhs[k]
+ *   ivt_u, ivt_v            kg/(m s)  (ps / g) sum q[k] u[k] dhs[k], and with v
+ *   ke_col                  J/m^2     (ps / g) sum (u[k]^2 + v[k]^2) / 2 dhs[k]
+ *   omega_plev, vor_plev, div_plev, rh_plev, theta_plev [n]   the sigma-level field at the target levels of
+ *                                     spd_model_plev_configure: linear in ln p inside the full levels with the layer search and
+ *                                     weight of the pressure-level fields above; the value of level 0 above the top full level
+ *                                     and of level 7 below the lowest (no extrapolation); points under the ground are NOT masked.
+ * They are derived fields, not state: spd_model_get / _set, restarts and spd_model_copy_member do not know them.
+ *   _compute    members [first, first + count).  SPD_E_ARG, in this order: an unknown name, a name twice, a null model or a bad
+ *               member range, a pressure-level name without configured levels.  With refresh = 1 first spd_model_spectral2grid
+ *               of those members where a name reads u_grid ... ps_grid; with refresh = 0 the grid arrays are taken as they are.
+ *               Vorticity, divergence and grad ln ps are always transformed from the spectral state (time level 1) into arrays
+ *               of this call's own, made at first use.  Then one launch of the kernel per family ({omega_grid, omega_plev}; the
+ *               rest) into the result arrays, which are allocated the first time a name is asked for.  n_names = 0: every name
+ *               (the pressure-level ones only where target levels are configured).  The spectral state is not touched.
+ *   _read       a computed result as fp64 into dst_device[count][levels][48][96] ([count][48][96] for the column integrals),
+ *               device to device, stream-ordered. */
+int spd_model_derive_compute(spd_model_handle m, const char *const *names, int n_names, int first, int count, int refresh,
+                             void *stream);
+int spd_model_derive_read(spd_model_handle m, const char *name, int first, int count, void *dst_device, size_t dst_bytes,
+                          void *stream);
 /* The tape: time series of fields recorded on the device inside spd_model_step / spd_model_step_checked_begin calls of any length.
  * A ring buffer in device memory, per model, holds the last `capacity` samples of the chosen variables for every member; one
  * sample is taken after every step that leaves the model's absolute step counter at a multiple of `every` (the statistics' rule),

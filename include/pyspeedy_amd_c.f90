@@ -213,6 +213,23 @@ module pyspeedy_amd_c
             integer(c_int), value :: first, count
             integer(c_size_t), value :: dst_bytes
         end function
+        ! derived fields (pyspeedy_amd.h: spd_model_derive_*): vor_grid, div_grid, omega_grid, rh_grid, theta_grid (8 levels), tcwv,
+        ! ivt_u, ivt_v, ke_col (one plane), omega_plev, vor_plev, div_plev, rh_plev, theta_plev (the levels of spd_model_plev_configure)
+        integer(c_int) function spd_model_derive_compute(model, names, n_names, first, count, refresh, stream) &
+                bind(C, name="spd_model_derive_compute")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, stream
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), value :: n_names, first, count, refresh
+        end function
+        integer(c_int) function spd_model_derive_read(model, name, first, count, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_derive_read")
+            import :: c_ptr, c_int, c_char, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            character(kind=c_char), intent(in) :: name(*)
+            integer(c_int), value :: first, count
+            integer(c_size_t), value :: dst_bytes
+        end function
         ! the tape: time series of fields recorded on the device inside spd_model_step calls (pyspeedy_amd.h: spd_model_tape_*).
         ! names as for the statistics; dtype: SPD_TAPE_F32 (0) / SPD_TAPE_F64 (1); rows: (6, held) int32, oldest sample first:
         ! step counter after the sampled step, year, month, day, hour, minute; _read: (96, 48[, levels], nt, count) in the dtype

@@ -217,6 +217,8 @@ _SIGNATURES = {
     "spd_model_plev_levels": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     "spd_model_plev_compute": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "spd_model_plev_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_derive_compute": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "spd_model_derive_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     # outer boundary (include/pyspeedy_amd_driver.h): the procedures of speedy_driver.f90.j2
     "spd_modelstate_init": (C.c_int, [C.POINTER(C.c_int64)]),
     "spd_modelstate_init_ensemble": (C.c_int, [C.POINTER(C.c_int64), C.c_int32]),

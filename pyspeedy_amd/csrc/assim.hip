@@ -242,8 +242,8 @@ int spd_assim_check(const double *weights, int n_patterns, const char *const *na
         const int id = names[k] ? stats_id(names[k]) : -1;
         if (id < 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, u_plev, v_plev, t_plev, q_plev, z_plev, mslp)");
-        if (id == 6 || id == 7)
+                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, u_plev, v_plev, t_plev, q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
+        if (cat_kind(id) == CAT_PRECIP)
             return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' (entry " + std::to_string(k) +
                                          ") cannot be assimilated: precnv and precls are outputs of the column physics, not functions of the state");
         const int fixed = kStatsCatalogue[id].levels;
@@ -278,7 +278,7 @@ int spd_model_assim_configure(spd_model_handle m, const double *weights, int n_p
     std::vector<spd_model::Assim::Entry> entries;
     for (int k = 0; k < n_entries; ++k) {
         entries.push_back({stats_id(names[k]), levels[k], patterns[k]});
-        if (entries[k].name < kPlevFirst) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
+        if (!cat_needs_levels(entries[k].name)) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
         if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
         if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
             return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" + names[k] +

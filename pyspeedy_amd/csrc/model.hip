@@ -318,7 +318,7 @@ int sample_ids(const char *who, const char *const *names, int n_names, std::vect
         if (id < 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
                                          "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                         "q_plev, z_plev, mslp)");
+                                         "q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
         if (std::find(ids.begin(), ids.end(), id) != ids.end())
             return m_fail(SPD_E_ARG, std::string(who) + ": variable '" + names[k] + "' named twice");
         ids.push_back(id);
@@ -329,25 +329,34 @@ int sample_ids(const char *who, const char *const *names, int n_names, std::vect
 // the variables `ids` of the model's M members: which planes the slab holds (front.uv, precip, xf_fields, slab_fields, plev.mask)
 // and how large slab and tables are
 void plan_sample(const spd_model *m, const std::vector<int> &ids, spd_model::SampleFront &front, SamplePlan &plan) {
-    int needs = 0, plev_planes = 0;
-    auto levels_of = [&](int id) { return id >= kPlevFirst && id != kPlevFirst + PLEV_MSLP ? m->plev.n : kStatsCatalogue[id].levels; };
+    int needs = 0, plev_planes = 0;  // needs: bits of XfSource
+    auto levels_of = [&](int id) { return kStatsCatalogue[id].levels == 0 ? m->plev.n : kStatsCatalogue[id].levels; };
     for (int id : ids) {
         plan.vars.push_back({id, levels_of(id), plan.planes});
         plan.planes += static_cast<size_t>(levels_of(id));
-        if (id < 6) plan.xf.push_back(id);
-        front.precip = front.precip || id == 6 || id == 7;
-        if (id >= kPlevFirst) {
+        if (cat_kind(id) == CAT_XF) plan.xf.push_back(xf_source(id));
+        front.precip = front.precip || cat_kind(id) == CAT_PRECIP;
+        if (cat_kind(id) == CAT_PLEV) {
             front.plev.mask |= 1 << (id - kPlevFirst);
             needs |= kPlevNeeds[id - kPlevFirst];
             plev_planes += levels_of(id);
         }
+        if (cat_kind(id) == CAT_DERIVE) {
+            const int v = id - kDeriveFirst;
+            front.derive.mask |= 1 << v;
+            for (int x = 0; x < DIN_N; ++x)
+                if (kDeriveNeeds[v] >> x & 1) needs |= 1 << kDeriveInXf[x];
+            if (kDeriveNeeds[v] & kDinPs) needs |= 1 << XF_PS;
+            if (kDeriveNeeds[v] & kDinGrad) needs |= 1 << XF_PX | 1 << XF_PY;
+            plev_planes += levels_of(id);
+        }
     }
-    for (int id = 0; id < 6; ++id)
-        if ((needs >> id & 1) && std::find(plan.xf.begin(), plan.xf.end(), id) == plan.xf.end()) plan.xf.push_back(id);
-    for (int id : plan.xf) {
-        plan.xf_at[id] = front.xf_fields;
-        front.xf_fields += kStatsCatalogue[id].levels;
-        front.uv = front.uv || id < 2;
+    for (int x = 0; x < XF_N; ++x)
+        if ((needs >> x & 1) && std::find(plan.xf.begin(), plan.xf.end(), x) == plan.xf.end()) plan.xf.push_back(x);
+    for (int x : plan.xf) {
+        plan.xf_at[x] = front.xf_fields;
+        front.xf_fields += kXfLevels[x];
+        front.uv = front.uv || x == XF_U || x == XF_V;
     }
     front.slab_fields = front.xf_fields + plev_planes;
     const size_t M = static_cast<size_t>(m->M);
@@ -370,20 +379,41 @@ hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_mo
         for (size_t i = 0; i < M; ++i) {
             const size_t w = i * 8, s1 = i * 16;
             size_t j = 0;
-            for (const int id : plan.xf) {
-                for (int k = 0; k < kStatsCatalogue[id].levels; ++k, ++j) {
+            for (const int x : plan.xf) {
+                for (int k = 0; k < kXfLevels[x]; ++k, ++j) {
                     double *dst = front.slab + (i * front.slab_fields + j) * NG;
-                    switch (id) {
-                        case 0: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
-                        case 1: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
-                        case 2: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
-                        case 3: host_table[par].push_back({spec(P.tr, s1 + k), dst, 1, 0}); break;
-                        case 4: host_table[par].push_back({spec(m->phi_buf[par], w + k), dst, 1, 0}); break;
-                        default: host_table[par].push_back({spec(P.ps, i * 2), dst, 1, 0}); break;
+                    switch (x) {
+                        case XF_U: host_table[par].push_back({spec(P.sv, s1 + k), dst, 2, 0}); break;
+                        case XF_V: host_table[par].push_back({spec(P.sv, half + s1 + k), dst, 2, 0}); break;
+                        case XF_T: host_table[par].push_back({spec(P.t, s1 + k), dst, 1, 0}); break;
+                        case XF_Q: host_table[par].push_back({spec(P.tr, s1 + k), dst, 1, 0}); break;
+                        case XF_PHI: host_table[par].push_back({spec(m->phi_buf[par], w + k), dst, 1, 0}); break;
+                        case XF_PS: host_table[par].push_back({spec(P.ps, i * 2), dst, 1, 0}); break;
+                        case XF_VOR: host_table[par].push_back({spec(P.vor, s1 + k), dst, 1, 0}); break;
+                        case XF_DIV: host_table[par].push_back({spec(P.div, s1 + k), dst, 1, 0}); break;
+                        // grad ln ps as the step forms it (build_inverse_tables), at the export fields' time level
+                        case XF_PX: host_table[par].push_back({spec(P.ps, i * 2), dst, 2, 3, nullptr}); break;
+                        default: host_table[par].push_back({spec(P.ps, i * 2), dst, 2, 4, nullptr}); break;
                     }
                 }
             }
         }
+    }
+    if (front.derive.mask) {
+        DeriveArgs &a = front.derive;
+        const long stride = static_cast<long>(front.slab_fields) * NG;
+        auto plane = [&](int x) { return plan.xf_at[x] >= 0 ? front.slab + static_cast<size_t>(plan.xf_at[x]) * NG : nullptr; };
+        for (int x = 0; x < DIN_N; ++x) {
+            a.in[x] = plane(kDeriveInXf[x]);
+            a.in_stride[x] = stride;
+        }
+        a.ps = plane(XF_PS);
+        a.px = plane(XF_PX);
+        a.py = plane(XF_PY);
+        a.ps_stride = a.px_stride = a.py_stride = stride;
+        a.raw = 1;
+        a.n = m->plev.n;
+        std::copy(m->plev.lnp, m->plev.lnp + kPlevMaxLevels, a.lnp);
     }
     int plev_plane = front.xf_fields;
     if (front.plev.mask) {
@@ -403,11 +433,17 @@ hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_mo
     slab_plane.clear();
     for (const auto &v : plan.vars)
         for (int k = 0; k < v.levels; ++k) {
-            if (v.id < 6) slab_plane.push_back(plan.xf_at[v.id] + k);
-            else if (v.id >= kPlevFirst) {
+            if (cat_kind(v.id) == CAT_XF) slab_plane.push_back(plan.xf_at[xf_source(v.id)] + k);
+            else if (cat_kind(v.id) == CAT_PLEV) {
                 if (k == 0) {
                     front.plev.out[v.id - kPlevFirst] = front.slab + static_cast<size_t>(plev_plane) * NG;
                     front.plev.out_stride[v.id - kPlevFirst] = static_cast<long>(front.slab_fields) * NG;
+                }
+                slab_plane.push_back(plev_plane++);
+            } else if (cat_kind(v.id) == CAT_DERIVE) {
+                if (k == 0) {
+                    front.derive.out[v.id - kDeriveFirst] = front.slab + static_cast<size_t>(plev_plane) * NG;
+                    front.derive.out_stride[v.id - kDeriveFirst] = static_cast<long>(front.slab_fields) * NG;
                 }
                 slab_plane.push_back(plev_plane++);
             } else slab_plane.push_back(-1);
@@ -434,6 +470,11 @@ hipError_t sample_front(spd_model *m, const spd_model::SampleFront &f, int first
         PlevArgs a = f.plev;
         a.first = first;
         e = run_plev(a, count, s);
+    }
+    if (e == hipSuccess && f.derive.mask) {  // likewise, behind it
+        DeriveArgs a = f.derive;
+        a.first = first;
+        e = run_derive(a, count, s);
     }
     return e;
 }

@@ -2,7 +2,7 @@
 // the carving of an allocation that every in-loop feature's _configure and _read run around their own work; the front end of a
 // sample that the statistics and four of the tapes share (defined in model.hip).  model.hip holds the model's life, its registry,
 // the step loop and the rest of the C ABI; the host code of each in-loop feature lies behind its kernels in the feature's own file
-// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, plev.hip).
+// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, plev.hip, derive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +19,7 @@
 #include "context.hpp"
 #include "model.hpp"
 #include "plev.hpp"
+#include "derive.hpp"
 #include "stats.hpp"
 #include "spectra.hpp"
 #include "tape.hpp"
@@ -184,14 +185,17 @@ struct spd_model {
     FieldDesc *exp_inv_table[2] = {nullptr, nullptr}, *exp_fwd_table[2] = {nullptr, nullptr};  // 41 / 40 per member; [phi buffer]
     // What the front end of a sample (statistics or tape) runs and where it writes: vort2vel when u or v is wanted, the export
     // transforms over a descriptor table ([phi buffer]) whose destinations are the slab [M][slab_fields][4608], and the
-    // pressure-level kernel (raw = 1) from the slab's transformed planes into its further planes.  The statistics, the tape
-    // and the ensemble tape each own one, in their own allocation.
+    // pressure-level kernel (raw = 1) from the slab's transformed planes into its further planes, then the derived-field kernel
+    // (raw = 1) likewise.  The statistics, the tape and the ensemble tape each own one, in their own allocation.
     struct SampleFront {
         bool uv = false, precip = false;
         // slab_fields: planes of a member in the slab; the first xf_fields of them are written by the export transforms, the
-        // others (pressure-level variables only) by the pressure-level kernel from those
+        // others (pressure-level and derived variables only) by the pressure-level and derived-field kernels from those
         int slab_fields = 0, xf_fields = 0;
-        PlevArgs plev{};  // (plev.mask != 0: a pressure-level variable is sampled)
+        PlevArgs plev{};      // (plev.mask != 0: a pressure-level variable is sampled)
+        DeriveArgs derive{};  // (derive.mask != 0: a derived variable of the derived-field kernel is sampled)
+        // a variable on the target levels of spd_model_plev_configure is sampled (of either kernel)
+        bool holds_plev() const { return plev.mask != 0 || (derive.mask & kDerivePlevMask) != 0; }
         double *slab = nullptr;
         FieldDesc *table[2] = {nullptr, nullptr};
     };
@@ -293,7 +297,7 @@ struct spd_model {
     // at, its samples so far and the rows of the closed ones are host state.
     struct WinTape : SampleFront {
         struct Entry {
-            int name, op, levels;  // name: catalogue id, 14 wspd_grid, 15 wspd_plev
+            int name, op, levels;  // name: catalogue id; behind the catalogue: wspd_grid, wspd_plev
             double threshold;
             size_t offset;  // elements from `data` to slot 0, member 0 of the entry
         };
@@ -424,6 +428,16 @@ struct spd_model {
         int cap[PLEV_NVARS] = {};     // levels the allocation holds
         bool have[PLEV_NVARS] = {};   // computed since the levels were configured
     } plev;
+    // Derived fields (spd_model_derive_*): the result arrays [M][levels][4608] of vor_grid, div_grid ([0], [1]) and of the kernel's
+    // outputs ([2 + DeriveVar]), carved from the arena the first time a name is computed (the pressure-level ones again only if a
+    // later configuration has more levels), and grad ln ps [2][M][4608], transformed by a descriptor table of its own.
+    struct Derive {
+        double *out[2 + DRV_NVARS] = {};
+        int cap[2 + DRV_NVARS] = {};    // levels the allocation holds
+        bool have[2 + DRV_NVARS] = {};  // computed (the pressure-level ones: since the levels were configured)
+        double *grad = nullptr;
+        FieldDesc *table = nullptr;     // [M][18]: vor, div (8 levels each), px, py of a member
+    } derive;
 };
 
 namespace spd {
@@ -525,16 +539,41 @@ inline int destination_fits(const char *who, const void *dst_device, size_t dst_
 // ---- the catalogue of grid-space names that the statistics, the tapes and the pressure-level fields share ----
 struct StatsCatalogueEntry {
     const char *name;
-    int levels, unit;  // unit: as StatsPlane::unit
+    int levels, unit;  // levels: 0 = the configured target levels; unit: as StatsPlane::unit
+    int kind;          // CatKind
 };
+// where a name's planes come from: the export transforms (an XfSource), the column kernel's precipitation outputs, the
+// pressure-level kernel (levels 0: the configured target levels; mslp one), the derived-field kernel (levels 0: likewise)
+enum CatKind { CAT_XF = 0, CAT_PRECIP, CAT_PLEV, CAT_DERIVE };
 // ids 0 ... 5: from the spectral state through the export transforms; 6, 7: the column kernel's precipitation outputs;
 // 8 ... 13: the pressure-level variables (kPlevFirst + PlevVar; levels: the configured target levels, mslp one), written into the
-// slab in export units by the pressure-level kernel
-constexpr StatsCatalogueEntry kStatsCatalogue[] = {{"u_grid", KX, 0},   {"v_grid", KX, 0}, {"t_grid", KX, 0}, {"q_grid", KX, 1},
-                                                   {"phi_grid", KX, 2}, {"ps_grid", 1, 3}, {"precnv", 1, 0}, {"precls", 1, 0},
-                                                   {"u_plev", 0, 0},    {"v_plev", 0, 0},  {"t_plev", 0, 0}, {"q_plev", 0, 0},
-                                                   {"z_plev", 0, 0},    {"mslp", 1, 0}};
-constexpr int kPlevFirst = 8;
+// slab in export units by the pressure-level kernel; 14, 15: vorticity and divergence through the export transforms;
+// 16 ... 27: the derived-field kernel's outputs (kDeriveFirst + DeriveVar), written into the slab in export units
+constexpr StatsCatalogueEntry kStatsCatalogue[] = {
+    {"u_grid", KX, 0, CAT_XF},       {"v_grid", KX, 0, CAT_XF},      {"t_grid", KX, 0, CAT_XF},     {"q_grid", KX, 1, CAT_XF},
+    {"phi_grid", KX, 2, CAT_XF},     {"ps_grid", 1, 3, CAT_XF},      {"precnv", 1, 0, CAT_PRECIP},  {"precls", 1, 0, CAT_PRECIP},
+    {"u_plev", 0, 0, CAT_PLEV},      {"v_plev", 0, 0, CAT_PLEV},     {"t_plev", 0, 0, CAT_PLEV},    {"q_plev", 0, 0, CAT_PLEV},
+    {"z_plev", 0, 0, CAT_PLEV},      {"mslp", 1, 0, CAT_PLEV},       {"vor_grid", KX, 0, CAT_XF},   {"div_grid", KX, 0, CAT_XF},
+    {"omega_grid", KX, 0, CAT_DERIVE}, {"rh_grid", KX, 0, CAT_DERIVE}, {"theta_grid", KX, 0, CAT_DERIVE}, {"tcwv", 1, 0, CAT_DERIVE},
+    {"ivt_u", 1, 0, CAT_DERIVE},     {"ivt_v", 1, 0, CAT_DERIVE},    {"ke_col", 1, 0, CAT_DERIVE},  {"omega_plev", 0, 0, CAT_DERIVE},
+    {"vor_plev", 0, 0, CAT_DERIVE},  {"div_plev", 0, 0, CAT_DERIVE}, {"rh_plev", 0, 0, CAT_DERIVE}, {"theta_plev", 0, 0, CAT_DERIVE}};
+constexpr int kPlevFirst = 8, kVorGrid = 14, kDeriveFirst = 16;
+// the derived names, and what every recorder's "unknown variable" message appends to the list it has always given
+#define SPD_DERIVED_TAIL "; derived fields: " SPD_DERIVED_NAMES
+#define SPD_DERIVED_NAMES \
+    "vor_grid, div_grid, omega_grid, rh_grid, theta_grid, tcwv, ivt_u, ivt_v, ke_col, omega_plev, vor_plev, div_plev, rh_plev, theta_plev"
+inline constexpr int cat_kind(int id) { return kStatsCatalogue[id].kind; }
+// the name is computed at the target levels of spd_model_plev_configure (mslp, of one level, is the pressure-level kernel's as well)
+inline constexpr bool cat_needs_levels(int id) {
+    return cat_kind(id) == CAT_PLEV || (cat_kind(id) == CAT_DERIVE && kStatsCatalogue[id].levels == 0);
+}
+// What the export transforms can write into a slab: catalogue ids 0 ... 5, vorticity and divergence (catalogue ids 14, 15), and
+// the two components of grad ln ps, which no recorder can name (the step's own entries of mode 3 / 4 with kcos = 2).
+enum XfSource { XF_U = 0, XF_V, XF_T, XF_Q, XF_PHI, XF_PS, XF_VOR, XF_DIV, XF_PX, XF_PY, XF_N };
+constexpr int kXfLevels[XF_N] = {KX, KX, KX, KX, KX, 1, KX, KX, 1, 1};
+inline constexpr int xf_source(int id) { return id < 6 ? id : XF_VOR + (id - kVorGrid); }  // of a CAT_XF name
+// the XfSource of each sigma-level input of the derived-field kernel (DeriveIn)
+constexpr int kDeriveInXf[DIN_N] = {XF_U, XF_V, XF_T, XF_Q, XF_VOR, XF_DIV};
 // sigma-level inputs (catalogue ids 0 ... 5, as bits) of each pressure-level variable: ps always; T with Z (both extrapolations)
 constexpr int kPlevNeeds[PLEV_NVARS] = {1 << 0 | 1 << 5, 1 << 1 | 1 << 5, 1 << 2 | 1 << 5, 1 << 3 | 1 << 5, 1 << 2 | 1 << 4 | 1 << 5,
                                         1 << 2 | 1 << 5};
@@ -552,10 +591,10 @@ struct SamplePlan {
         size_t first_plane;  // planes of the variables before this one (of one member)
     };
     std::vector<Var> vars;
-    // what the export transforms write into the slab, in slab order: the sigma-level variables asked for, then those only a
-    // pressure-level variable needs; xf_at[id]: first slab plane of variable id (-1: not transformed)
+    // what the export transforms write into the slab (XfSource), in slab order: the variables asked for, then those only a
+    // pressure-level or derived variable needs; xf_at[x]: first slab plane of source x (-1: not transformed)
     std::vector<int> xf;
-    int xf_at[6] = {-1, -1, -1, -1, -1, -1};
+    int xf_at[XF_N] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
     size_t planes = 0;                        // planes of all variables of one member
     size_t slab_bytes = 0, table_bytes = 0;   // of the slab and of ONE descriptor table, rounded up to kSampleAlign
 };

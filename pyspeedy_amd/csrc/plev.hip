@@ -13,6 +13,7 @@
 
 #include "model_state.hpp"
 #include "plev.hpp"
+#include "plev_layer.hpp"
 #include "vertical_consts.hpp"
 
 namespace spd {
@@ -20,29 +21,8 @@ namespace spd {
 namespace {
 constexpr int kT = 256;
 
-struct LayerRecip {
-    double r[KX - 1];
-    constexpr LayerRecip() : r{} {
-        for (int k = 0; k < KX - 1; ++k) r[k] = 1.0 / (vc::sigl[k + 1] - vc::sigl[k]);
-    }
-};
-constexpr LayerRecip kRecip{};
-
-__device__ __forceinline__ void load8(double (&x)[KX], const double *__restrict__ base) {
-#pragma unroll
-    for (int k = 0; k < KX; ++k) x[k] = base[static_cast<long>(k) * NG];
-}
-
-// X[k] + w (X[k+1] - X[k]) of the layer the flags select (ge[k]: s >= sigl[k], k = 1 ... 6)
-__device__ __forceinline__ double layer_value(const double (&x)[KX], const bool (&ge)[KX - 1], double w) {
-    double lo = x[0], hi = x[1];
-#pragma unroll
-    for (int k = 1; k < KX - 1; ++k) {
-        lo = ge[k] ? x[k] : lo;
-        hi = ge[k] ? x[k + 1] : hi;
-    }
-    return lo + w * (hi - lo);
-}
+using plevl::layer_value;
+using plevl::load8;
 
 // blockIdx.x: points, blockIdx.y: member of the launch
 __global__ __launch_bounds__(kT) void plev_kernel(const PlevArgs a) {
@@ -80,17 +60,10 @@ __global__ __launch_bounds__(kT) void plev_kernel(const PlevArgs a) {
     for (int j = 0; j < a.n; ++j) {
         const double s = a.lnp[j] - lnps;
         const long o = static_cast<long>(j) * NG + p;
-        bool ge[KX - 1];
-        double sg = vc::sigl[0], rv = kRecip.r[0];
-#pragma unroll
-        for (int k = 1; k < KX - 1; ++k) {
-            ge[k] = s >= vc::sigl[k];
-            sg = ge[k] ? vc::sigl[k] : sg;
-            rv = ge[k] ? kRecip.r[k] : rv;
-        }
-        ge[0] = true;
-        const double w = (s - sg) * rv;
-        const bool top = s < vc::sigl[0], below = s > vc::sigl[KX - 1];
+        const plevl::Layer layer = plevl::find_layer(s);
+        const bool(&ge)[KX - 1] = layer.ge;
+        const double w = layer.w;
+        const bool top = layer.top, below = layer.below;
         if (want_u) a.out[PLEV_U][i * a.out_stride[PLEV_U] + o] = top ? u[0] : below ? u[KX - 1] : layer_value(u, ge, w);
         if (want_v) a.out[PLEV_V][i * a.out_stride[PLEV_V] + o] = top ? v[0] : below ? v[KX - 1] : layer_value(v, ge, w);
         if (want_q) a.out[PLEV_Q][i * a.out_stride[PLEV_Q] + o] = top ? q[0] : below ? q[KX - 1] : layer_value(q, ge, w);
@@ -125,7 +98,7 @@ hipError_t run_plev(const PlevArgs &args, int count, hipStream_t s) {
 
 static int plev_id(const char *name) {
     const int id = name ? stats_id(name) : -1;
-    return id >= kPlevFirst ? id - kPlevFirst : -1;
+    return id >= 0 && cat_kind(id) == CAT_PLEV ? id - kPlevFirst : -1;
 }
 
 extern "C" {
@@ -145,18 +118,18 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
     if (!up && !down) return m_fail(SPD_E_ARG, std::string(who) + ": the levels must be strictly increasing or strictly decreasing");
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
     if (int rc = usable(m, who)) return rc;
-    if (m->stats.on && m->stats.plev.mask)
+    if (m->stats.on && m->stats.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": statistics of a pressure-level variable are configured; switch them off first "
                                                     "(spd_model_stats_configure)");
-    if (m->tape.on && m->tape.plev.mask)
+    if (m->tape.on && m->tape.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the tape holds a pressure-level variable; switch it off first (spd_model_tape_configure)");
-    if (m->enstape.on && m->enstape.plev.mask)
+    if (m->enstape.on && m->enstape.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the ensemble tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_enstape_configure)");
-    if (m->wintape.on && m->wintape.plev.mask)
+    if (m->wintape.on && m->wintape.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the window tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_wintape_configure)");
-    if (m->projtape.on && m->projtape.plev.mask)
+    if (m->projtape.on && m->projtape.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the projection tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_projtape_configure)");
     spd_model::Plev &pl = m->plev;
@@ -166,6 +139,8 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
         pl.lnp[j] = j < n ? std::log(levels_pa[j]) : 0.0;
     }
     for (bool &h : pl.have) h = false;  // (results of the previous levels are not handed out under the new ones)
+    for (int v = 0; v < DRV_NVARS; ++v)
+        if (kDerivePlevMask >> v & 1) m->derive.have[2 + v] = false;
     return SPD_OK;
 }
 

@@ -149,7 +149,7 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
             if (id < 0)
                 return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
                                              "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                             "q_plev, z_plev, mslp)");
+                                             "q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
             entries.push_back({id, levels[k], patterns[k]});
         }
         // (a level is checked here against the name's fixed count; a pressure-level name's count is the model's, below)
@@ -165,7 +165,7 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
     }
     if (int rc = configure_allowed(m, who)) return rc;
     for (int k = 0; k < n_entries; ++k) {
-        if (entries[k].name < kPlevFirst) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
+        if (!cat_needs_levels(entries[k].name)) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
         if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
         if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
             return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +

@@ -136,7 +136,7 @@ int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n
         return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
     if (int rc = configure_allowed(m, who)) return rc;
     for (size_t k = 0; k < ids.size(); ++k)
-        if (ids[k] >= kPlevFirst && m->plev.n == 0)
+        if (cat_needs_levels(ids[k]) && m->plev.n == 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
     spd_model::Tape &tp = m->tape;
     if (int rc = retire(m, tp)) return rc;

@@ -187,7 +187,7 @@ static hipError_t run_wintape_step(const WinTapePlane *planes, int nplanes, cons
 // ---- host side: the schedule, the step loop's launches, the configuration and the C ABI (spd_model_wintape_*, spd_wintape_plan) ----
 
 namespace {
-// names: the catalogue's fourteen, then the two wind speeds of this recorder only (u and v: the catalogue ids they are formed from)
+// names: the catalogue's, then the two wind speeds of this recorder only (u and v: the catalogue ids they are formed from)
 constexpr int kWinWspdGrid = kStatsCatalogueSize, kWinWspdPlev = kStatsCatalogueSize + 1, kWinNNames = kStatsCatalogueSize + 2;
 constexpr int kWinNOps = 6;
 int win_name_id(const char *name) {
@@ -196,7 +196,7 @@ int win_name_id(const char *name) {
     if (std::strcmp(name, "wspd_plev") == 0) return kWinWspdPlev;
     return stats_id(name);
 }
-bool win_needs_levels(int id) { return id == kWinWspdPlev || (id >= kPlevFirst && id < kStatsCatalogueSize); }
+bool win_needs_levels(int id) { return id == kWinWspdPlev || (id < kStatsCatalogueSize && cat_needs_levels(id)); }
 int win_u_id(int id) { return id == kWinWspdGrid ? 0 : kPlevFirst + PLEV_U; }
 const char *const kWinOff = "no window tape configured (spd_model_wintape_configure)";
 const char *const kWinOpNames[kWinNOps] = {"SPD_WIN_SUM", "SPD_WIN_MEAN", "SPD_WIN_MIN", "SPD_WIN_MAX", "SPD_WIN_COUNT_ABOVE", "SPD_WIN_COUNT_BELOW"};
@@ -280,7 +280,7 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
         if (id < 0)
             return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
                                          "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                         "q_plev, z_plev, mslp, wspd_grid, wspd_plev)");
+                                         "q_plev, z_plev, mslp, wspd_grid, wspd_plev)" SPD_DERIVED_TAIL);
         entries.push_back({id, ops[k], 0, 0.0, 0});
     }
     for (int k = 0; k < n_entries; ++k)

@@ -341,6 +341,7 @@ class EnsembleModel:
     # ---- time-mean statistics accumulated on the device (spd_model_stats_*, include/pyspeedy_amd.h) ---------------------
     STATS_VARIABLES = ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid", "ps_grid", "precnv", "precls",
                        "u_plev", "v_plev", "t_plev", "q_plev", "z_plev", "mslp")  # (the last six: after plev_configure)
+    # (every recorder that takes these names takes the fourteen DERIVED_VARIABLES as well)
 
     def stats_configure(self, variables, every, variance=True):
         """Sample `variables` (any of STATS_VARIABLES) after every step that leaves current_step at a multiple of `every`, inside
@@ -363,9 +364,9 @@ class EnsembleModel:
         return int(n)
 
     def _stats_shape(self, name):
-        if name in self.PLEV_VARIABLES[:5]:
+        if name in self.PLEV_VARIABLES[:5] or name in self.DERIVED_VARIABLES[9:]:
             return (len(self.plev_levels), 48, 96)
-        levels = 8 if name in ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid") else 1
+        levels = 8 if name in ("u_grid", "v_grid", "t_grid", "q_grid", "phi_grid") + self.DERIVED_VARIABLES[:5] else 1
         return (levels, 48, 96) if levels > 1 else (48, 96)
 
     def _stats_read(self, name, kind, first, count):
@@ -1267,6 +1268,35 @@ class EnsembleModel:
                 t = torch.empty((count,) + self._stats_shape(name), dtype=torch.float64, device=self.sp.device)
                 check(self._lib.spd_model_plev_read(self._m, name.encode(), first, count, C.c_void_p(t.data_ptr()), t.numel() * 8,
                                                     self._stream()), "spd_model_plev_read(%s)" % name)
+                out[name] = t
+        return out
+
+    # ---- derived fields (spd_model_derive_*, include/pyspeedy_amd.h) ------------------------------------------------------
+    # Every recorder that takes STATS_VARIABLES takes these names as well (the window tape: next to WINTAPE_NAMES).
+    DERIVED_VARIABLES = ("vor_grid", "div_grid", "omega_grid", "rh_grid", "theta_grid", "tcwv", "ivt_u", "ivt_v", "ke_col",
+                         "omega_plev", "vor_plev", "div_plev", "rh_plev", "theta_plev")  # (the last five: after plev_configure)
+
+    def derived(self, names=None, first=0, count=None, refresh=True):
+        """Derived fields of members [first, first + count): a dict of float64 tensors on the model's device.  [count][8][48][96]:
+        vor_grid, div_grid (1/s), omega_grid (Pa/s, the model's own continuity equation), rh_grid (a fraction, not clipped),
+        theta_grid (K); [count][48][96]: tcwv (kg/m^2), ivt_u, ivt_v (kg/(m s)), ke_col (J/m^2); [count][n][48][96] at the levels
+        of plev_configure: omega_plev, vor_plev, div_plev, rh_plev, theta_plev (linear in ln p between the full levels, the
+        nearest full level's value outside them; points under the ground are not masked).  `names`: any of DERIVED_VARIABLES,
+        None = all that can be computed (the pressure-level ones only with levels configured).  With `refresh` the grid arrays
+        are first brought up to date (spectral2grid() of those members); without, they are used as they are."""
+        if names is None:
+            names = [v for v in self.DERIVED_VARIABLES if not v.endswith("_plev") or self.plev_levels]
+        names = [str(v) for v in names]
+        first, count = self._range(first, count)
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        out = {}
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_derive_compute(self._m, arr, len(names), first, count, int(bool(refresh)), self._stream()),
+                  "spd_model_derive_compute")
+            for name in names:
+                t = torch.empty((count,) + self._stats_shape(name), dtype=torch.float64, device=self.sp.device)
+                check(self._lib.spd_model_derive_read(self._m, name.encode(), first, count, C.c_void_p(t.data_ptr()), t.numel() * 8,
+                                                      self._stream()), "spd_model_derive_read(%s)" % name)
                 out[name] = t
         return out
 

@@ -13,11 +13,13 @@
 
 #include <cstddef>
 
+#include "step_plan.hpp"
+
 struct spd_model;
 
 namespace spd {
 
-constexpr int kEnsTapeGroups = 4;         // partials per slot: one per group stream of the step (spd_model: cstream[4])
+constexpr int kEnsTapeGroups = kGroupStreams;  // partials per slot: one per group stream of the step (step_plan.hpp)
 constexpr int kEnsTapeReadSamples = 64;   // samples of one launch of the read kernel (their counts travel by value)
 
 // One plane (a level of a variable), as the fold kernel sees it.

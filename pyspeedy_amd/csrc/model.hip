@@ -16,6 +16,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -26,6 +27,7 @@
 #include "launch_events.hpp"
 #include "sppt_point.hpp"
 #include "staged_products.hpp"
+#include "step_plan.hpp"
 #include "stream_apart.hpp"
 
 namespace spd {
@@ -727,7 +729,7 @@ int spd_model_destroy(spd_model_handle m) {
         }
     }
     for (size_t i = keep_first ? 1 : 0; i < m->blocks.size(); ++i) (void)hipFree(m->blocks[i].base);
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < kGroupStreams; ++i) {
         if (m->cstream[i]) (void)hipStreamDestroy(m->cstream[i]);
         if (m->cev[i]) (void)hipEventDestroy(m->cev[i]);
     }
@@ -967,12 +969,7 @@ static bool staged_products(const spd_model *m) { return !(m->split_dyn_physics 
 
 // cpl != nullptr: the coupling that follows the step is part of the last launch
 // ride != nullptr: the range check of the PREVIOUS step of these members rides in this step's spectral -> grid launch
-// tau: how the column kernel keeps the longwave transmissivities (step_segment); the default is the array form
-constexpr int kTauFromMembers = 20;  // members of a round from which the compact form is used (step_segment)
-struct TauPlan {
-    bool compact = false;                             // the launch uses the compact record instead of rad_tau2
-    bool store_record = false, store_array = false;  // (compact shortwave steps) what the step leaves behind
-};
+// tau: how the column kernel keeps the longwave transmissivities (step_plan.hpp); the default is the array form
 static hipError_t step_range(spd_model *m, int j1, int j2, double dt, int compute_shortwave, int first, int count, int diag,
                              bool run_geo, const CouplerArgs *cpl, hipStream_t s, hipEvent_t after_grid2spec = nullptr,
                              const CheckArgs *ride = nullptr, int rim_mode = kRimPlain, const TauPlan &tau = TauPlan{}) {
@@ -1413,7 +1410,7 @@ static int ensure_steps_record(spd_model *m, int nsteps) {
 static int ensure_group_streams(spd_model *m, int G) {
     M_HIP(hipSetDevice(m->ctx->device));
     if (!m->ev_start) M_HIP(hipEventCreateWithFlags(&m->ev_start, hipEventDisableTiming));
-    for (int g = 0; g < G && g < 4; ++g) {
+    for (int g = 0; g < G && g < kGroupStreams; ++g) {
         if (m->cstream[g]) continue;
         // on a hardware queue none of the groups before it is on (stream_apart.hpp: measured, not assumed)
         bool apart = true;
@@ -1424,75 +1421,64 @@ static int ensure_group_streams(spd_model *m, int G) {
     return SPD_OK;
 }
 
-// do_single_step (speedy.f90:20-74) `nsteps` times for all members.  Nothing synchronises; the range check of
-// diagnostics.f90 is available separately through spd_model_check (the reference runs it after every step).
-// record: the range check of every step is left in m->h_steps_err[step][member] (spd_model_step_checked_begin) -- the check of step
-// k rides in the spectral -> grid launch of step k + 1 of the same members, the last one is a launch of its own behind the call.
-// One segment of a call: `nsteps` steps for all members, all rounds and member groups, forked from and joined into the caller's
-// stream.  A call without in-loop breeding is one segment (row0 = 0, rows = nsteps); with it, step_impl issues the segments between
-// the rescale steps, and the rows of a checked call (h_steps_err, steps_accepted) of this segment start at row0 of the call's `rows`.
-static int step_segment(spd_model *m, int nsteps, void *stream, bool record, const char *who, int row0, int rows) {
-    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = usable(m, who)) return rc;
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized (error code -1 of the reference)");
-    if (!m->dyn) return m_fail(SPD_E_ARG, std::string(who) + ": call spd_model_set_time_step first");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it with spd_model_step_checked_end first");
-    const spd_model::Nudge &nd = m->nudge;
-    const bool nudge = nd.loops();
-    if (nudge && nd.in_use == 0)
-        return m_fail(SPD_E_ARG, std::string(who) + ": in-loop nudging is configured but no target slot is in use (spd_model_nudge_set_times)");
-    const long long nudged0 = nd.applied;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const double delt = 86400.0 / 36;
-    // Members never exchange data, so the step is issued group by group on separate streams: every group runs the same
-    // six launches on its own members, and the groups' kernels overlap on the GPU.  The caller's stream orders the whole call:
-    // the group streams start after everything already enqueued on it, and it continues after all of them.
-    // (a call of ONE step forks and joins the group streams around that step -- two dependent cross-stream hand-overs per
-    // step cost more than the overlap gains: measured +12 % at 64 members through spd_parallel_step -- so it is issued serially)
-    const int G = (m->split_dyn_physics || m->profile > 0 || nsteps == 1) ? 1 : m->nchunks;
-    // a range check that was put off rides in the first spectral -> grid launch of this call -- when that is ONE launch over all
-    // members on the stream the check was put off on; otherwise it goes out on its own first
-    if (m->deferred.active && (G > 1 || s != m->deferred.stream || record))
-        if (int rc = settle_deferred_check(m)) return rc;
-    hipStream_t gs[4] = {s, nullptr, nullptr, nullptr};
-    if (G > 1) {
-        if (int rc = ensure_group_streams(m, G)) return rc;
-        M_HIP(hipEventRecord(m->ev_start, s));
-        for (int g = 0; g < G; ++g) {
-            gs[g] = m->cstream[g];
-            M_HIP(hipStreamWaitEvent(gs[g], m->ev_start, 0));
-        }
+// ---- the step loop: a segment is planned once, every step is decided once on the host, issued per member group and committed ----
+
+// What a step changes on the host side of the model, listed once: saved when a segment begins (HostState: the values behind the
+// references) and put back for every round after the first.
+static auto host_state(spd_model *m) {
+    return std::tie(m->cal, m->current_step, m->phi_cur, m->surf_cache_valid, m->phi_ahead, m->sppt_first, m->sppt_step, m->air_absortivity_co2);
+}
+using HostState = std::tuple<Calendar, int, int, bool, bool, bool, long long, double>;
+
+// the open windows of the accumulation tape (its first step) and of the window tape (its first step, its samples so far): put back
+// for every round like the host state, and written to the recorders by the first round only
+struct OpenWindows { int acc_start; WinOpen win; };
+
+// One segment of a call: what is decided before its first step, every recorder's cursor (every round takes the same samples and
+// writes the same slots, for its own members; the two window recorders count closed windows), and what became of its launches.
+struct Segment {
+    spd_model *m;
+    int nsteps;
+    bool record;  // a checked call: the range check of every step is recorded, from row0 of the call's rows on
+    const char *who;
+    int row0;
+    hipStream_t gs[kGroupStreams];
+    Partition part;
+    bool offset, rim, tau_compact;
+    int c0;          // the step counter the segment starts at
+    double tau_co2;  // the CO2 absorptivity the record was made with
+    HostState start;
+    long long nudged0;
+    SampleCursor stats, tape, spectra, enstape, acctape, wintape, projtape;
+    OpenWindows open0, open;
+    int rc = SPD_OK;
+    bool launched, device_failed;  // a launch of this segment went out / a device call of it failed
+    void check_launch(hipError_t e, const char *feature) {  // what a launch of a step returned; feature: "" or "<label>: "
+        if (e == hipSuccess) return;
+        (void)hipGetLastError();
+        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + feature + hipGetErrorString(e));
+        device_failed = true;
     }
-    // whatever way this function is left, the caller's stream continues behind everything the group streams were given
-    struct Join {
-        hipStream_t s, *gs;
-        hipEvent_t *ev;
-        int G;
-        ~Join() {
-            if (G > 1)
-                for (int g = 0; g < G; ++g)
-                    if (hipEventRecord(ev[g], gs[g]) == hipSuccess) (void)hipStreamWaitEvent(s, ev[g], 0);
-        }
-    } join{s, gs, m->cev, G};
-    // Two groups that start together stay together: they have the same work, so both run their transform launches at the same
-    // time and their column launches at the same time, and only the tails overlap.  The second group therefore starts when the
-    // first has issued three quarters of its first step (behind its grid -> spectral launch): from then on one group's
-    // latency-bound transforms run beside the other's streaming column / spectral kernels.  Measured at 64 members: 0.241 ms
-    // per step every time, against 0.243 ... 0.250 when left to chance (profiles/r03_member_groups.txt); 96 members -2.8 %;
-    // nothing at 32 / 48 members or with 3 groups.  It costs a call the time its first and last three quarters of a step run
-    // alone; applied to calls of at least kOffsetFrom steps (in 20-step calls it measured 0 ... +1.5 %; in the 36-step calls of
-    // a time loop with daily hooks -1.8 %: 9.58 -> 9.41 ms per simulated day, round 6; 72 until then).
-    constexpr int kOffsetFrom = 36;
-    const bool offset = G == 2 && nsteps >= kOffsetFrom;
-    if (offset && !m->ev_offset) M_HIP(hipEventCreateWithFlags(&m->ev_offset, hipEventDisableTiming));
-    // rounds (see block_members): the members of a round go through all steps of the call before the next round starts
-    // (also with ONE group when the caller says so by setting member_groups to 1 on a large model -- the outer boundary does for
-    // the two device models it keeps a large ensemble in, which are each other's groups: csrc/driver.cpp -- but never while profiling
-    // or in the split-launch mode, whose single group is the whole model by definition)
-    int rounds = 1;
-    const bool may_round = G > 1 || (m->nchunks == 1 && m->profile == 0 && !m->split_dyn_physics);
-    if (may_round && nsteps > 1 && m->block_members > 0 && m->M >= 4 * m->block_members)
-        rounds = (m->M + G * m->block_members - 1) / (G * m->block_members);
+    void note_accepted(int row) const {  // (record: what the host side of the model looks like after `row` steps of the segment)
+        if (!record) return;
+        int32_t *a = m->steps_accepted.data() + 7 * static_cast<size_t>(row0 + row);
+        stamp_row(a, m->current_step, m->cal);
+        a[6] = m->cal.month_idx;
+    }
+    void rewind() {  // a round begins
+        for (SampleCursor *c : {&stats, &tape, &spectra, &enstape, &acctape, &wintape, &projtape}) c->rewind();
+        open = open0;
+    }
+};
+
+static const char kSstUncovered[] = "SST anomaly planes do not cover the simulated period (speedy.py:338-372)";
+static bool sst_anomaly_covered(const spd_model *m, const TimeInterp &w) {
+    return !m->sst_anomaly_flag || (w.a0 >= 0 && w.a1 >= 0 && w.a0 < m->anom_planes && w.a1 < m->anom_planes);
+}
+
+// The quiet rim, the transmissivities' form, whether every step of the segment can be taken, and where the recorders stand.
+static int plan_segment(Segment &sg) {
+    spd_model *m = sg.m;
     // The quiet rim.  A coefficient beyond the truncation's halo (m + n >= 33, triangle.hpp) feeds nothing but itself, and a member
     // whose state is all +0.0 bits there stays so: its tendencies there are the +0.0 of the packed fields, and the spectral step
     // makes +0.0 of +0.0 (diffuse: (+-0 - a (+0)) b = +-0; advance: +0 + dt (+-0) = +0, and the two filter lines keep +0; the
@@ -1508,273 +1494,281 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
     // for the rest of the call, which is merely slower); phi is recomputed every step from t and phis, and detect saw the +0.0
     // that this t and phis give.  Nothing is carried from call to call -- a host may write the state between calls, through
     // device views as well -- and calls of one step never skip.
-    const bool rim = nsteps >= 2 && !folds(m);
-    m->rim_call = rim;
-    struct HostState {  // what a step changes on the host side of the model
-        Calendar cal;
-        int current_step, phi_cur;
-        bool surf_cache_valid, phi_ahead, sppt_first;
-        long long sppt_step;
-        double co2;
-    };
-    const HostState start{m->cal, m->current_step, m->phi_cur, m->surf_cache_valid, m->phi_ahead, m->sppt_first, m->sppt_step,
-                          m->air_absortivity_co2};
-    // The longwave transmissivities of the steps between two shortwave steps (every third step computes them; the reference keeps
-    // them in rad_tau2): inside a segment of two steps or more the fused column kernel hands them on as the compact record they
-    // are made of and recomputes (physics.hip, COMPACT; option tau_recompute).  The schedule is the segment's own -- every round
-    // and member group follows it, and nothing is carried from call to call: a host may have written rad_tau2 in between,
-    // through device views as well.
-    //   a step without shortwave uses the record when a shortwave step of this segment came before it, rad_tau2 otherwise;
-    //   a shortwave step stores the record unless it is the segment's last step (nobody would read it), and
-    //   stores rad_tau2 when no later shortwave step of the segment will overwrite it (or diag_every_step says so):
-    // at the end of every segment rad_tau2 is what the array form leaves, and only there can anybody look at it -- snapshots,
-    // container copies, get(), the physics replay; no recorder can name it (kStatsCatalogue, kAccNames).
-    // A round takes part from kTauFromMembers members up -- the size from which the default plan steps the members in groups whose
-    // launches overlap and the column kernel waits on memory.  Below that it runs at the issue rate of one wavefront per SIMD and
-    // the exponentials cost more than the bytes save: measured +1.9 % per step at one member, +1 % at 8, +1.5 % at 16, against
-    // -0.5 ... -3 % from 20 up (profiles/tau_recompute_ab.txt).  Option value 2: rounds of any size.
-    bool tau_compact = m->tau_recompute != 0 && nsteps > 1 && staged_products(m);
-    if ((rounds > 1 || tau_compact) && m->sst_anomaly_flag) {  // (what can refuse a step is asked for ALL steps before the first round goes out)
+    sg.rim = sg.nsteps >= 2 && !folds(m);
+    m->rim_call = sg.rim;
+    sg.start = host_state(m);
+    sg.c0 = m->current_step;
+    // (the transmissivities' schedule: step_plan.hpp)
+    sg.tau_compact = m->tau_recompute != 0 && sg.nsteps > 1 && staged_products(m);
+    if ((sg.part.rounds > 1 || sg.tau_compact) && m->sst_anomaly_flag) {  // (what can refuse a step is asked for ALL steps before the first round goes out)
         Calendar ahead = m->cal;
-        for (int it = 0; it < nsteps; ++it) {
+        for (int it = 0; it < sg.nsteps; ++it) {
             ahead.advance();
-            const TimeInterp w = time_interp(ahead);
-            if (w.a0 < 0 || w.a1 < 0 || w.a0 >= m->anom_planes || w.a1 >= m->anom_planes) {
-                if (rounds > 1) return m_fail(SPD_E_ARG, "SST anomaly planes do not cover the simulated period (speedy.py:338-372)");
-                tau_compact = false;  // the segment will be refused half-way without poisoning the model: its steps leave rad_tau2
+            if (!sst_anomaly_covered(m, time_interp(ahead))) {
+                if (sg.part.rounds > 1) return m_fail(SPD_E_ARG, kSstUncovered);
+                sg.tau_compact = false;  // the segment will be refused half-way without poisoning the model: its steps leave rad_tau2
             }
         }
     }
-    const int tau_first_sw = ((3 - start.current_step % 3) % 3 + 3) % 3;  // the segment's first shortwave step (0-based)
-    double tau_co2 = 0.0;                                                  // the CO2 absorptivity the record was made with
-    int rc = SPD_OK;
-    auto note_accepted = [&](int row) {  // (record: what the host side of the model looks like after `row` steps of the call)
-        if (!record) return;
-        int32_t *a = m->steps_accepted.data() + 7 * static_cast<size_t>(row0 + row);
-        stamp_row(a, m->current_step, m->cal);
-        a[6] = m->cal.month_idx;
-    };
-    if (record && row0 == 0) m->steps_accepted.assign(7 * static_cast<size_t>(rows + 1), 0);
-    note_accepted(0);
-    bool launched = false, device_failed = false;  // a launch of this call went out / a device call of it failed
-    auto check_launch = [&](hipError_t e, const char *feature) {  // what a launch of a step returned; feature: "" or "<label>: "
-        if (e == hipSuccess) return;
-        (void)hipGetLastError();
-        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + feature + hipGetErrorString(e));
-        device_failed = true;
-    };
-    const int tl_check = 1;  // the check looks at time level 2 (do_single_step checks the state the step has just produced)
-    const long long samples0 = m->stats.samples;  // (statistics: every round takes the same samples)
-    const long long tape0 = m->tape.ring.taken;        // (... and writes the same slots of the tape, for its own members)
-    const long long spectra0 = m->spectra.ring.taken;  // (... and of the spectra)
-    const long long enstape0 = m->enstape.ring.taken;  // (... and folds its members into the same slots of the ensemble tape)
-    // the accumulation tape: the open window's first step and the windows closed are put back for every round, whose members
-    // accumulate into their own part of the accumulators and close into their own part of the same slots
+    // where every recorder stands when the segment begins
+    sg.nudged0 = m->nudge.applied;
+    sg.stats = SampleCursor(m->stats.samples);
+    sg.tape = SampleCursor(m->tape.ring.taken);
+    sg.spectra = SampleCursor(m->spectra.ring.taken);
+    sg.enstape = SampleCursor(m->enstape.ring.taken);
+    sg.projtape = SampleCursor(m->projtape.ring.taken);
     spd_model::AccTape &ac = m->acctape;
     if (ac.on && (ac.window_start < 0 || ac.window_start > m->current_step)) ac.window_start = m->current_step;
-    const long long acctape0 = ac.ring.taken;
-    const int acc_start0 = ac.window_start;
-    // the window tape: the open window (its first step, its samples so far) and the windows closed, put back for every round likewise
+    sg.acctape = SampleCursor(ac.ring.taken);
     spd_model::WinTape &wt = m->wintape;
     if (wt.on && (wt.window_start < 0 || wt.window_start > m->current_step)) {
         wt.window_start = m->current_step;
         wt.samples = 0;
     }
-    const long long wintape0 = wt.ring.taken;
-    const WinOpen win_open0{wt.window_start, wt.samples};
-    const WinSchedule win_schedule{wt.window, wt.every, wt.sample_every};
-    const long long projtape0 = m->projtape.ring.taken;  // (the projection tape: every round writes the same slots, for its own members)
-    // the ensemble tape's last sample of this call: a sample whose slot a later sample of the SAME call takes again is not folded at
-    // all -- nobody can read it, and with rounds its members would otherwise land in the partials of the sample that replaced it
-    long long enstape_last = enstape0;
-    if (m->enstape.on)
-        enstape_last += (static_cast<long long>(m->current_step) + nsteps) / m->enstape.every - m->current_step / m->enstape.every;
-    for (int round = 0, round_first = 0; round < rounds && rc == SPD_OK; ++round) {
-        long long taken = 0, tape_taken = 0, spectra_taken = 0, enstape_taken = 0, acctape_taken = 0;
-        int acc_start = acc_start0;
-        long long wintape_taken = 0, projtape_taken = 0;
-        WinOpen win_open = win_open0;
-        const int round_count = m->M / rounds + (round < m->M % rounds ? 1 : 0);
-        if (round > 0) {  // the same steps again, for the next members
-            m->cal = start.cal;
-            m->current_step = start.current_step;
-            m->phi_cur = start.phi_cur;
-            m->surf_cache_valid = start.surf_cache_valid;
-            m->phi_ahead = start.phi_ahead;
-            m->sppt_first = start.sppt_first;
-            m->sppt_step = start.sppt_step;
-            m->air_absortivity_co2 = start.co2;
+    sg.wintape = SampleCursor(wt.ring.taken);
+    sg.open0 = OpenWindows{ac.window_start, WinOpen{wt.window_start, wt.samples}};
+    return SPD_OK;
+}
+
+// What step `it` of a round does, decided once on the host for all member groups.
+struct StepPlan {
+    bool new_day;
+    ZonalDevice zd;  // (new_day) the day's zonal forcing
+    int sw, diag, fresh;
+    long long stats_n, tape_n, spectra_n, enstape_n, projtape_n;  // the sample a recorder takes behind this step; 0: it is not due
+    bool fold_enstape, acc_close, run_geo;
+    int acc_step, acc_slot;  // the accumulation tape reads the diagnostics-only outputs of EVERY step: number acc_step of its window
+    // the window tape: what this step does to the open window (sample number win_k of it, 0: none; win_n samples at a close)
+    WinDecision win;
+    WinOpen win_after;
+    int32_t win_row[8];
+    int win_k, win_n, win_slot;
+    TauPlan tau;
+    Calendar next;  // the date after the step
+    TimeInterp w;
+};
+
+// (a refused step leaves sg.rc set, and nothing of it goes out)
+static StepPlan decide_step(Segment &sg, int round, int it) {
+    spd_model *m = sg.m;
+    const spd_model::AccTape &ac = m->acctape;
+    const spd_model::WinTape &wt = m->wintape;
+    const int c = m->current_step;
+    StepPlan p{};
+    p.new_day = c % 36 == 0;
+    if (p.new_day) p.zd = forcing_host(m, 1);
+    p.sw = (c % 3 == 0) ? 1 : 0;
+    // a step whose state the statistics sample: its diagnostics-only outputs are stored when precnv / precls are sampled
+    if (m->stats.on && due_after(c, m->stats.every)) p.stats_n = sg.stats.next();
+    if (m->tape.on && due_after(c, m->tape.every)) p.tape_n = sg.tape.next();
+    // (the spectra read the spectral state only: they never ask for the diagnostics-only outputs)
+    if (m->spectra.on && due_after(c, m->spectra.every)) p.spectra_n = sg.spectra.next();
+    if (m->enstape.on && due_after(c, m->enstape.every)) {
+        p.enstape_n = sg.enstape.next();
+        p.fold_enstape = enstape_folds(p.enstape_n, sg.enstape.base, sg.c0, sg.nsteps, m->enstape.every, m->enstape.ring.capacity);
+    }
+    // (round 0 opens the sample: its slot holds no member yet, in any of its partials)
+    if (p.fold_enstape && round == 0) {
+        int *held = m->enstape.counts.data() + kEnsTapeGroups * static_cast<size_t>(m->enstape.ring.slot(p.enstape_n));
+        std::fill(held, held + kEnsTapeGroups, 0);
+    }
+    p.acc_step = c + 1 - sg.open.acc_start;
+    p.acc_close = ac.on && due_after(c, ac.every);
+    if (ac.on) p.acc_slot = ac.ring.slot(sg.acctape.open());
+    p.next = m->cal;
+    p.next.advance();
+    p.win_after = sg.open.win;
+    if (wt.on) p.win = wintape_advance(WinSchedule{wt.window, wt.every, wt.sample_every}, p.win_after, c + 1, p.next, p.win_row);
+    p.win_k = p.win.sample ? sg.open.win.samples + 1 : 0;
+    p.win_n = sg.open.win.samples + (p.win.sample ? 1 : 0);
+    if (p.win.sample || p.win.close) p.win_slot = wt.ring.slot(sg.wintape.open());
+    if (m->projtape.on && due_after(c, m->projtape.every)) p.projtape_n = sg.projtape.next();
+    p.diag = (m->diag_every_step || it == sg.nsteps - 1 || (p.stats_n && m->stats.precip) || (p.tape_n && m->tape.precip) ||
+              (p.fold_enstape && m->enstape.precip) || ac.on || (p.win.sample && wt.precip) || (p.projtape_n && m->projtape.precip)) ? 1 : 0;
+    // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
+    // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
+    // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
+    // It rides as tail blocks in the step's spectral_step_kernel launch (dynamics.hip; as a launch of its own the step
+    // was 2 ... 7 % slower).
+    p.w = time_interp(p.next);
+    p.fresh = (!m->surf_cache_valid || (p.next.hour == 0 && p.next.minute == 0)) ? 1 : 0;
+    if (!sst_anomaly_covered(m, p.w)) {
+        sg.rc = m_fail(SPD_E_ARG, kSstUncovered);
+        return p;
+    }
+    const bool tau_round = sg.tau_compact && (m->tau_recompute == 2 || sg.part.round_count(round) >= kTauFromMembers);
+    p.tau = tau_plan(tau_round, p.sw != 0, it, sg.nsteps, tau_first_sw(sg.c0), m->diag_every_step);
+    if (p.tau.store_record) sg.tau_co2 = m->air_absortivity_co2;
+    // (forcing_host changes the absorptivity on the first step of a day only, and that is a shortwave step)
+    else if (p.tau.compact) assert(m->air_absortivity_co2 == sg.tau_co2);
+    p.run_geo = begin_step_geopotential(m);
+    return p;
+}
+
+// The launches of step `it` for the members [first, first + count) of group g, on the group's stream: the step, nudging and the last
+// step's check, then the recorders one after the other, each behind the one before it.
+static void issue_group(Segment &sg, const StepPlan &p, int round, int it, int g, int first, int count) {
+    spd_model *m = sg.m;
+    const spd_model::Nudge &nd = m->nudge;
+    const spd_model::AccTape &ac = m->acctape;
+    hipStream_t s = sg.gs[g];
+    const bool record = sg.record, first_of_call = it == 0 && round == 0;
+    const double delt = 86400.0 / 36;
+    const int tl_check = 1;  // the check looks at time level 2 (do_single_step checks the state the step has just produced)
+    sg.launched = true;
+    if (p.new_day && (sg.rc = forcing_range(m, p.zd, first, count, s)) != SPD_OK) sg.device_failed = true;
+    CouplerArgs cpl{m->S, p.w, first, count, 1 + (m->current_step + 1) / 36, m->land_coupling_flag, m->sst_anomaly_flag, m->anom_planes,
+                    p.fresh};
+    if (sg.rc == SPD_OK) {
+        hipError_t e = hipSuccess;
+        if (sg.offset && first_of_call && g == 1) e = hipStreamWaitEvent(s, m->ev_offset, 0);
+        if (sg.rim && it == 0 && e == hipSuccess)  // arm the flags of this group's members, on its stream
+            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_rim + first), 1, static_cast<size_t>(count), s);
+        // (the check of the step before this one, for these members: written to that step's row)
+        const CheckArgs chk{m->P.vor, m->P.div, m->P.t, tl_check, record && it > 0 ? m->h_steps_err + static_cast<size_t>(sg.row0 + it - 1) * m->M : nullptr,
+                            nullptr, m->steps_ticket, first};
+        if (e == hipSuccess)
+            e = step_range(m, 2, 2, 2 * delt, p.sw, first, count, p.diag, p.run_geo, &cpl, s,
+                           (sg.offset && first_of_call && g == 0) ? m->ev_offset : nullptr, record && it > 0 ? &chk : nullptr,
+                           sg.rim ? (it == 0 ? kRimDetect : kRimSkip) : kRimPlain, p.tau);
+        sg.check_launch(e, "");
+    }
+    if (sg.rc == SPD_OK && nd.loops()) {  // directly behind the step, on the group's stream: every check and sample sees the nudged state
+        const NudgeAt at = nudge_at(nd.stamps, m->current_step + 1);
+        sg.check_launch(run_nudge(nd.planes, nd.nplanes, nd.mask, first, count, at.s0, at.s1, at.a, s), "nudging: ");
+    }
+    if (sg.rc == SPD_OK && record && it == sg.nsteps - 1) {  // the last step's check: nothing comes behind it to carry it
+        sg.check_launch(run_diagnostics_range(m->P, m->ctx->dev, first, count, tl_check, m->h_steps_err + static_cast<size_t>(sg.row0 + it) * m->M,
+                                              nullptr, m->steps_ticket, s), "");
+        ++m->checks_alone;
+    }
+    if (sg.rc == SPD_OK && p.stats_n)  // behind this group's last launch of the step, on its stream
+        sg.check_launch(stats_sample(m, first, count, p.stats_n, s), "time statistics: ");
+    if (sg.rc == SPD_OK && p.tape_n)  // behind the statistics' sample, on the same stream
+        sg.check_launch(tape_sample(m, first, count, p.tape_n, s), "tape: ");
+    if (sg.rc == SPD_OK && p.spectra_n)  // behind the tape's sample, on the same stream
+        sg.check_launch(spectra_sample(m, first, count, p.spectra_n, s), "spectra: ");
+    if (sg.rc == SPD_OK && p.fold_enstape)  // behind the spectra's sample, on the same stream: partial g of the slot
+        sg.check_launch(enstape_sample(m, first, count, p.enstape_n, g, s), "ensemble tape: ");
+    if (sg.rc == SPD_OK && ac.on)  // behind the ensemble tape's sample, on the same stream, on every step
+        sg.check_launch(run_acctape_step(ac.planes, ac.nplanes, first, count, p.acc_step, p.acc_close ? 1 : 0, p.acc_slot, m->stored32 ? 1 : 0,
+                                         ac.dtype == SPD_TAPE_F64 ? 1 : 0, s),
+                        "accumulation tape: ");
+    if (sg.rc == SPD_OK && (p.win.sample || p.win.close))  // behind the accumulation tape's launch, on the same stream
+        sg.check_launch(wintape_step(m, first, count, p.win_k, p.win.close ? 1 : 0, p.win_n, p.win_slot, s), "window tape: ");
+    if (sg.rc == SPD_OK && p.projtape_n)  // behind the window tape's launch, on the same stream
+        sg.check_launch(projtape_sample(m, first, count, p.projtape_n, s), "projection tape: ");
+}
+
+// The host side after a step that went out for every group of the round: every round moves the model's counter and date and its own
+// cursors and open windows; what a host can read afterwards is written by the first round only (ring.hpp: SampleCursor::commit).
+static void commit_step(Segment &sg, const StepPlan &p, bool first_round, int it) {
+    spd_model *m = sg.m;
+    sppt_advance(m);
+    m->current_step += 1;
+    m->cal = p.next;
+    m->surf_cache_valid = true;
+    if (first_round) sg.note_accepted(it + 1);
+    if (first_round && m->nudge.loops()) m->nudge.applied = sg.nudged0 + it + 1;
+    if (first_round && p.stats_n) m->stats.samples = sg.stats.last();
+    // the sample's step and the date of the sampled state, kept beside its slot
+    if (p.tape_n) sg.tape.commit(m->tape.ring, first_round, m->current_step, p.next);
+    if (p.spectra_n) sg.spectra.commit(m->spectra.ring, first_round, m->current_step, p.next);
+    if (p.enstape_n) sg.enstape.commit(m->enstape.ring, first_round, m->current_step, p.next);
+    if (p.projtape_n) sg.projtape.commit(m->projtape.ring, first_round, m->current_step, p.next);
+    if (p.acc_close) {  // the window is closed and the next one starts at the step counter as it stands now
+        spd_model::AccTape &ac = m->acctape;
+        sg.acctape.next();
+        sg.open.acc_start = m->current_step;
+        sg.acctape.commit(ac.ring, first_round, m->current_step, p.next);
+        if (first_round) ac.window_start = sg.open.acc_start;
+        if (first_round) ac.ring.row(ac.ring.taken)[6] = p.acc_step;
+    }
+    spd_model::WinTape &wt = m->wintape;
+    sg.open.win = p.win_after;  // (the window tape's open window with this step's sample, or the next one after a close)
+    if (p.win.close) sg.wintape.next();
+    if (wt.on && first_round) {
+        wt.window_start = sg.open.win.start;
+        wt.samples = sg.open.win.samples;
+        if (p.win.close) {
+            sg.wintape.commit(wt.ring, true, m->current_step, p.next);
+            std::memcpy(wt.ring.row(wt.ring.taken), p.win_row, sizeof(p.win_row));
         }
-        const int base = round_count / G, extra = round_count % G;
-        const bool tau_round = tau_compact && (m->tau_recompute == 2 || round_count >= kTauFromMembers);
-        for (int it = 0; it < nsteps && rc == SPD_OK; ++it) {
-            const bool new_day = m->current_step % 36 == 0;
-            ZonalDevice zd{};
-            if (new_day) zd = forcing_host(m, 1);
-            const int sw = (m->current_step % 3 == 0) ? 1 : 0;
-            // a step whose state the statistics sample: its diagnostics-only outputs are stored when precnv / precls are sampled
-            const bool sample = m->stats.on && (m->current_step + 1) % m->stats.every == 0;
-            if (sample) ++taken;
-            const bool record_tape = m->tape.on && (m->current_step + 1) % m->tape.every == 0;
-            if (record_tape) ++tape_taken;
-            // (the spectra read the spectral state only: they never ask for the diagnostics-only outputs)
-            const bool record_spectra = m->spectra.on && (m->current_step + 1) % m->spectra.every == 0;
-            if (record_spectra) ++spectra_taken;
-            const bool record_enstape = m->enstape.on && (m->current_step + 1) % m->enstape.every == 0;
-            if (record_enstape) ++enstape_taken;
-            const bool fold_enstape = record_enstape && enstape0 + enstape_taken + m->enstape.ring.capacity > enstape_last;
-            // (round 0 opens the sample: its slot holds no member yet, in any of its partials)
-            if (fold_enstape && round == 0) {
-                int *held = m->enstape.counts.data() + kEnsTapeGroups * static_cast<size_t>(m->enstape.ring.slot(enstape0 + enstape_taken));
-                std::fill(held, held + kEnsTapeGroups, 0);
-            }
-            // the accumulation tape reads the diagnostics-only outputs of EVERY step; this step is number acc_step of its window
-            const int acc_step = m->current_step + 1 - acc_start;
-            const bool acc_close = ac.on && (m->current_step + 1) % ac.every == 0;
-            // the window tape: what this step does to the open window (sample number win_k of it, 0: none; win_n samples at a close)
-            Calendar next = m->cal;
-            next.advance();
-            WinDecision win{false, false};
-            WinOpen win_after = win_open;
-            int32_t win_row[8] = {};
-            if (wt.on) win = wintape_advance(win_schedule, win_after, m->current_step + 1, next, win_row);
-            const int win_k = win.sample ? win_open.samples + 1 : 0, win_n = win_open.samples + (win.sample ? 1 : 0);
-            const bool record_projtape = m->projtape.on && (m->current_step + 1) % m->projtape.every == 0;
-            if (record_projtape) ++projtape_taken;
-            const int diag = (m->diag_every_step || it == nsteps - 1 || (sample && m->stats.precip) || (record_tape && m->tape.precip) ||
-                              (fold_enstape && m->enstape.precip) || ac.on || (win.sample && wt.precip) ||
-                              (record_projtape && m->projtape.precip)) ? 1 : 0;
-            // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
-            // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
-            // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
-            // It rides as tail blocks in the step's spectral_step_kernel launch (dynamics.hip; as a launch of its own the step
-            // was 2 ... 7 % slower).
-            const TimeInterp w = time_interp(next);
-            const int fresh = (!m->surf_cache_valid || (next.hour == 0 && next.minute == 0)) ? 1 : 0;
-            if (m->sst_anomaly_flag && (w.a0 < 0 || w.a1 < 0 || w.a0 >= m->anom_planes || w.a1 >= m->anom_planes)) {
-                rc = m_fail(SPD_E_ARG, "SST anomaly planes do not cover the simulated period (speedy.py:338-372)");
-                break;
-            }
-            TauPlan tau;
-            if (tau_round && sw && it != nsteps - 1) {
-                tau.compact = tau.store_record = true;
-                tau.store_array = it + 3 > nsteps - 1 || m->diag_every_step;
-                tau_co2 = m->air_absortivity_co2;
-            } else if (tau_round && !sw && it > tau_first_sw) {
-                tau.compact = true;
-                // (forcing_host changes the absorptivity on the first step of a day only, and that is a shortwave step)
-                assert(m->air_absortivity_co2 == tau_co2);
-            }
-            const bool run_geo = begin_step_geopotential(m);
-            const bool first_of_call = it == 0 && round == 0;
-            for (int g = 0, first = round_first; g < G && rc == SPD_OK; ++g) {
-                const int count = base + (g < extra ? 1 : 0);
+    }
+}
+
+// do_single_step (speedy.f90:20-74) `nsteps` times for all members.  Nothing synchronises; the range check of
+// diagnostics.f90 is available separately through spd_model_check (the reference runs it after every step).
+// record: the range check of every step is left in m->h_steps_err[step][member] (spd_model_step_checked_begin) -- the check of step
+// k rides in the spectral -> grid launch of step k + 1 of the same members, the last one is a launch of its own behind the call.
+// One segment of a call: `nsteps` steps for all members, all rounds and member groups, forked from and joined into the caller's
+// stream.  A call without in-loop breeding is one segment (row0 = 0, rows = nsteps); with it, step_impl issues the segments between
+// the rescale steps, and the rows of a checked call (h_steps_err, steps_accepted) of this segment start at row0 of the call's `rows`.
+static int step_segment(spd_model *m, int nsteps, void *stream, bool record, const char *who, int row0, int rows) {
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (int rc = usable(m, who)) return rc;
+    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized (error code -1 of the reference)");
+    if (!m->dyn) return m_fail(SPD_E_ARG, std::string(who) + ": call spd_model_set_time_step first");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it with spd_model_step_checked_end first");
+    if (m->nudge.loops() && m->nudge.in_use == 0)
+        return m_fail(SPD_E_ARG, std::string(who) + ": in-loop nudging is configured but no target slot is in use (spd_model_nudge_set_times)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Segment sg{m, nsteps, record, who, row0};
+    sg.part = partition_members(m->M, m->nchunks, m->block_members, nsteps, m->split_dyn_physics || m->profile > 0);
+    const int G = sg.part.G;
+    // a range check that was put off rides in the first spectral -> grid launch of this call -- when that is ONE launch over all
+    // members on the stream the check was put off on; otherwise it goes out on its own first
+    if (m->deferred.active && (G > 1 || s != m->deferred.stream || record))
+        if (int rc = settle_deferred_check(m)) return rc;
+    if (int rc = plan_segment(sg)) return rc;
+    // The caller's stream orders the whole call: the group streams start after everything already enqueued on it, and it continues
+    // after all of them.
+    sg.gs[0] = s;
+    if (G > 1) {
+        if (int rc = ensure_group_streams(m, G)) return rc;
+        M_HIP(hipEventRecord(m->ev_start, s));
+        for (int g = 0; g < G; ++g) {
+            sg.gs[g] = m->cstream[g];
+            M_HIP(hipStreamWaitEvent(sg.gs[g], m->ev_start, 0));
+        }
+    }
+    // whatever way this function is left, the caller's stream continues behind everything the group streams were given
+    struct Join {
+        hipStream_t s, *gs;
+        hipEvent_t *ev;
+        int G;
+        ~Join() {
+            if (G > 1)
+                for (int g = 0; g < G; ++g)
+                    if (hipEventRecord(ev[g], gs[g]) == hipSuccess) (void)hipStreamWaitEvent(s, ev[g], 0);
+        }
+    } join{s, sg.gs, m->cev, G};
+    // Two groups that start together stay together: they have the same work, so both run their transform launches at the same
+    // time and their column launches at the same time, and only the tails overlap.  The second group therefore starts when the
+    // first has issued three quarters of its first step (behind its grid -> spectral launch): from then on one group's
+    // latency-bound transforms run beside the other's streaming column / spectral kernels.  Measured at 64 members: 0.241 ms
+    // per step every time, against 0.243 ... 0.250 when left to chance (profiles/r03_member_groups.txt); 96 members -2.8 %;
+    // nothing at 32 / 48 members or with 3 groups.  It costs a call the time its first and last three quarters of a step run
+    // alone; applied to calls of at least kOffsetFrom steps (in 20-step calls it measured 0 ... +1.5 %; in the 36-step calls of
+    // a time loop with daily hooks -1.8 %: 9.58 -> 9.41 ms per simulated day, round 6; 72 until then).
+    constexpr int kOffsetFrom = 36;
+    sg.offset = G == 2 && nsteps >= kOffsetFrom;
+    if (sg.offset && !m->ev_offset) M_HIP(hipEventCreateWithFlags(&m->ev_offset, hipEventDisableTiming));
+    if (record && row0 == 0) m->steps_accepted.assign(7 * static_cast<size_t>(rows + 1), 0);
+    sg.note_accepted(0);
+    for (int round = 0, round_first = 0; round < sg.part.rounds && sg.rc == SPD_OK; ++round) {
+        const int round_count = sg.part.round_count(round);
+        if (round > 0) host_state(m) = sg.start;  // the same steps again, for the next members
+        sg.rewind();
+        for (int it = 0; it < nsteps && sg.rc == SPD_OK; ++it) {
+            const StepPlan p = decide_step(sg, round, it);
+            for (int g = 0, first = round_first; g < G && sg.rc == SPD_OK; ++g) {
+                const int count = sg.part.group_count(round_count, g);
                 if (count == 0) continue;
-                launched = true;
-                if (new_day) {
-                    rc = forcing_range(m, zd, first, count, gs[g]);
-                    device_failed = device_failed || rc != SPD_OK;
-                }
-                CouplerArgs cpl{m->S, w, first, count, 1 + (m->current_step + 1) / 36, m->land_coupling_flag, m->sst_anomaly_flag,
-                                m->anom_planes, fresh};
-                if (rc == SPD_OK) {
-                    hipError_t e = hipSuccess;
-                    if (offset && first_of_call && g == 1) e = hipStreamWaitEvent(gs[1], m->ev_offset, 0);
-                    if (rim && it == 0 && e == hipSuccess)  // arm the flags of this group's members, on its stream
-                        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_rim + first), 1, static_cast<size_t>(count), gs[g]);
-                    // (the check of the step before this one, for these members: written to that step's row)
-                    const CheckArgs chk{m->P.vor, m->P.div, m->P.t, tl_check, record && it > 0 ? m->h_steps_err + static_cast<size_t>(row0 + it - 1) * m->M : nullptr,
-                                        nullptr, m->steps_ticket, first};
-                    if (e == hipSuccess)
-                        e = step_range(m, 2, 2, 2 * delt, sw, first, count, diag, run_geo, &cpl, gs[g],
-                                       (offset && first_of_call && g == 0) ? m->ev_offset : nullptr, record && it > 0 ? &chk : nullptr,
-                                       rim ? (it == 0 ? kRimDetect : kRimSkip) : kRimPlain, tau);
-                    check_launch(e, "");
-                }
-                if (rc == SPD_OK && nudge) {  // directly behind the step, on the group's stream: every check and sample sees the nudged state
-                    const NudgeAt at = nudge_at(nd.stamps, m->current_step + 1);
-                    check_launch(run_nudge(nd.planes, nd.nplanes, nd.mask, first, count, at.s0, at.s1, at.a, gs[g]), "nudging: ");
-                }
-                if (rc == SPD_OK && record && it == nsteps - 1) {  // the last step's check: nothing comes behind it to carry it
-                    const hipError_t e = run_diagnostics_range(m->P, m->ctx->dev, first, count, tl_check,
-                                                               m->h_steps_err + static_cast<size_t>(row0 + it) * m->M, nullptr, m->steps_ticket, gs[g]);
-                    if (e != hipSuccess) {
-                        rc = m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-                        device_failed = true;
-                    }
-                    ++m->checks_alone;
-                }
-                if (rc == SPD_OK && sample) {  // behind this group's last launch of the step, on its stream
-                    check_launch(stats_sample(m, first, count, samples0 + taken, gs[g]), "time statistics: ");
-                }
-                if (rc == SPD_OK && record_tape) {  // behind the statistics' sample, on the same stream
-                    check_launch(tape_sample(m, first, count, tape0 + tape_taken, gs[g]), "tape: ");
-                }
-                if (rc == SPD_OK && record_spectra) {  // behind the tape's sample, on the same stream
-                    check_launch(spectra_sample(m, first, count, spectra0 + spectra_taken, gs[g]), "spectra: ");
-                }
-                if (rc == SPD_OK && fold_enstape) {  // behind the spectra's sample, on the same stream: partial g of the slot
-                    check_launch(enstape_sample(m, first, count, enstape0 + enstape_taken, g, gs[g]), "ensemble tape: ");
-                }
-                if (rc == SPD_OK && ac.on) {  // behind the ensemble tape's sample, on the same stream, on every step
-                    check_launch(run_acctape_step(ac.planes, ac.nplanes, first, count, acc_step, acc_close ? 1 : 0,
-                                                  ac.ring.slot(acctape0 + acctape_taken + 1), m->stored32 ? 1 : 0,
-                                                  ac.dtype == SPD_TAPE_F64 ? 1 : 0, gs[g]),
-                                 "accumulation tape: ");
-                }
-                if (rc == SPD_OK && (win.sample || win.close)) {  // behind the accumulation tape's launch, on the same stream
-                    check_launch(wintape_step(m, first, count, win_k, win.close ? 1 : 0, win_n, wt.ring.slot(wintape0 + wintape_taken + 1), gs[g]),
-                                 "window tape: ");
-                }
-                if (rc == SPD_OK && record_projtape) {  // behind the window tape's launch, on the same stream
-                    check_launch(projtape_sample(m, first, count, projtape0 + projtape_taken, gs[g]), "projection tape: ");
-                }
+                issue_group(sg, p, round, it, g, first, count);
                 first += count;
             }
-            if (rc != SPD_OK) break;
-            sppt_advance(m);
-            m->current_step += 1;
-            m->cal = next;
-            m->surf_cache_valid = true;
-            if (round == 0) note_accepted(it + 1);
-            if (round == 0 && nudge) m->nudge.applied = nudged0 + it + 1;
-            if (round == 0 && sample) m->stats.samples = samples0 + taken;
-            if (round == 0 && record_tape) {  // the sample's step and the date of the sampled state, kept beside its slot
-                m->tape.ring.taken = tape0 + tape_taken;
-                m->tape.ring.stamp(m->tape.ring.taken, m->current_step, next);
-            }
-            if (round == 0 && record_spectra) {  // (the same for the spectra)
-                m->spectra.ring.taken = spectra0 + spectra_taken;
-                m->spectra.ring.stamp(m->spectra.ring.taken, m->current_step, next);
-            }
-            if (round == 0 && record_enstape) {  // (... and for the ensemble tape)
-                m->enstape.ring.taken = enstape0 + enstape_taken;
-                m->enstape.ring.stamp(m->enstape.ring.taken, m->current_step, next);
-            }
-            if (round == 0 && record_projtape) {  // (... and for the projection tape)
-                m->projtape.ring.taken = projtape0 + projtape_taken;
-                m->projtape.ring.stamp(m->projtape.ring.taken, m->current_step, next);
-            }
-            if (acc_close) {  // the window is closed and the next one starts at the step counter as it stands now
-                ++acctape_taken;
-                acc_start = m->current_step;
-                if (round == 0) {
-                    ac.ring.taken = acctape0 + acctape_taken;
-                    ac.window_start = acc_start;
-                    ac.ring.stamp(ac.ring.taken, m->current_step, next);
-                    ac.ring.row(ac.ring.taken)[6] = acc_step;
-                }
-            }
-            win_open = win_after;  // (the window tape's open window with this step's sample, or the next one after a close)
-            if (win.close) ++wintape_taken;
-            if (wt.on && round == 0) {
-                wt.window_start = win_open.start;
-                wt.samples = win_open.samples;
-                if (win.close) {
-                    wt.ring.taken = wintape0 + wintape_taken;
-                    std::memcpy(wt.ring.row(wt.ring.taken), win_row, sizeof(win_row));
-                }
-            }
+            if (sg.rc == SPD_OK) commit_step(sg, p, round == 0, it);
         }
         round_first += round_count;
     }
@@ -1782,13 +1776,13 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
     // launches of a step write its work arrays one after the other) that the others -- and the host side of the model, whose step
     // counter and date only move with complete steps -- have not.  Whatever the plan (one group, several, rounds), the model is
     // unusable until spd_model_init has rebuilt its state; the message of the failure itself stays the call's error text.
-    if (rc != SPD_OK && launched && device_failed) {
+    if (sg.rc != SPD_OK && sg.launched && sg.device_failed) {
         const std::string text = spd_last_error();
         m->initialized = false;
         m->step_poison = "a device error interrupted a model step after some of its launches had gone out (" + text + ")";
-        (void)m_fail(rc, text);
+        (void)m_fail(sg.rc, text);
     }
-    return rc;
+    return sg.rc;
 }
 
 // A call of spd_model_step / spd_model_step_checked_begin.  Without in-loop breeding: one segment, the launches it always issued.
@@ -2008,7 +2002,7 @@ int spd_model_get_date(spd_model_handle m, int *ymdhm) {
 int spd_model_group_streams(spd_model_handle m, int32_t *created, int32_t *apart) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_group_streams: null model");
     int n = 0;
-    for (int g = 0; g < 4; ++g) n += m->cstream[g] ? 1 : 0;
+    for (int g = 0; g < kGroupStreams; ++g) n += m->cstream[g] ? 1 : 0;
     if (created) *created = n;
     if (apart) *apart = m->groups_apart ? 1 : 0;
     return SPD_OK;

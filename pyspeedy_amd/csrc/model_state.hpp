@@ -129,8 +129,8 @@ struct spd_model {
     // counter, geopotential buffer, SPPT counter, CO2) is rewound for every round.  0: off (PYSPEEDY_AMD_BLOCK_MEMBERS, option
     // "block_members").
     int block_members = 32;
-    hipStream_t cstream[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr}, ev_start = nullptr, ev_offset = nullptr;
+    hipStream_t cstream[kGroupStreams] = {};
+    hipEvent_t cev[kGroupStreams] = {}, ev_start = nullptr, ev_offset = nullptr;
     bool split_dyn_physics = false;  // PYSPEEDY_AMD_SPLIT_DYN=1: separate dynamics and physics launches (for measurements)
     // spd_model_set_physics_precision (BASELINE cfg 5): column physics arithmetic in fp32 AND fp32 storage of what only the
     // column physics reads back (RegEntry::f32: its time-level-1 inputs, the persisted radiation state, diagnostics-only outputs)

@@ -46,6 +46,24 @@ struct SampleRing {
     void clear() { taken = 0; }  // (the next sample goes into slot 0: no device work)
 };
 
+// A recorder's sample number through the rounds of a segment of the step loop: every round issues the same samples, counted on from
+// what the recorder had taken when the segment began, and only the first round writes the host side.
+struct SampleCursor {
+    long long base = 0, count = 0;  // samples taken at the segment's start; samples of the current round
+    SampleCursor() = default;
+    explicit SampleCursor(long long taken) : base(taken) {}
+    void rewind() { count = 0; }                   // (a new round)
+    long long next() { return base + ++count; }    // the number of the sample to issue
+    long long last() const { return base + count; }
+    long long open() const { return base + count + 1; }  // (recorders of windows: the number the open window will close under)
+    // the sample last issued has been taken at step counter `step` and date `at`: the ring counts it and keeps its row
+    void commit(SampleRing &ring, bool first_round, int step, const Calendar &at) const {
+        if (!first_round) return;
+        ring.taken = last();
+        ring.stamp(ring.taken, step, at);
+    }
+};
+
 // A member that fails the range check inside a checked call leaves samples behind it that were taken from a state the model does
 // not accept: the recorder refuses to be read until it is reset.
 struct Validity {

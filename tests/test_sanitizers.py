@@ -1,6 +1,7 @@
 """CPU tier: sanitizer builds of the host-side C++ of the product and of the CPU oracle, each run through a program that
 exercises its entry points (tests/sanitize/).
-* AddressSanitizer + UndefinedBehaviorSanitizer: tables.cpp, surface_host.cpp, the oracle (oracle/orc_*.c);
+* AddressSanitizer + UndefinedBehaviorSanitizer: tables.cpp, surface_host.cpp, the oracle (oracle/orc_*.c), and the step loop's
+  host-side schedule (step_plan.hpp, ring.hpp) against brute-force restatements;
 * AddressSanitizer + UndefinedBehaviorSanitizer (with leak detection) AND ThreadSanitizer: the outer boundary's host logic,
   csrc/driver.cpp -- containers, placement, gathering / splitting, the kept plan, pending-step tokens and their error paths --
   built unchanged against a stub of driver_backend.hpp and of the spd_model_* functions (tests/sanitize/driver_stub.cpp): four
@@ -30,6 +31,14 @@ def test_host_tables_and_surface_preprocessing_under_asan_ubsan(tmp_path):
     run(["g++", "-std=c++17", "-ffp-contract=off", *SAN, "-I" + csrc, os.path.join(ROOT, "tests", "sanitize", "host_sanitize.cpp"),
          os.path.join(csrc, "tables.cpp"), os.path.join(csrc, "surface_host.cpp"), "-o", "host_sanitize"], tmp_path)
     assert "host sanitize ok" in run([str(tmp_path / "host_sanitize")], tmp_path)
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_step_plan_and_sample_cursor_under_asan_ubsan(tmp_path):
+    csrc = os.path.join(ROOT, "pyspeedy_amd", "csrc")
+    run(["g++", "-std=c++17", "-ffp-contract=off", *SAN, "-I" + csrc, os.path.join(ROOT, "tests", "sanitize", "step_plan_sanitize.cpp"),
+         os.path.join(csrc, "tables.cpp"), os.path.join(csrc, "surface_host.cpp"), "-o", "step_plan_sanitize"], tmp_path)
+    assert "step plan sanitize ok" in run([str(tmp_path / "step_plan_sanitize")], tmp_path)
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not available")

@@ -15,6 +15,7 @@
 
 #include "assim.hpp"
 #include "assim_weights.hpp"
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "tables.hpp"
 
@@ -28,16 +29,6 @@ constexpr int kChunks = (NSPEC + kW - 1) / kW;
 constexpr int kLmax = TRUNC + 1;  // the largest total wavenumber that takes part
 constexpr int kLD = kAssimMax;    // the leading dimension of W in device memory
 constexpr int kLDS = kAssimMax + 1;  // ... and in the LDS: a lane per row reads W[k][i] for 64 k at once without a bank conflict
-
-typedef double double2v __attribute__((ext_vector_type(2)));
-
-// Pointers that come out of the descriptor table are generic to the compiler; they are device-memory addresses.
-__device__ __forceinline__ double2v load_global(const double *p) {
-    return *(const __attribute__((address_space(1))) double2v *)p;
-}
-__device__ __forceinline__ void store_global(double *p, double2v v) {
-    *(__attribute__((address_space(1))) double2v *)p = v;
-}
 
 // The observations of one event, by value: yo[e] (NaN: missing) and the error variances.
 struct AssimObs {
@@ -84,7 +75,7 @@ __global__ __launch_bounds__(kXT) void assim_transform_kernel(const AssimPlane *
     const AssimPlane d = planes[blockIdx.y >> 1];
     double *base = d.state + (blockIdx.y & 1) * d.level_stride + 2 * k;
     if (inside)
-        for (int i = wave; i < r; i += kXT / kW) xs[i * kW + lane] = load_global(base + members[i] * d.member_stride);
+        for (int i = wave; i < r; i += kXT / kW) xs[i * kW + lane] = load_pair(base + members[i] * d.member_stride);
     __syncthreads();
     if (!inside) return;
     for (int j0 = kJ * wave; j0 < r; j0 += kJ * (kXT / kW)) {  // (a column at or beyond r is formed from zeros of W and stored nowhere)
@@ -102,7 +93,7 @@ __global__ __launch_bounds__(kXT) void assim_transform_kernel(const AssimPlane *
         }
 #pragma unroll
         for (int b = 0; b < kJ; ++b)
-            if (j0 + b < r) store_global(base + members[j0 + b] * d.member_stride, acc[b]);
+            if (j0 + b < r) store_pair(base + members[j0 + b] * d.member_stride, acc[b]);
     }
 }
 }  // namespace
@@ -344,17 +335,15 @@ int spd_model_assim_configure(spd_model_handle m, const double *weights, int n_p
     next.member_list = carve.take<int>(mbytes);
     next.xplanes = carve.take<AssimPlane>(xbytes);
     hipError_t e = hipMemset(p, 0, total);
-    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
-    if (e == hipSuccess) e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<SampleSource> sources;  // (per plane of plan.vars, in their order)
+    if (e == hipSuccess) e = build_sample_front(m, plan, next, sources);
     std::vector<ProjTapePlane> host_planes;
     std::vector<ProjTapeItem> host_items;
     for (size_t q = 0; q < distinct.size(); ++q) {
         const int id = distinct[q].first, level = distinct[q].second;
         const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
         ProjTapePlane d{};
-        d.slab_plane = slab_plane[var->first_plane + static_cast<size_t>(level)];
-        d.src = nullptr;  // (precnv / precls are refused: every plane comes from the slab)
-        d.unit = kStatsCatalogue[id].unit;
+        d.source = sources[var->first_plane + static_cast<size_t>(level)];  // (precnv / precls are refused: every plane comes from the slab)
         d.first = static_cast<int>(host_items.size());
         for (size_t k = 0; k < E; ++k)
             if (plane_of[k] == static_cast<int>(q)) host_items.push_back({entries[k].pattern, static_cast<int>(k)});

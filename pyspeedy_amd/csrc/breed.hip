@@ -22,6 +22,7 @@
 
 #include "breed.hpp"
 #include "breed_factor.hpp"
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "tables.hpp"
 
@@ -31,16 +32,6 @@ namespace {
 constexpr int kT = 256;
 constexpr int kBlocks = (NSPEC + kT - 1) / kT;  // 4 blocks (or 4 coefficients a lane) over the 992 coefficients
 constexpr int kLmax = TRUNC + 1;                // the largest total wavenumber that takes part
-
-typedef double double2v __attribute__((ext_vector_type(2)));
-
-// Pointers that come out of the descriptor table are generic to the compiler; they are device-memory addresses.
-__device__ __forceinline__ double2v load_global(const double *p) {
-    return *(const __attribute__((address_space(1))) double2v *)p;
-}
-__device__ __forceinline__ void store_global(double *p, double2v v) {
-    *(__attribute__((address_space(1))) double2v *)p = v;
-}
 
 // blockIdx.x: plane, blockIdx.y: bred member
 __global__ __launch_bounds__(kT) void breed_norm_kernel(const BreedPlane *__restrict__ planes, const BreedPair *__restrict__ pairs,
@@ -56,7 +47,7 @@ __global__ __launch_bounds__(kT) void breed_norm_kernel(const BreedPlane *__rest
         if (k >= NSPEC) break;
         const int n = k / MX, m = k - n * MX, l = m + n;
         if (l > kLmax) continue;
-        const double2v p = load_global(xp + 2 * k), c = load_global(xc + 2 * k);
+        const double2v p = load_pair(xp + 2 * k), c = load_pair(xc + 2 * k);
         const double dx = __dsub_rn(p.x, c.x), dy = __dsub_rn(p.y, c.y);
         double q = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
         if (m != 0) q = __dmul_rn(2.0, q);
@@ -105,14 +96,14 @@ __global__ __launch_bounds__(kT) void breed_rescale_kernel(const BreedPlane *__r
     const BreedPlane d = planes[blockIdx.y];
     double *p0 = d.state + pr.member * d.member_stride + 2 * k, *p1 = p0 + d.level_stride;
     const double *c0 = d.state + pr.control * d.member_stride + 2 * k, *c1 = c0 + d.level_stride;
-    const double2v xc = load_global(c0), yc = load_global(c1);
-    double2v x = load_global(p0), y = load_global(p1);
+    const double2v xc = load_pair(c0), yc = load_pair(c1);
+    double2v x = load_pair(p0), y = load_pair(p1);
     x.x = __dadd_rn(xc.x, __dmul_rn(s, __dsub_rn(x.x, xc.x)));
     x.y = __dadd_rn(xc.y, __dmul_rn(s, __dsub_rn(x.y, xc.y)));
     y.x = __dadd_rn(yc.x, __dmul_rn(s, __dsub_rn(y.x, yc.x)));
     y.y = __dadd_rn(yc.y, __dmul_rn(s, __dsub_rn(y.y, yc.y)));
-    store_global(p0, x);
-    store_global(p1, y);
+    store_pair(p0, x);
+    store_pair(p1, y);
 }
 
 // a lane per member
@@ -165,12 +156,12 @@ __global__ __launch_bounds__(kT) void breed_gram_kernel(const BreedPlane *__rest
         if (k >= NSPEC) break;
         const int n = k / MX, m = k - n * MX, l = m + n;
         if (l > kLmax) continue;
-        const double2v c = load_global(xc + 2 * k);
+        const double2v c = load_pair(xc + 2 * k);
         const double e = elm2[MX * l];
         double2v di[kTile], dj[kTile];
 #pragma unroll
         for (int a = 0; a < kTile; ++a) {
-            const double2v p = load_global(row[a] + 2 * k), q = load_global(col[a] + 2 * k);
+            const double2v p = load_pair(row[a] + 2 * k), q = load_pair(col[a] + 2 * k);
             di[a].x = __dsub_rn(p.x, c.x), di[a].y = __dsub_rn(p.y, c.y);
             dj[a].x = __dsub_rn(q.x, c.x), dj[a].y = __dsub_rn(q.y, c.y);
         }
@@ -266,9 +257,9 @@ __global__ __launch_bounds__(kW) void breed_transform_kernel(const BreedPlane *_
     const BreedFamily fam = fams[blockIdx.z];
     const BreedPlane d = planes[blockIdx.y >> 1];
     double *base = d.state + (blockIdx.y & 1) * d.level_stride + 2 * k;
-    const double2v xc = load_global(base + fam.control * d.member_stride);
+    const double2v xc = load_pair(base + fam.control * d.member_stride);
     for (int i = 0; i < rk; ++i) {
-        const double2v x = load_global(base + members[fam.first + i] * d.member_stride);
+        const double2v x = load_pair(base + members[fam.first + i] * d.member_stride);
         double2v v;
         v.x = __dsub_rn(x.x, xc.x), v.y = __dsub_rn(x.y, xc.y);
         delta[i][threadIdx.x] = v;
@@ -302,7 +293,7 @@ __global__ __launch_bounds__(kW) void breed_transform_kernel(const BreedPlane *_
             if (j0 + b < rk) {
                 double2v x;
                 x.x = __dadd_rn(xc.x, acc[b].x), x.y = __dadd_rn(xc.y, acc[b].y);
-                store_global(base + members[fam.first + j0 + b] * d.member_stride, x);
+                store_pair(base + members[fam.first + j0 + b] * d.member_stride, x);
             }
     }
 }

@@ -12,7 +12,7 @@
 #include <cmath>
 
 #include "enstape.hpp"
-#include "export_unit.hpp"
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "tables.hpp"
 
@@ -28,33 +28,6 @@ static_assert(NG % 2 == 0 && kPairs % kT == 0, "a plane is a whole number of blo
 // the default plan at 64 members (32 members) is four round trips.
 constexpr int kBatch = 8;
 
-typedef double double2v __attribute__((ext_vector_type(2)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-
-// Pointers that come out of the descriptor table are generic to the compiler (flat loads and stores); they are device-memory
-// addresses, and saying so gives the global forms (as tape.hip).
-template <typename T>
-__device__ __forceinline__ T stream_load_global(const T *p) {
-    return __builtin_nontemporal_load((const __attribute__((address_space(1))) T *)p);
-}
-template <typename T>
-__device__ __forceinline__ T load_global(const T *p) {
-    return *(const __attribute__((address_space(1))) T *)p;
-}
-template <typename T>
-__device__ __forceinline__ void store_global(T *p, T v) {
-    *(__attribute__((address_space(1))) T *)p = v;
-}
-
-__device__ __forceinline__ double2v member_value(const double *p) { return stream_load_global(reinterpret_cast<const double2v *>(p)); }
-__device__ __forceinline__ double2v member_value(const float *p) {
-    const float2v f = stream_load_global(reinterpret_cast<const float2v *>(p));
-    double2v x;
-    x.x = static_cast<double>(f.x);
-    x.y = static_cast<double>(f.y);
-    return x;
-}
-
 // The walk: members j = 0 ... count - 1 at base + j * stride, kBatch loads ahead of the first update.  A batch past the last member
 // loads that member again instead of branching around the load (a branch per load would wait for each one on its own).
 template <typename T>
@@ -64,7 +37,7 @@ __device__ __forceinline__ void fold_members(const T *base, long stride, int cou
 #pragma unroll
         for (int b = 0; b < kBatch; ++b) {
             const int j = j0 + b < count ? j0 + b : count - 1;
-            x[b] = member_value(base + j * stride);
+            x[b] = widen(stream_load_pair(base + j * stride));
         }
 #pragma unroll
         for (int b = 0; b < kBatch; ++b) {
@@ -91,19 +64,15 @@ __global__ __launch_bounds__(kT) void enstape_fold_kernel(const EnsTapePlane *__
     const long at = static_cast<long>(partial) * nplanes * NG + p;
     double2v mean = {0.0, 0.0}, m2 = {0.0, 0.0};
     if (n0 > 0) {  // (the first members of a sample's partial: nothing of it is read -- a lap over the ring needs no device work)
-        mean = load_global(reinterpret_cast<const double2v *>(d.mean + at));
-        m2 = load_global(reinterpret_cast<const double2v *>(d.m2 + at));
+        mean = load_pair(d.mean + at);
+        m2 = load_pair(d.m2 + at);
     }
-    if (d.slab_plane >= 0)
-        fold_members(slab + (static_cast<long>(first) * slab_fields + d.slab_plane) * NG + p, static_cast<long>(slab_fields) * NG, count,
-                     d.unit, n0, mean, m2);
-    else if (store32)
-        fold_members(static_cast<const float *>(d.src) + static_cast<long>(first) * NG + p, static_cast<long>(NG), count, d.unit, n0, mean, m2);
-    else
-        fold_members(static_cast<const double *>(d.src) + static_cast<long>(first) * NG + p, static_cast<long>(NG), count, d.unit, n0, mean, m2);
+    with_sample_plane(d.source, slab, slab_fields, store32, first, [=](auto plane, long stride, double2v &mean, double2v &m2) {
+        fold_members(plane + p, stride, count, d.source.unit, n0, mean, m2);
+    }, mean, m2);
     // (plain stores: a later round of the same sample reads the partial back, and so does the read)
-    store_global(reinterpret_cast<double2v *>(d.mean + at), mean);
-    store_global(reinterpret_cast<double2v *>(d.m2 + at), m2);
+    store_pair(d.mean + at, mean);
+    store_pair(d.m2 + at, m2);
 }
 
 // blockIdx.x: pairs of points of the variable's planes, blockIdx.y: sample of this launch
@@ -241,15 +210,13 @@ int spd_model_enstape_configure(spd_model_handle m, const char *const *names, in
     next.m2 = carve.take<double>(ring);
     carve_front(carve, plan, next);
     next.planes = carve.take<EnsTapePlane>(desc);
-    std::vector<int> slab_plane;
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<SampleSource> sources;
+    hipError_t e = build_sample_front(m, plan, next, sources);
     std::vector<EnsTapePlane> host_planes;
     for (const auto &v : next.vars)
         for (int k = 0; k < v.levels; ++k) {
             EnsTapePlane d{};
-            d.slab_plane = slab_plane[host_planes.size()];
-            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.unit = kStatsCatalogue[v.id].unit;
+            d.source = sources[host_planes.size()];
             d.mean = next.mean + (v.first_plane + static_cast<size_t>(k)) * NG;
             d.m2 = next.m2 + (v.first_plane + static_cast<size_t>(k)) * NG;
             host_planes.push_back(d);

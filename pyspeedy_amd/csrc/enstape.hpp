@@ -13,6 +13,7 @@
 
 #include <cstddef>
 
+#include "sample_source.hpp"
 #include "step_plan.hpp"
 
 struct spd_model;
@@ -24,10 +25,8 @@ constexpr int kEnsTapeReadSamples = 64;   // samples of one launch of the read k
 
 // One plane (a level of a variable), as the fold kernel sees it.
 struct EnsTapePlane {
-    const void *src;  // physics output of member 0 (slab_plane < 0: precnv / precls); unused otherwise
-    int slab_plane;   // plane index inside a member's slab entries (-1: read `src` directly)
-    int unit;         // export_unit's code (export_unit.hpp), as TapePlane::unit
-    double *mean;     // the plane's mean in partial (slot 0, group 0); partial (slot, g) lies (slot * 4 + g) * nplanes * 4608 further
+    SampleSource source;  // where the sample's value lies, and its unit
+    double *mean;    // the plane's mean in partial (slot 0, group 0); partial (slot, g) lies (slot * 4 + g) * nplanes * 4608 further
     double *m2;       // ... and its M2
 };
 

@@ -368,9 +368,9 @@ void plan_sample(const spd_model *m, const std::vector<int> &ids, spd_model::Sam
 
 // front.slab and front.table[] point into the caller's allocation: uploads the export descriptors of spd_model_spectral2grid
 // (build_tables) with the slab as destination, for the chosen variables, and sets up the pressure-level kernel of a sample (from
-// the slab's transformed planes into its further planes).  slab_plane: per plane of plan.vars, in their order, the slab plane the
-// value is read from (-1: precnv / precls, read where the column kernel stores them).
-hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_model::SampleFront &front, std::vector<int> &slab_plane) {
+// the slab's transformed planes into its further planes).  sources: per plane of plan.vars, in their order, the slab plane the
+// value is read from (-1: precnv / precls, read at `src`, where the column kernel stores them) and the catalogue's unit.
+hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_model::SampleFront &front, std::vector<SampleSource> &sources) {
     const size_t M = static_cast<size_t>(m->M);
     const ModelPtrs &P = m->P;
     auto spec = [](double *base, size_t field) { return base + field * NSPEC * C; };
@@ -432,23 +432,25 @@ hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_mo
         a.n = m->plev.n;
         std::copy(m->plev.lnp, m->plev.lnp + kPlevMaxLevels, a.lnp);
     }
-    slab_plane.clear();
+    sources.clear();
     for (const auto &v : plan.vars)
         for (int k = 0; k < v.levels; ++k) {
-            if (cat_kind(v.id) == CAT_XF) slab_plane.push_back(plan.xf_at[xf_source(v.id)] + k);
+            SampleSource d{nullptr, -1, kStatsCatalogue[v.id].unit};
+            if (cat_kind(v.id) == CAT_XF) d.slab_plane = plan.xf_at[xf_source(v.id)] + k;
             else if (cat_kind(v.id) == CAT_PLEV) {
                 if (k == 0) {
                     front.plev.out[v.id - kPlevFirst] = front.slab + static_cast<size_t>(plev_plane) * NG;
                     front.plev.out_stride[v.id - kPlevFirst] = static_cast<long>(front.slab_fields) * NG;
                 }
-                slab_plane.push_back(plev_plane++);
+                d.slab_plane = plev_plane++;
             } else if (cat_kind(v.id) == CAT_DERIVE) {
                 if (k == 0) {
                     front.derive.out[v.id - kDeriveFirst] = front.slab + static_cast<size_t>(plev_plane) * NG;
                     front.derive.out_stride[v.id - kDeriveFirst] = static_cast<long>(front.slab_fields) * NG;
                 }
-                slab_plane.push_back(plev_plane++);
-            } else slab_plane.push_back(-1);
+                d.slab_plane = plev_plane++;
+            } else d.src = m->reg.at(kStatsCatalogue[v.id].name).ptr;  // CAT_PRECIP: the column kernel's output of that name, in the registry
+            sources.push_back(d);
         }
     hipError_t e = hipSuccess;
     if (front.xf_fields > 0) {

@@ -602,9 +602,9 @@ struct SamplePlan {
 int sample_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids);
 // the variables `ids` of the model's M members: which planes the slab holds and how large slab and tables are
 void plan_sample(const spd_model *m, const std::vector<int> &ids, spd_model::SampleFront &front, SamplePlan &plan);
-// uploads the descriptor tables of a front end whose slab and tables point into the caller's allocation; slab_plane: per plane of
-// plan.vars, the slab plane its value is read from (-1: precnv / precls)
-hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_model::SampleFront &front, std::vector<int> &slab_plane);
+// uploads the descriptor tables of a front end whose slab and tables point into the caller's allocation; sources: per plane of
+// plan.vars, where its value is read from and its unit (sample_source.hpp)
+hipError_t build_sample_front(const spd_model *m, const SamplePlan &plan, spd_model::SampleFront &front, std::vector<SampleSource> &sources);
 // the launches of a front end for the members [first, first + count) on `s`
 hipError_t sample_front(spd_model *m, const spd_model::SampleFront &f, int first, int count, hipStream_t s);
 // slab | tables[2] of a front end

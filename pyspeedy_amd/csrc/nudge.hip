@@ -15,6 +15,7 @@
 // the device holds no schedule.
 #include <hip/hip_runtime.h>
 
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "nudge.hpp"
 #include "tables.hpp"
@@ -25,16 +26,6 @@ namespace {
 constexpr int kT = 256;
 constexpr int kBlocks = (NSPEC + kT - 1) / kT;  // 4 blocks over the 992 coefficients; the last one is partial
 constexpr int kLmax = TRUNC + 1;                // the largest total wavenumber that is nudged
-
-typedef double double2v __attribute__((ext_vector_type(2)));
-
-// Pointers that come out of the descriptor table are generic to the compiler; they are device-memory addresses.
-__device__ __forceinline__ double2v load_global(const double *p) {
-    return *(const __attribute__((address_space(1))) double2v *)p;
-}
-__device__ __forceinline__ void store_global(double *p, double2v v) {
-    *(__attribute__((address_space(1))) double2v *)p = v;
-}
 
 // blockIdx.x: coefficients, blockIdx.y: plane (descriptor), blockIdx.z: member of the group
 __global__ __launch_bounds__(kT) void nudge_kernel(const NudgePlane *__restrict__ planes, const int *__restrict__ mask, int first,
@@ -47,21 +38,21 @@ __global__ __launch_bounds__(kT) void nudge_kernel(const NudgePlane *__restrict_
     const int n = k / MX, l = k - n * MX + n;
     if (l > kLmax) return;
     const NudgePlane d = planes[blockIdx.y];
-    const double g = *(const __attribute__((address_space(1))) double *)(d.gain + l);
-    double2v t = load_global(d.target + s0 * d.slot_stride + 2 * k);
+    const double g = load_global(d.gain + l);
+    double2v t = load_pair(d.target + s0 * d.slot_stride + 2 * k);
     if (s1 != s0) {
-        const double2v t1 = load_global(d.target + s1 * d.slot_stride + 2 * k);
+        const double2v t1 = load_pair(d.target + s1 * d.slot_stride + 2 * k);
         t.x = __dadd_rn(t.x, __dmul_rn(a, __dsub_rn(t1.x, t.x)));
         t.y = __dadd_rn(t.y, __dmul_rn(a, __dsub_rn(t1.y, t.y)));
     }
     double *x0 = d.state + i * d.member_stride + 2 * k, *x1 = x0 + d.level_stride;
-    double2v u = load_global(x0), v = load_global(x1);
+    double2v u = load_pair(x0), v = load_pair(x1);
     u.x = __dadd_rn(u.x, __dmul_rn(g, __dsub_rn(t.x, u.x)));
     u.y = __dadd_rn(u.y, __dmul_rn(g, __dsub_rn(t.y, u.y)));
     v.x = __dadd_rn(v.x, __dmul_rn(g, __dsub_rn(t.x, v.x)));
     v.y = __dadd_rn(v.y, __dmul_rn(g, __dsub_rn(t.y, v.y)));
-    store_global(x0, u);
-    store_global(x1, v);
+    store_pair(x0, u);
+    store_pair(x1, v);
 }
 }  // namespace
 

@@ -2,7 +2,7 @@
 // scalar series (spd_model_projtape_*, include/pyspeedy_amd.h; the definition is in projtape.hpp and DESIGN section 4j).
 //
 // A sample is what an fp64 tape of the same name holds: model.hip runs the tape's front end into a slab of the recorder's own, and
-// the kernel below applies export_unit (export_unit.hpp) exactly as tape_store_kernel does; precnv / precls are read where the
+// the kernel below applies export_unit (sample_source.hpp) exactly as tape_store_kernel does; precnv / precls are read where the
 // column kernel stores them, in their stored precision, widened.  One 256-lane workgroup per (member, distinct plane among the
 // entries): it loads its plane once, 18 values per lane at p = t + 256 r (every load of a wavefront is 512 contiguous bytes), and
 // then serves every entry on that plane -- four at a time: each lane forms the lane sums of four patterns side by side, each in
@@ -16,7 +16,7 @@
 // read by the host's gather only.
 #include <hip/hip_runtime.h>
 
-#include "export_unit.hpp"
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "projtape.hpp"
 #include "tables.hpp"
@@ -30,10 +30,6 @@ constexpr int kBatch = 4;      // entries per barrier: one per wavefront of the 
 static_assert(NG % kT == 0, "a plane is a whole number of passes of the workgroup");
 static_assert(kBatch * 64 == kT, "one wavefront per entry of a batch");
 
-// Pointers that come out of the descriptor table are generic to the compiler (flat loads); they are device-memory addresses.
-__device__ __forceinline__ double load_global(const double *p) { return *(const __attribute__((address_space(1))) double *)p; }
-__device__ __forceinline__ float load_global(const float *p) { return *(const __attribute__((address_space(1))) float *)p; }
-
 // blockIdx.x: distinct plane (descriptor), blockIdx.y: member of the group
 __global__ __launch_bounds__(kT) void projtape_kernel(const ProjTapePlane *__restrict__ planes, const ProjTapeItem *__restrict__ items,
                                                       const double *__restrict__ weights, const double *__restrict__ slab, int slab_fields,
@@ -44,18 +40,20 @@ __global__ __launch_bounds__(kT) void projtape_kernel(const ProjTapePlane *__res
     const int t = threadIdx.x;
     const long i = first + static_cast<long>(blockIdx.y);
     double x[kPer];
-    if (d.slab_plane >= 0) {
-        const double *src = slab + (i * slab_fields + d.slab_plane) * NG;
+    // with_sample_plane's decision (sample_source.hpp), written out: with the unrolled loop behind a function boundary of any kind
+    // the compiler forms the 18 values in another order and commutes the operands of the first products below
+    if (d.source.slab_plane >= 0) {
+        const double *src = slab + (i * slab_fields + d.source.slab_plane) * NG;
 #pragma unroll
-        for (int r = 0; r < kPer; ++r) x[r] = export_unit(src[t + kT * r], d.unit);
+        for (int r = 0; r < kPer; ++r) x[r] = export_unit(load_global(src + t + kT * r), d.source.unit);
     } else if (store32) {
-        const float *src = static_cast<const float *>(d.src) + i * NG;
+        const float *src = static_cast<const float *>(d.source.src) + i * NG;
 #pragma unroll
-        for (int r = 0; r < kPer; ++r) x[r] = export_unit(static_cast<double>(load_global(src + t + kT * r)), d.unit);
+        for (int r = 0; r < kPer; ++r) x[r] = export_unit(static_cast<double>(load_global(src + t + kT * r)), d.source.unit);
     } else {
-        const double *src = static_cast<const double *>(d.src) + i * NG;
+        const double *src = static_cast<const double *>(d.source.src) + i * NG;
 #pragma unroll
-        for (int r = 0; r < kPer; ++r) x[r] = export_unit(load_global(src + t + kT * r), d.unit);
+        for (int r = 0; r < kPer; ++r) x[r] = export_unit(load_global(src + t + kT * r), d.source.unit);
     }
     const int wave = t >> 6, lane = t & 63;
     for (int e0 = 0; e0 < d.count; e0 += kBatch) {
@@ -213,17 +211,15 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
     carve_front(carve, plan, next);
     next.planes = carve.take<ProjTapePlane>(desc);
     next.items = carve.take<ProjTapeItem>(list);
-    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<SampleSource> sources;  // (per plane of plan.vars, in their order)
+    hipError_t e = build_sample_front(m, plan, next, sources);
     std::vector<ProjTapePlane> host_planes;
     std::vector<ProjTapeItem> host_items;
     for (size_t q = 0; q < distinct.size(); ++q) {
         const int id = distinct[q].first, level = distinct[q].second;
         const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
         ProjTapePlane d{};
-        d.slab_plane = slab_plane[var->first_plane + static_cast<size_t>(level)];
-        d.src = id == 6 ? static_cast<const void *>(m->pa.precnv) : id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-        d.unit = kStatsCatalogue[id].unit;
+        d.source = sources[var->first_plane + static_cast<size_t>(level)];
         d.first = static_cast<int>(host_items.size());
         for (size_t k = 0; k < E; ++k)
             if (plane_of[k] == static_cast<int>(q)) host_items.push_back({entries[k].pattern, static_cast<int>(k)});

@@ -13,16 +13,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "sample_source.hpp"
+
 struct spd_model;
 
 namespace spd {
 
 // One distinct plane (a level of a name) among the entries, as the kernel sees it.
 struct ProjTapePlane {
-    const void *src;  // physics output of member 0 (slab_plane < 0: precnv / precls, float while the model stores fp32)
-    int slab_plane;   // plane inside a member's slab entries (-1: read `src` directly)
-    int unit;         // 0 as it is, 1 q (kg/kg), 2 phi (m), 3 ps (Pa) -- export_unit.hpp, as TapePlane::unit
-    int first, count; // its entries: items [first, first + count) of the list below
+    SampleSource source;  // where the sample's value lies, and its unit
+    int first, count;     // its entries: items [first, first + count) of the list below
 };
 
 // One entry, in the list sorted by plane: the pattern it projects onto and its column in a member's row of the ring.

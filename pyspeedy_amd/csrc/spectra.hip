@@ -16,6 +16,7 @@
 // a group fall on the 16 different 4-bank slots of the bank row: the walk is free of conflicts with the row left at 31 elements.
 #include <hip/hip_runtime.h>
 
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "spectra.hpp"
 #include "tables.hpp"
@@ -28,8 +29,6 @@ constexpr int kLevelSlots = KX + 1;  // blockIdx.x: the eight levels, then ln ps
 constexpr double kRootHalf = 0.70710678118654752440;
 static_assert(kSpectraBins == NX && kT == 4 * kSpectraBins, "a lane per bin, 32 lanes per quantity");
 static_assert(4 * NSPEC * 16 <= 64 * 1024, "the four planes of a level fit the static LDS limit");
-
-typedef double double2v __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void stage(double2v *lds, const double *__restrict__ plane) {
     const double2v *src = reinterpret_cast<const double2v *>(plane);

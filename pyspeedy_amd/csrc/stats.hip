@@ -10,7 +10,6 @@
 
 #include <cmath>
 
-#include "export_unit.hpp"
 #include "model_state.hpp"
 #include "stats.hpp"
 #include "tables.hpp"
@@ -27,14 +26,8 @@ __global__ __launch_bounds__(kT) void stats_accumulate_kernel(const StatsPlane *
     if (p >= NG) return;
     const StatsPlane d = planes[blockIdx.y];
     const long i = first + static_cast<long>(blockIdx.z);
-    double x;
-    if (d.slab_plane >= 0)
-        x = slab[(i * slab_fields + d.slab_plane) * NG + p];
-    else if (store32)
-        x = static_cast<double>(static_cast<const float *>(d.src)[i * NG + p]);
-    else
-        x = static_cast<const double *>(d.src)[i * NG + p];
-    x = export_unit(x, d.unit);
+    double x = with_sample_plane(d.source, slab, slab_fields, store32, i, [&](auto plane, long) { return static_cast<double>(plane[p]); });
+    x = export_unit(x, d.source.unit);
     double *mean = d.mean + i * d.member_stride + p;
     double *m2 = d.m2 ? d.m2 + i * d.member_stride + p : nullptr;
     if (n == 1) {  // the first sample of a period: nothing is read (reset needs no device work)
@@ -147,15 +140,13 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     if (next.variance) next.m2 = carve.take<double>(acc);
     carve_front(carve, plan, next);
     next.planes = carve.take<StatsPlane>(desc);
-    std::vector<int> slab_plane;
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<SampleSource> sources;
+    hipError_t e = build_sample_front(m, plan, next, sources);
     std::vector<StatsPlane> host_planes;
     for (const auto &v : next.vars)
         for (int k = 0; k < v.levels; ++k) {
             StatsPlane d{};
-            d.slab_plane = slab_plane[host_planes.size()];
-            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.unit = kStatsCatalogue[v.id].unit;
+            d.source = sources[host_planes.size()];
             d.mean = next.mean + v.offset + static_cast<size_t>(k) * NG;
             d.m2 = next.variance ? next.m2 + v.offset + static_cast<size_t>(k) * NG : nullptr;
             d.member_stride = static_cast<long>(v.levels) * NG;

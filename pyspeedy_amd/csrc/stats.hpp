@@ -5,15 +5,15 @@
 
 #include <cstddef>
 
+#include "sample_source.hpp"
+
 struct spd_model;
 
 namespace spd {
 
 // One plane (a level of a variable) of every member, as the accumulate kernel sees it.
 struct StatsPlane {
-    const void *src;       // sample slab: the plane of member 0 (slab_plane >= 0); otherwise the physics output of member 0
-    int slab_plane;        // plane index inside a member's slab entries (-1: read `src` directly: precnv / precls)
-    int unit;              // 0 as transformed, 1 q (kg/kg), 2 phi (m), 3 ps (Pa) -- export_units_kernel's constants
+    SampleSource source;   // where the sample's value lies, and its unit
     double *mean, *m2;     // accumulators of member 0 at this plane (m2: nullptr without variance)
     long member_stride;    // doubles between two members in mean / m2 (levels * 4608)
 };

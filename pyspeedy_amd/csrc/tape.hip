@@ -1,16 +1,16 @@
 // Time series of grid-space fields recorded on the GPU inside multi-step calls (spd_model_tape_*, include/pyspeedy_amd.h).
 //
 // A sample is what the statistics sample (stats.hip): model.hip runs the same front end -- vort2vel, the export descriptors with a
-// slab of the tape's own as destination, the pressure-level kernel with raw = 1 -- and the store kernel below applies the export
-// units with export_units_kernel's fp32 literals, exactly as stats_accumulate_kernel does, and writes the value into the ring
-// instead of folding it into a mean.  precnv / precls are read where the column kernel stores them, in their stored precision.
+// slab of the tape's own as destination, the pressure-level kernel with raw = 1 -- and the store kernel below finds the value and
+// applies the export units through the same two functions as stats_accumulate_kernel (sample_source.hpp: precnv / precls are read
+// where the column kernel stores them, in their stored precision) and writes it into the ring instead of folding it into a mean.
 // Streaming kernels: every value is read once and written once and nothing on the device reads the ring until the host asks, so
 // loads and stores carry the non-temporal hint.  Two points (16 bytes of fp64) per lane, coalesced over the 4608 points of a plane.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
-#include "export_unit.hpp"
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "stream_store.hpp"
 #include "tables.hpp"
@@ -23,24 +23,6 @@ constexpr int kT = 256;
 constexpr int kPairs = NG / 2;  // 2304 = 9 blocks of 256 lanes: no partial block
 static_assert(NG % 2 == 0 && kPairs % kT == 0, "a plane is a whole number of blocks of point pairs");
 
-typedef double double2v __attribute__((ext_vector_type(2)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
-template <typename T> struct Pair;
-template <> struct Pair<double> { using type = double2v; };
-template <> struct Pair<float> { using type = float2v; };
-
-// Pointers that come out of the descriptor table are generic to the compiler (flat loads and stores); they are device-memory
-// addresses, and saying so gives the global forms.
-template <typename T>
-__device__ __forceinline__ T stream_load_global(const T *p) {
-    return __builtin_nontemporal_load((const __attribute__((address_space(1))) T *)p);
-}
-template <typename T>
-__device__ __forceinline__ void stream_store_global(T *p, T v) {
-    __builtin_nontemporal_store(v, (__attribute__((address_space(1))) T *)p);
-}
-
 // blockIdx.x: pairs of points, blockIdx.y: plane, blockIdx.z: member of the group
 template <typename T>
 __global__ __launch_bounds__(kT) void tape_store_kernel(const TapePlane *__restrict__ planes, const double *__restrict__ slab, int slab_fields,
@@ -50,19 +32,11 @@ __global__ __launch_bounds__(kT) void tape_store_kernel(const TapePlane *__restr
     if (p >= NG) return;
     const TapePlane d = planes[blockIdx.y];
     const long i = first + static_cast<long>(blockIdx.z);
-    double2v x;
-    if (d.slab_plane >= 0) {
-        x = stream_load(reinterpret_cast<const double2v *>(slab + (i * slab_fields + d.slab_plane) * NG + p));
-    } else if (store32) {
-        const float2v f = stream_load_global(reinterpret_cast<const float2v *>(static_cast<const float *>(d.src) + i * NG + p));
-        x.x = static_cast<double>(f.x);
-        x.y = static_cast<double>(f.y);
-    } else {
-        x = stream_load_global(reinterpret_cast<const double2v *>(static_cast<const double *>(d.src) + i * NG + p));
-    }
+    const double2v x = with_sample_plane(d.source, slab, slab_fields, store32, i,
+                                         [&](auto plane, long) { return widen(stream_load_pair(plane + p)); });
     T2 out;
-    out.x = static_cast<T>(export_unit(x.x, d.unit));
-    out.y = static_cast<T>(export_unit(x.y, d.unit));
+    out.x = static_cast<T>(export_unit(x.x, d.source.unit));
+    out.y = static_cast<T>(export_unit(x.y, d.source.unit));
     T *dst = static_cast<T *>(d.dst) + static_cast<long>(slot) * d.slot_stride + i * d.member_stride + p;
     stream_store_global(reinterpret_cast<T2 *>(dst), out);
 }
@@ -167,15 +141,13 @@ int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n
     next.data = carve.take<char>(ring);
     carve_front(carve, plan, next);
     next.planes = carve.take<TapePlane>(desc);
-    std::vector<int> slab_plane;
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<SampleSource> sources;
+    hipError_t e = build_sample_front(m, plan, next, sources);
     std::vector<TapePlane> host_planes;
     for (const auto &v : next.vars)
         for (int k = 0; k < v.levels; ++k) {
             TapePlane d{};
-            d.slab_plane = slab_plane[host_planes.size()];
-            d.src = v.id == 6 ? static_cast<const void *>(m->pa.precnv) : v.id == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.unit = kStatsCatalogue[v.id].unit;
+            d.source = sources[host_planes.size()];
             d.dst = static_cast<char *>(next.data) + (v.offset + static_cast<size_t>(k) * NG) * elem;
             d.member_stride = static_cast<long>(v.levels) * NG;
             d.slot_stride = static_cast<long>(M) * v.levels * NG;

@@ -6,15 +6,15 @@
 
 #include <cstddef>
 
+#include "sample_source.hpp"
+
 struct spd_model;
 
 namespace spd {
 
 // One plane (a level of a variable) of every member, as the store kernel sees it.
 struct TapePlane {
-    const void *src;     // physics output of member 0 (slab_plane < 0: precnv / precls); unused otherwise
-    int slab_plane;      // plane index inside a member's slab entries (-1: read `src` directly)
-    int unit;            // 0 as it is, 1 q (kg/kg), 2 phi (m), 3 ps (Pa) -- export_units_kernel's constants, as StatsPlane::unit
+    SampleSource source; // where the sample's value lies, and its unit
     void *dst;           // slot 0, member 0 of the variable at this plane (float or double: the tape's dtype)
     long member_stride;  // elements between two members of the variable (levels * 4608)
     long slot_stride;    // elements between two slots of the variable (M * levels * 4608)

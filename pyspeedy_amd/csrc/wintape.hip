@@ -2,7 +2,7 @@
 // steps of a multi-step call (spd_model_wintape_*, include/pyspeedy_amd.h).
 //
 // A sample is what an fp64 tape of the same name holds: model.hip runs the tape's front end into a slab of the recorder's own, and
-// the kernel below applies export_unit (export_unit.hpp) exactly as tape_store_kernel does; precnv / precls are read where the
+// the kernel below applies export_unit (sample_source.hpp) exactly as tape_store_kernel does; precnv / precls are read where the
 // column kernel stores them, in their stored precision, widened.  A wind-speed name is sqrt(u * u + v * v) of two such values in
 // four correctly rounded operations without contraction, so that a host restatement gives the same bits.  One launch per member
 // group serves every entry: a lane loads two points of one plane of one member once and updates whichever of sum, minimum, maximum
@@ -19,7 +19,7 @@
 
 #include <cmath>
 
-#include "export_unit.hpp"
+#include "global_mem.hpp"
 #include "model_state.hpp"
 #include "tables.hpp"
 #include "wintape.hpp"
@@ -30,44 +30,6 @@ namespace {
 constexpr int kT = 256;
 constexpr int kPairs = NG / 2;  // 2304 = 9 blocks of 256 lanes: no partial block
 static_assert(NG % 2 == 0 && kPairs % kT == 0, "a plane is a whole number of blocks of point pairs");
-
-typedef double double2v __attribute__((ext_vector_type(2)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-template <typename T> struct Pair;
-template <> struct Pair<double> { using type = double2v; };
-template <> struct Pair<float> { using type = float2v; };
-
-// Pointers that come out of the descriptor table are generic to the compiler (flat loads and stores); they are device-memory
-// addresses, and saying so gives the global forms.
-template <typename T>
-__device__ __forceinline__ void stream_store_global(T *p, T v) {
-    __builtin_nontemporal_store(v, (__attribute__((address_space(1))) T *)p);
-}
-__device__ __forceinline__ double2v load_global(const double *p) {
-    return *(const __attribute__((address_space(1))) double2v *)p;
-}
-__device__ __forceinline__ float2v load_global(const float *p) {
-    return *(const __attribute__((address_space(1))) float2v *)p;
-}
-__device__ __forceinline__ void store_global(double *p, double2v v) {
-    *(__attribute__((address_space(1))) double2v *)p = v;
-}
-
-template <typename T>
-__device__ __forceinline__ void ring_store(void *ring, long at, double2v v) {
-    using T2 = typename Pair<T>::type;
-    T2 out;
-    out.x = static_cast<T>(v.x);
-    out.y = static_cast<T>(v.y);
-    stream_store_global(reinterpret_cast<T2 *>(static_cast<T *>(ring) + at), out);
-}
-
-__device__ __forceinline__ double2v both(double v) {
-    double2v r;
-    r.x = v;
-    r.y = v;
-    return r;
-}
 
 // blockIdx.x: pairs of points, blockIdx.y: plane (descriptor), blockIdx.z: member of the group
 template <typename T>
@@ -80,19 +42,11 @@ __global__ __launch_bounds__(kT) void wintape_step_kernel(const WinTapePlane *__
     const long at = i * d.member_stride + p;
     double2v x = both(0.0);
     if (k > 0) {
-        if (d.slab_a >= 0) {
-            x = load_global(slab + (i * slab_fields + d.slab_a) * NG + p);
-        } else if (store32 && d.narrow) {
-            const float2v f = load_global(static_cast<const float *>(d.src) + i * NG + p);
-            x.x = static_cast<double>(f.x);
-            x.y = static_cast<double>(f.y);
-        } else {
-            x = load_global(static_cast<const double *>(d.src) + i * NG + p);
-        }
-        x.x = export_unit(x.x, d.unit);
-        x.y = export_unit(x.y, d.unit);
+        x = with_sample_plane(d.source, slab, slab_fields, store32 && d.narrow, i, [&](auto plane, long) { return widen(load_pair(plane + p)); });
+        x.x = export_unit(x.x, d.source.unit);
+        x.y = export_unit(x.y, d.source.unit);
         if (d.slab_b >= 0) {  // wind speed: u and v carry no unit conversion
-            const double2v v = load_global(slab + (i * slab_fields + d.slab_b) * NG + p);
+            const double2v v = load_pair(slab + (i * slab_fields + d.slab_b) * NG + p);
             x.x = __dsqrt_rn(__dadd_rn(__dmul_rn(x.x, x.x), __dmul_rn(v.x, v.x)));
             x.y = __dsqrt_rn(__dadd_rn(__dmul_rn(x.y, x.y), __dmul_rn(v.y, v.y)));
         }
@@ -105,13 +59,13 @@ __global__ __launch_bounds__(kT) void wintape_step_kernel(const WinTapePlane *__
     if (d.sum) {
         double2v acc = x;
         if (held) {
-            acc = load_global(d.sum + at);
+            acc = load_pair(d.sum + at);
             if (k > 0) {
                 acc.x = acc.x + x.x;
                 acc.y = acc.y + x.y;
             }
         }
-        if (keep) store_global(d.sum + at, acc);
+        if (keep) store_pair(d.sum + at, acc);
         if (close) {
             if (d.ring[0]) ring_store<T>(d.ring[0], ring_at, n > 0 ? acc : both(0.0));
             if (d.ring[1]) {
@@ -128,38 +82,38 @@ __global__ __launch_bounds__(kT) void wintape_step_kernel(const WinTapePlane *__
     if (d.mn) {
         double2v acc = x;
         if (held) {
-            acc = load_global(d.mn + at);
+            acc = load_pair(d.mn + at);
             if (k > 0) {
                 acc.x = x.x < acc.x ? x.x : acc.x;
                 acc.y = x.y < acc.y ? x.y : acc.y;
             }
         }
-        if (keep) store_global(d.mn + at, acc);
+        if (keep) store_pair(d.mn + at, acc);
         if (close) ring_store<T>(d.ring[2], ring_at, n > 0 ? acc : both(nan));
     }
     if (d.mx) {
         double2v acc = x;
         if (held) {
-            acc = load_global(d.mx + at);
+            acc = load_pair(d.mx + at);
             if (k > 0) {
                 acc.x = x.x > acc.x ? x.x : acc.x;
                 acc.y = x.y > acc.y ? x.y : acc.y;
             }
         }
-        if (keep) store_global(d.mx + at, acc);
+        if (keep) store_pair(d.mx + at, acc);
         if (close) ring_store<T>(d.ring[3], ring_at, n > 0 ? acc : both(nan));
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         if (!d.cnt[c]) continue;
         double2v acc = both(0.0);
-        if (held) acc = load_global(d.cnt[c] + at);
+        if (held) acc = load_pair(d.cnt[c] + at);
         if (k > 0) {
             const double t = d.thr[c];
             acc.x = acc.x + ((c == 0 ? x.x > t : x.x < t) ? 1.0 : 0.0);
             acc.y = acc.y + ((c == 0 ? x.y > t : x.y < t) ? 1.0 : 0.0);
         }
-        if (keep) store_global(d.cnt[c] + at, acc);
+        if (keep) store_pair(d.cnt[c] + at, acc);
         if (close) ring_store<T>(d.ring[4 + c], ring_at, acc);
     }
 }
@@ -368,8 +322,8 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
     double *acc_at = carve.take<double>(accs);
     carve_front(carve, plan, next);
     next.planes = carve.take<WinTapePlane>(desc);
-    std::vector<int> slab_plane;  // (per plane of plan.vars, in their order)
-    hipError_t e = build_sample_front(m, plan, next, slab_plane);
+    std::vector<SampleSource> sources;  // (per plane of plan.vars, in their order)
+    hipError_t e = build_sample_front(m, plan, next, sources);
     std::vector<WinTapePlane> host_planes;
     for (int v = 0; v < kWinNNames; ++v) {
         bool any = false;
@@ -384,11 +338,9 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
         const size_t plane_b = wspd ? plan_var(win_u_id(v) + 1).first_plane : 0;
         for (size_t k = 0; k < nlev; ++k) {
             WinTapePlane d{};
-            d.slab_a = slab_plane[plane_a + k];
-            d.slab_b = wspd ? slab_plane[plane_b + k] : -1;
-            d.src = v == 6 ? static_cast<const void *>(m->pa.precnv) : v == 7 ? static_cast<const void *>(m->pa.precls) : nullptr;
-            d.narrow = (v == 6 || v == 7) && m->reg[kStatsCatalogue[v].name].f32 ? 1 : 0;  // (what physics_storage32 keeps as float)
-            d.unit = wspd ? 0 : kStatsCatalogue[v].unit;
+            d.source = sources[plane_a + k];  // (a wind speed: its u, a slab plane of unit 0)
+            d.slab_b = wspd ? sources[plane_b + k].slab_plane : -1;
+            d.narrow = !wspd && cat_kind(v) == CAT_PRECIP && m->reg[kStatsCatalogue[v].name].f32 ? 1 : 0;  // (what physics_storage32 keeps as float)
             d.sum = acc[0] ? acc[0] + k * NG : nullptr;
             d.mn = acc[1] ? acc[1] + k * NG : nullptr;
             d.mx = acc[2] ? acc[2] + k * NG : nullptr;

@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "sample_source.hpp"
+
 struct spd_model;
 
 namespace spd {
@@ -17,10 +19,8 @@ struct Calendar;
 // One plane (a level of a name) of every member, as the accumulate kernel sees it.  Accumulator and ring pointers are those of
 // member 0 at this plane; a member lies member_stride elements further in the accumulators and in a ring slot alike.
 struct WinTapePlane {
-    const void *src;     // physics output of member 0 (slab_a < 0: precnv / precls; float when `narrow` and the model stores fp32)
-    int slab_a;          // plane inside a member's slab entries (-1: read `src` directly)
+    SampleSource source; // where the sample's value a lies, and its unit (`src` is float only when `narrow` as well)
     int slab_b;          // second slab plane of a wind-speed name (value = sqrt(a * a + b * b)), else -1
-    int unit;            // 0 as it is, 1 q (kg/kg), 2 phi (m), 3 ps (Pa) -- export_unit.hpp, as TapePlane::unit
     int narrow;          // 1: `src` is among the arrays physics_storage32 keeps as float
     double *sum;         // running sum (an entry asks for sum or mean), else null
     double *mn, *mx;     // running minimum / maximum, else null

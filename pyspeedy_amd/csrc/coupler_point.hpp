@@ -26,9 +26,14 @@ __device__ inline double forin5(const double *f12, size_t p, const TimeInterp &w
            w.w5[2] * f12[p + static_cast<size_t>(NGc) * w.m5[2]] + w.w5[3] * f12[p + static_cast<size_t>(NGc) * w.m5[3]] +
            w.w5[4] * f12[p + static_cast<size_t>(NGc) * w.m5[4]];
 }
+// What forint returns is copied as it is into snow_depth, soil_avail_water and (through the 0.5 clamp) sice_om / sice_am, which
+// a host reads back: product and sum are two statements, so that device code (-ffp-contract=on fuses inside ONE expression only)
+// rounds twice as interpolation.f90:40-58 does and these fields equal the reference's bit for bit.  Fused, soil_avail_water was
+// off by one ulp at 72 points and sice_am at 1 ... 28 (profiles/boundary_parity.txt).
 __device__ inline double forint(const double *f12, size_t p, const TimeInterp &w) {
     const double a = f12[p + static_cast<size_t>(NGc) * w.l0];
-    return a + w.wlin * (f12[p + static_cast<size_t>(NGc) * w.l1] - a);
+    const double d = w.wlin * (f12[p + static_cast<size_t>(NGc) * w.l1] - a);
+    return a + d;
 }
 }  // namespace cpl
 
@@ -80,7 +85,8 @@ __device__ __forceinline__ void coupler_point(const SurfacePtrs &S, int mem, int
         if (sst_anomaly) {
             const size_t oa = static_cast<size_t>(mem) * anom_planes * NG + p;
             const double a = S.sst_anom[oa + static_cast<size_t>(NG) * w.a0];
-            sstan_ob = a + w.wan * (S.sst_anom[oa + static_cast<size_t>(NG) * w.a1] - a);
+            const double da = w.wan * (S.sst_anom[oa + static_cast<size_t>(NG) * w.a1] - a);  // (two roundings, as forint: sstan_am is a copy)
+            sstan_ob = a + da;
             stream_store(&S.sstan_ob[o], sstan_ob);
         }
         if (sstcl > sstfr) {

@@ -962,6 +962,71 @@ int spd_model_assim_info(spd_model_handle m, int *r, int *n_entries, int *every,
                          long long *applied);
 int spd_assim_weights_host(const double *y, int n_entries, int r, const double *yo, const double *var, double inflation, double *w_out,
                            double *stats_out);
+/* The verification tape: bias, mean squared error, ensemble variance, CRPS and the rank histogram of a masked ensemble against a
+ * truth member of the SAME model (typically a nature run that the assimilation's mask leaves alone), by variable, level and
+ * region, recorded on the device at scheduled steps inside spd_model_step / spd_model_step_checked_begin calls of any length
+ * (in-loop mode) or once on the state as it stands (_apply).  It writes nothing into the model.  Off unless configured, and a model
+ * that never configures it issues the launches it always issued.
+ * Configuration.  mask[M] (int32, 0 or 1): the members with mask 1 are the ensemble a_1 < ... < a_r, 2 <= r <= 64.  truth: a
+ * member index with mask 0.  P weight maps, 1 <= P <= 64, fp64 [48][96], finite: the projection tape's layout and rules.  E
+ * entries (name, level, pattern), 1 <= E <= 256; name is any name the projection tape accepts (precnv and precls included); the
+ * *_plev names and mslp need spd_model_plev_configure first.  every >= 1; capacity >= 1 slots of the ring.
+ * Value.  x_j[p] and y[p], p = 96 row + column, are what an fp64 tape of that name holds at that level for member a_j and for the
+ * truth: the same front end (run over the member ranges that cover the mask and the truth), export units and stored precision of
+ * precnv / precls.
+ * Scores of a point, once per distinct (name, level), in fp64, every operation rounded on its own (no fused multiply-add):
+ *     s = x_1;  s = s + x_j (j = 2 ... r);  mean = s / r;  e = mean - y;  se = e e
+ *     a = (x_1 - mean)^2;  a = a + (x_j - mean)^2 (j = 2 ... r);  v = a / (r - 1)
+ *     b = |x_1 - y|;  b = b + |x_j - y| (j = 2 ... r)
+ *     c = 0;  c = c + |x_j - x_k| for j = 1 ... r - 1 (outer), k = j + 1 ... r (inner)
+ *     crps = b / r - c / (r r);  rank = #{j : x_j < y};  tie = 1 if some x_j == y
+ * An entry with the pattern w: bias, mse, variance, crps = the sums of w e, w se, w v, w crps over the 4608 points in exactly the
+ * projection tape's order (lane sums over 18 passes, then the tree); and 66 int32 counts over the points with w != 0:
+ * counts[k], k = 0 ... r, the points without a tie whose rank is k; counts[r + 1] the points with a tie; zero behind.
+ * Ring.  One slot per event: [2 phases][E][4] fp64 and [2][E][66] int32.  Phase 0 is the state as the event finds it.  Phase 1 is
+ * the state an in-loop analysis (spd_model_assim_*) left at the same step, front end and kernels run again; without one it reads
+ * NaN / -1.  The step counter, the date and the flag `analysis` of an event are kept on the host (_rows: 7 int32, oldest first).
+ * Schedule.  In-loop, after the step that leaves the absolute step counter at n with n % every == 0.  A call with in-loop
+ * verification is issued in segments that end at the multiples of the `every` of each looping joined consumer (breeding or
+ * assimilation, and verification); at such a step: the verification's phase 0 if due, the rescale or analysis if due, the
+ * verification's phase 1 if an analysis was applied.  It is bit for bit the host loop  step(k); _apply; step(k); ...  -- checked
+ * calls included --, and no state bit and no other recorder's ring differs from a run without it.
+ *   _configure  one hipMalloc of its own (synchronises the device); the ring is empty, `applied` 0.  SPD_E_ARG, before anything is
+ *               allocated, in this order: every < 1; capacity < 1; in_loop neither 0 nor 1; n_patterns outside 1 ... 64; n_entries
+ *               outside 1 ... 256; null weights; null lists; a weight that is not finite (pattern, point, row, column); per entry
+ *               an unknown name, a level or pattern out of range; a null mask; a null model; a checked call in flight; a mask
+ *               entry that is not 0 or 1; r outside 2 ... 64; truth outside 0 ... M - 1; truth inside the mask; a pressure-level
+ *               name without target levels.  SPD_E_DEVICE when the allocation fails: the tape is off, the model as usable as before.
+ *   spd_verif_check  the same checks without a model, for `members` members (mask may be NULL: only the rest is checked then).
+ *   _off        switches it off and frees everything.
+ *   _reset      empties the ring (no device work).  spd_model_init does the same.
+ *   _apply      one event (phase 0) on the state as it stands, stream-ordered; writes a ring slot and nothing else.
+ *   _compute    the scores [E][4] fp64 and counts [E][66] int32 of the state as it stands into device memory; writes no ring.  It
+ *               uses the configuration's slab and scratch: order it against _apply and the steps by the stream.
+ *   _read       the events [t0, t0 + nt) of the held ones, oldest first, as [nt][2][E][4] fp64 (bias, mse, variance, crps) into
+ *               device memory; _hist the same events as [nt][2][E][66] int32 (8-byte aligned).  Refused while a checked call is in
+ *               flight and after a failed range check of a checked call until _reset or spd_model_init.
+ *   _rows       rows[held][7] (host memory): step counter, year, month, day, hour, minute of the event's state, analysis (0 / 1).
+ *   _info       r, truth, E, every, capacity, events taken since _configure / _reset, the mode, and `applied`: the events recorded
+ *               since _configure; any pointer may be NULL; all zero and truth -1 without a configuration.
+ *   spd_verif_host  one entry as the device forms it, compiled for the host: x [r][4608], y [4608], w [4608] -> out4 = bias, mse,
+ *               variance, crps and hist66 as a ring slot's counts.
+ * spd_model_plev_configure is refused while an entry is a pressure-level name.  spd_model_copy_member does not carry the
+ * configuration, and the outer boundary (spd_parallel_step*) does not keep it. */
+int spd_verif_check(const double *weights, int n_patterns, const char *const *names, const int *levels, const int *patterns, int n_entries,
+                    const int32_t *mask, int members, int truth, int every, int capacity, int in_loop);
+int spd_model_verif_configure(spd_model_handle m, const double *weights, int n_patterns, const char *const *names, const int *levels,
+                              const int *patterns, int n_entries, const int32_t *mask, int truth, int every, int capacity, int in_loop);
+int spd_model_verif_off(spd_model_handle m);
+int spd_model_verif_reset(spd_model_handle m);
+int spd_model_verif_apply(spd_model_handle m, void *stream);
+int spd_model_verif_compute(spd_model_handle m, void *scores_device, size_t scores_bytes, void *hist_device, size_t hist_bytes, void *stream);
+int spd_model_verif_read(spd_model_handle m, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_verif_hist(spd_model_handle m, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_verif_rows(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_verif_info(spd_model_handle m, int *r, int *truth, int *n_entries, int *every, int *capacity, long long *taken, int *in_loop,
+                         long long *applied);
+int spd_verif_host(const double *x, int r, const double *y, const double *w, double *out4, int32_t *hist66);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

@@ -13,7 +13,8 @@
 !! window means, extremes and threshold counts of the state's fields (spd_model_wintape_*, spd_wintape_plan), and nudging of the
 !! spectral state toward target fields inside the device loop (spd_model_nudge_*), and breeding: the rescaling of member
 !! perturbations against their control runs inside the device loop (spd_model_breed_*, spd_breed_check), orthonormalised on request,
-!! and assimilation: an ensemble square-root filter inside the device loop (spd_model_assim_*, spd_assim_check)
+!! and assimilation: an ensemble square-root filter inside the device loop (spd_model_assim_*, spd_assim_check), and the
+!! verification tape: scores of an ensemble against a truth member inside the device loop (spd_model_verif_*, spd_verif_check)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -631,6 +632,79 @@ module pyspeedy_amd_c
             integer(c_int), value :: n_entries, r
             real(c_double), value :: inflation
             real(c_double), intent(out) :: w_out(*), stats_out(*)
+        end function
+        ! the verification tape: scores of a masked ensemble against a truth member of the same model, inside the device loop
+        ! (in_loop = 1) or once on the state as it stands (_apply) (pyspeedy_amd.h: spd_model_verif_*).  weights(96, 48,
+        ! n_patterns); entries as the projection tape's; mask: one integer(c_int32_t) per member (0 or 1), or c_null_ptr for
+        ! spd_verif_check; truth 0-based; _read: real(c_double) (4, n_entries, 2, nt) in device memory; _hist: integer(c_int32_t)
+        ! (66, n_entries, 2, nt) in device memory; rows(7, *); spd_verif_host: x(4608, r), y(4608), w(4608), out4(4), hist66(66)
+        integer(c_int) function spd_verif_check(weights, n_patterns, names, levels, patterns, n_entries, mask, members, truth, every, &
+                capacity, in_loop) bind(C, name="spd_verif_check")
+            import :: c_ptr, c_int, c_double
+            real(c_double), intent(in) :: weights(*)
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), patterns(*)
+            type(c_ptr), value :: mask
+            integer(c_int), value :: n_patterns, n_entries, members, truth, every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_verif_configure(model, weights, n_patterns, names, levels, patterns, n_entries, mask, &
+                truth, every, capacity, in_loop) bind(C, name="spd_model_verif_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model, mask
+            real(c_double), intent(in) :: weights(*)
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), patterns(*)
+            integer(c_int), value :: n_patterns, n_entries, truth, every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_verif_off(model) bind(C, name="spd_model_verif_off")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_verif_reset(model) bind(C, name="spd_model_verif_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_verif_apply(model, stream) bind(C, name="spd_model_verif_apply")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, stream
+        end function
+        integer(c_int) function spd_model_verif_compute(model, scores_device, scores_bytes, hist_device, hist_bytes, stream) &
+                bind(C, name="spd_model_verif_compute")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, scores_device, hist_device, stream
+            integer(c_size_t), value :: scores_bytes, hist_bytes
+        end function
+        integer(c_int) function spd_model_verif_read(model, t0, nt, dst_device, dst_bytes, stream) bind(C, name="spd_model_verif_read")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_verif_hist(model, t0, nt, dst_device, dst_bytes, stream) bind(C, name="spd_model_verif_hist")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_verif_rows(model, rows, max_rows) bind(C, name="spd_model_verif_rows")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(7, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_verif_info(model, r, truth, n_entries, every, capacity, taken, in_loop, applied) &
+                bind(C, name="spd_model_verif_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_int), intent(out) :: r, truth, n_entries, every, capacity, in_loop
+            integer(c_long_long), intent(out) :: taken, applied
+        end function
+        integer(c_int) function spd_verif_host(x, r, y, w, out4, hist66) bind(C, name="spd_verif_host")
+            import :: c_int, c_int32_t, c_double
+            real(c_double), intent(in) :: x(*), y(*), w(*)
+            integer(c_int), value :: r
+            real(c_double), intent(out) :: out4(4)
+            integer(c_int32_t), intent(out) :: hist66(66)
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
         ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for

@@ -207,6 +207,21 @@ _SIGNATURES = {
                                                                                                                   C.POINTER(C.c_longlong)]),
     "spd_assim_weights_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "spd_verif_check": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "spd_model_verif_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "spd_model_verif_off": (C.c_int, [C.c_void_p]),
+    "spd_model_verif_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_verif_apply": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "spd_model_verif_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_verif_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_verif_hist": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_verif_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_verif_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                                                                 C.POINTER(C.c_longlong)]),
+    "spd_verif_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int32)]),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),

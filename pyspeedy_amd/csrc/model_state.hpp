@@ -2,7 +2,7 @@
 // the carving of an allocation that every in-loop feature's _configure and _read run around their own work; the front end of a
 // sample that the statistics and four of the tapes share (defined in model.hip).  model.hip holds the model's life, its registry,
 // the step loop and the rest of the C ABI; the host code of each in-loop feature lies behind its kernels in the feature's own file
-// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, plev.hip, derive.hip).
+// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, verif.hip, plev.hip, derive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,6 +30,7 @@
 #include "assim.hpp"
 #include "wintape.hpp"
 #include "projtape.hpp"
+#include "verif.hpp"
 #include "ring.hpp"
 #include "surface.hpp"
 
@@ -411,6 +412,33 @@ struct spd_model {
         AssimPlane *xplanes = nullptr;
         bool loops() const { return on && in_loop; }  // spd_model_step is issued in segments
     } assim;
+    // The verification tape (spd_model_verif_*): scores of the masked members against a truth member of the same model, after every
+    // step that leaves the step counter at a multiple of `every` (verif.hip).  It reads members of every member group and round, so
+    // a call with in-loop verification is issued as segments that end at those steps (step_impl), and the event goes out on the
+    // caller's stream behind the join -- in front of breeding's or the assimilation's event of the same step, and once more behind
+    // an analysis that was applied there.  It writes nothing into the model.  One allocation of its own (hipMalloc): the rings
+    // [capacity][2][E][4] doubles (`data`) and [capacity][2][E][66] int32 (`counts`), the patterns [P][4608], slab, tables, the
+    // distinct planes' sources, the entry list, the member list, and the point kernel's scratch [planes][4][4608] doubles
+    // (`point`) and [planes][4608] int32 (`bin`).
+    struct Verif : SampleFront {
+        struct Entry {
+            int name, level, pattern;  // name: catalogue id
+        };
+        bool on = false, in_loop = false;
+        int every = 0, npatterns = 0, nplanes = 0, r = 0, truth = -1;
+        SampleRing ring;  // of events since _configure / _reset; rows [7]: step counter, y, m, d, h, min of the state, analysis (0 / 1)
+        Validity validity;
+        long long applied = 0;  // events recorded since _configure: in-loop ones and calls of _apply
+        std::vector<Entry> entries;
+        std::vector<int> members;                 // a_0 < ... < a_(r-1)
+        std::vector<std::pair<int, int>> ranges;  // the masked members and the truth as (first, count) of consecutive indices
+        void *alloc = nullptr;
+        double *data = nullptr, *weights = nullptr, *point = nullptr;
+        int *counts = nullptr, *bin = nullptr, *member_list = nullptr;
+        SampleSource *planes = nullptr;
+        VerifItem *items = nullptr;
+        bool loops() const { return on && in_loop; }  // spd_model_step is issued in segments
+    } verif;
     // spd_model_assim_transform, which works without an assimilation configured: the transform's plane descriptors, a member list
     // and W [64][64] in a small allocation of their own, made at the first call.
     struct AssimTransform {

@@ -76,10 +76,7 @@ __global__ __launch_bounds__(kT) void projtape_kernel(const ProjTapePlane *__res
         for (int b = 0; b < kBatch; ++b) tree[b][t] = s[b];
         __syncthreads();
         if (wave < nb) {
-            const double *row = tree[wave];
-            double v = __dadd_rn(__dadd_rn(row[lane], row[lane + 128]), __dadd_rn(row[lane + 64], row[lane + 192]));
-#pragma unroll
-            for (int half = 32; half > 0; half >>= 1) v = __dadd_rn(v, __shfl_down(v, half, 64));
+            const double v = projtape_fold(tree[wave], lane);
             if (lane == 0) ring_slot[i * n_entries + items[d.first + e0 + wave].column] = v;
         }
         __syncthreads();  // (the next batch overwrites the rows)

@@ -30,6 +30,18 @@ struct ProjTapeItem {
     int pattern, column;
 };
 
+#if defined(__HIPCC__)
+// The tree of the definition over the 256 lane sums of `row` (LDS, complete behind a barrier), formed by one wavefront: the two
+// halvings that cross wavefronts are read from the LDS by lane t < 64, the six inside the wavefront go through cross-lane moves.
+// Lane 0 returns the result; a lane >= half adds something nobody reads.  (projtape_kernel, and verif_reduce_kernel of verif.hip.)
+__device__ __forceinline__ double projtape_fold(const double *row, int lane) {
+    double v = __dadd_rn(__dadd_rn(row[lane], row[lane + 128]), __dadd_rn(row[lane + 64], row[lane + 192]));
+#pragma unroll
+    for (int half = 32; half > 0; half >>= 1) v = __dadd_rn(v, __shfl_down(v, half, 64));
+    return v;
+}
+#endif
+
 // One launch of the projection kernel for the members [first, first + count), all planes (projtape.hip).  weights: [P][4608];
 // slab: [M][slab_fields][4608] fp64, as the front end left it; store32: the model keeps precnv / precls as float; ring_slot:
 // member 0 of the sample's slot, [M][n_entries].  The assimilation's observation operator is this launch into a one-slot ring.

@@ -1130,6 +1130,126 @@ class EnsembleModel:
         """The date of each held event's state, oldest first (a list of datetime)."""
         return self._row_times(self._assim_rows())
 
+    # ---- the verification tape: scores of an ensemble against a truth member (spd_model_verif_*, include/pyspeedy_amd.h) -------
+    def verif_configure(self, weights, entries, members, truth, every, capacity=64, in_loop=True):
+        """Score the members with mask 1 in `members` (2 ... 64 of them) against the member `truth` (mask 0: a nature run in the
+        same model) after every step that leaves current_step at a multiple of `every`, inside run() / run_checked() calls of any
+        length (`in_loop`) or only when verif_apply() is called.  `weights` [P][48][96] and `entries` (name, level, pattern) are
+        the projection tape's (pyspeedy_amd.projection_weights; up to 256 entries, precnv and precls included): per entry the
+        weighted sums of the ensemble mean's error, its square, the ensemble variance and the CRPS, and the rank histogram over
+        the points whose weight is not zero, each in a fixed, documented order, go to a ring of `capacity`
+        events -- before and, where an in-loop analysis was applied at the same step, after it.  Writes nothing into the model.
+        Synchronises the device."""
+        rows = []
+        for entry in entries:
+            if len(entry) != 3:
+                raise ValueError("an entry is (name, level, pattern), got %r" % (entry,))
+            rows.append((str(entry[0]), int(entry[1]), int(entry[2])))
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 3 or w.shape[1:] != (48, 96):
+            raise ValueError("weights must be [P][48][96], got shape %r" % (w.shape,))
+        mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
+        if mask.shape != (self.nmembers,):
+            raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
+        n = max(len(rows), 1)
+        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
+        levels = (C.c_int * n)(*[r[1] for r in rows])
+        patterns = (C.c_int * n)(*[r[2] for r in rows])
+        with torch.cuda.device(self.sp.device):
+            rc = self._lib.spd_model_verif_configure(self._m, w.ctypes.data_as(C.POINTER(C.c_double)), w.shape[0], names, levels, patterns,
+                                                     len(rows), mask.ctypes.data_as(C.POINTER(C.c_int32)), int(truth), int(every),
+                                                     int(capacity), int(bool(in_loop)))
+        if rc != 0:
+            text = (self._lib.spd_last_error() or b"?").decode()
+            if self.verif_info()["members"] == 0:
+                self._verif_entries = ()  # (refused behind the point where the earlier configuration went)
+            raise _lib.SpeedyHipError("spd_model_verif_configure failed (%d): %s" % (rc, text))
+        self._verif_entries = tuple(rows)
+
+    def verif_off(self):
+        """Switch the verification tape off and free everything it holds."""
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_verif_off(self._m), "spd_model_verif_off")
+        self._verif_entries = ()
+
+    def verif_reset(self):
+        """Empty the ring of verification events (no device work)."""
+        check(self._lib.spd_model_verif_reset(self._m), "spd_model_verif_reset")
+
+    def verif_apply(self):
+        """One event on the state as it stands: a ring slot whose first half holds the scores (the second reads NaN / -1);
+        asynchronous on the current stream.  run(k); verif_apply() is what the in-loop mode does at a scheduled step."""
+        check(self._lib.spd_model_verif_apply(self._m, self._stream()), "spd_model_verif_apply")
+
+    def verif_compute(self):
+        """The scores of the state as it stands, without touching the ring: dict(bias, mse, variance, crps) of float64 tensors
+        [E] and hist, an int32 tensor [E][r + 2] (ranks 0 ... r, then the ties), on the model's device."""
+        info = self.verif_info()
+        scores = torch.empty((info["entries"], 4), dtype=torch.float64, device=self.sp.device)
+        hist = torch.empty((info["entries"], 66), dtype=torch.int32, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_verif_compute(self._m, C.c_void_p(scores.data_ptr()), scores.numel() * 8, C.c_void_p(hist.data_ptr()),
+                                                    hist.numel() * 4, self._stream()), "spd_model_verif_compute")
+        return dict(bias=scores[:, 0], mse=scores[:, 1], variance=scores[:, 2], crps=scores[:, 3], hist=hist[:, :info["members"] + 2])
+
+    def verif_info(self):
+        """dict(members, truth, entries, every, capacity, taken, held, in_loop, applied): masked members r (0: off), the truth
+        member (-1: off), the configuration, events recorded since verif_configure / verif_reset and events the ring holds, the
+        mode, and the events recorded since verif_configure."""
+        r, truth, entries, every, capacity, in_loop = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        taken, applied = C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.spd_model_verif_info(self._m, C.byref(r), C.byref(truth), C.byref(entries), C.byref(every), C.byref(capacity),
+                                             C.byref(taken), C.byref(in_loop), C.byref(applied)), "spd_model_verif_info")
+        return dict(members=r.value, truth=truth.value, entries=entries.value, every=every.value, capacity=capacity.value,
+                    taken=int(taken.value), held=int(min(taken.value, capacity.value)), in_loop=bool(in_loop.value),
+                    applied=int(applied.value))
+
+    @property
+    def verif_entries(self):
+        """The configured entries, a tuple of (name, level, pattern) in the order of the last axis of verif() (empty: off)."""
+        return getattr(self, "_verif_entries", ())
+
+    def _verif_rows(self):
+        return self._ring_rows("spd_model_verif_rows", self.verif_info()["held"], 7)
+
+    def verif_steps(self):
+        """The model's step counter at each held event, oldest first (numpy int array)."""
+        return self._row_steps(self._verif_rows())
+
+    def verif_times(self):
+        """The date of each held event's state, oldest first (a list of datetime)."""
+        return self._row_times(self._verif_rows())
+
+    def verif(self, t0=0, nt=None):
+        """The events [t0, t0 + nt) of the held ones, oldest first: dict(bias, mse, variance, crps, rmse, spread) of float64
+        tensors [nt][2][E] on the model's device -- axis 1 is the phase: 0 the state as the event found it (the background), 1 the
+        state an in-loop analysis left at the same step (NaN where there was none) -- with rmse = sqrt(mse), spread =
+        sqrt(variance), and analysis, an int32 tensor [nt]: 1 where phase 1 is filled."""
+        info = self.verif_info()
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        buf = torch.empty((max(nt, 0), 2, info["entries"], 4), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_verif_read(self._m, t0, nt, C.c_void_p(buf.data_ptr()), buf.numel() * 8, self._stream()),
+                  "spd_model_verif_read")
+        rows = self._verif_rows()[t0:t0 + max(nt, 0)]
+        analysis = torch.as_tensor(np.ascontiguousarray(rows[:, 6]), dtype=torch.int32).to(self.sp.device)
+        return dict(bias=buf[..., 0], mse=buf[..., 1], variance=buf[..., 2], crps=buf[..., 3], rmse=torch.sqrt(buf[..., 1]),
+                    spread=torch.sqrt(buf[..., 2]), analysis=analysis)
+
+    def verif_hist(self, t0=0, nt=None):
+        """The rank histograms of the same events: an int32 tensor [nt][2][E][r + 2] on the model's device -- per entry the number
+        of points with a non-zero weight whose truth lies above exactly k members, k = 0 ... r, without equalling any, then the
+        number of points where it equals one (ties); -1 in a phase that was not filled."""
+        info = self.verif_info()
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        buf = torch.empty((max(nt, 0), 2, info["entries"], 66), dtype=torch.int32, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_verif_hist(self._m, t0, nt, C.c_void_p(buf.data_ptr()), buf.numel() * 4, self._stream()),
+                  "spd_model_verif_hist")
+        return buf[..., :info["members"] + 2]
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

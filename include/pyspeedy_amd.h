@@ -1027,6 +1027,74 @@ int spd_model_verif_rows(spd_model_handle m, int32_t *rows, int max_rows);
 int spd_model_verif_info(spd_model_handle m, int *r, int *truth, int *n_entries, int *every, int *capacity, long long *taken, int *in_loop,
                          long long *applied);
 int spd_verif_host(const double *x, int r, const double *y, const double *w, double *out4, int32_t *hist66);
+/* The quantile tape: the distribution over the members at every grid point -- minimum, maximum, quantiles and exceedance
+ * probabilities of a masked ensemble --, recorded on the device at scheduled steps inside spd_model_step /
+ * spd_model_step_checked_begin calls of any length (in-loop mode) or once on the state as it stands (_apply).  It writes nothing
+ * into the model.  Off unless configured, and a model that never configures it issues the launches it always issued.
+ * Configuration.  mask[M] (int32, 0 or 1): the members with mask 1 are the ensemble a_0 < ... < a_(r-1), 2 <= r <= 64; the others
+ * are neither loaded nor stored.  E entries (name, level, op, param), 1 <= E <= 64; name is any name the verification tape accepts
+ * (the statistics' catalogue, the derived and pressure-level names, precnv and precls in their stored precision); the names on
+ * target levels and mslp need spd_model_plev_configure first.  op: SPD_Q_MIN, SPD_Q_MAX (param is not read), SPD_Q_QUANTILE (param
+ * is q, 0 <= q <= 1), SPD_Q_PROB_ABOVE, SPD_Q_PROB_BELOW (param is a finite threshold in the unit an fp64 tape holds the name
+ * in).  every >= 1; capacity >= 1 slots of the ring.
+ * Value.  x_j[p], p = 96 row + column, is what an fp64 tape of that name holds at that level for member a_j at that step: the
+ * same front end (run over the member ranges that cover the mask), export units and stored precision of precnv / precls.
+ * s_0 ... s_(r-1) is the stable ascending order of x_0 ... x_(r-1): x_j stands before x_k iff x_j < x_k, or neither is less than
+ * the other and j < k (numpy's sort(kind="stable"); where -0.0 and +0.0 meet, the member index decides which sign bit comes
+ * first).  A state that the range check accepts holds no NaN, and what a NaN gives is not specified.
+ *     min = s_0;  max = s_(r-1)
+ *     quantile q:  h = fl(q (r - 1)), lo = floor(h), f = h - lo (exact), hi = min(lo + 1, r - 1), formed once on the host.
+ *                  f == 0: s_lo, no arithmetic.  Otherwise v = s_lo + f (s_hi - s_lo) in fp64, the subtraction, the product and
+ *                  the sum each rounded on its own (no fused multiply-add), then v = s_hi if v > s_hi.  So s_lo <= v <= s_hi, and
+ *                  v does not decrease with q.
+ *     prob_above thr:  #{j : x_j > thr} / r;   prob_below thr:  #{j : x_j < thr} / r   (strict; one division, one rounding)
+ * No operation depends on the launch plan, so the bits are the same in every plan.
+ * Ring.  One slot per event: [E][4608] fp64, entry k in the caller's order.  The step counter and the date of an event's state are
+ * kept on the host (_rows: 6 int32, oldest first).
+ * Schedule.  In-loop, after the step that leaves the absolute step counter at n with n % every == 0.  A call with the in-loop
+ * quantile tape is issued in segments that end at the multiples of the `every` of each looping joined consumer (this one, breeding
+ * or assimilation, verification); at such a step: the quantile sample if due, the verification's phase 0 if due, the rescale or
+ * analysis if due, the verification's phase 1 if an analysis was applied.  The sample is always the state the step left, before
+ * an in-loop analysis.  It is bit for bit the host loop  step(k); _apply; step(k); ...  -- checked calls included --, and no
+ * state bit and no other recorder's ring differs from a run without it.
+ *   _configure  one hipMalloc of its own (synchronises the device); the ring is empty, `applied` 0.  SPD_E_ARG, before anything is
+ *               allocated, in this order: every < 1; capacity < 1; in_loop neither 0 nor 1; n_entries outside 1 ... 64; null
+ *               lists; per entry an unknown name, a level out of range, an unknown op, a quantile that is not within 0 ... 1
+ *               (NaN included), a threshold that is not finite; a null mask; a null model; a checked call in flight; a mask entry
+ *               that is not 0 or 1; r outside 2 ... 64; a pressure-level name without target levels.  SPD_E_DEVICE when the
+ *               allocation fails (the byte count is in the message): the tape is off, the model as usable as before.
+ *   spd_qtape_check  the same checks without a model, for `members` members (mask may be NULL: only the rest is checked then).
+ *   _off        switches it off and frees everything.
+ *   _reset      empties the ring (no device work).  spd_model_init does the same.
+ *   _apply      one event on the state as it stands, stream-ordered; writes a ring slot and nothing else.
+ *   _compute    the planes [E][4608] fp64 of the state as it stands into device memory; writes no ring.  It uses the
+ *               configuration's slab: order it against _apply and the steps by the stream.
+ *   _read       the events [t0, t0 + nt) of the held ones, oldest first, of entry `entry` as [nt][4608] fp64 into device memory.
+ *               Refused while a checked call is in flight and after a failed range check of a checked call until _reset or
+ *               spd_model_init.
+ *   _rows       rows[held][6] (host memory): step counter, year, month, day, hour, minute of the event's state.
+ *   _info       r, E, every, capacity, events taken since _configure / _reset, the mode, and `applied`: the events recorded since
+ *               _configure; any pointer may be NULL; all zero without a configuration.
+ *   spd_qtape_host  one plane's entries as the device forms them, compiled for the host: x [r][4608] -> out [n_entries][4608].
+ * spd_model_plev_configure is refused while an entry is a pressure-level name.  spd_model_copy_member does not carry the
+ * configuration, and the outer boundary (spd_parallel_step*) does not keep it: order statistics of two ensembles do not merge. */
+#define SPD_Q_MIN 0
+#define SPD_Q_MAX 1
+#define SPD_Q_QUANTILE 2
+#define SPD_Q_PROB_ABOVE 3
+#define SPD_Q_PROB_BELOW 4
+int spd_qtape_check(const char *const *names, const int *levels, const int *ops, const double *params, int n_entries, const int32_t *mask,
+                    int members, int every, int capacity, int in_loop);
+int spd_model_qtape_configure(spd_model_handle m, const char *const *names, const int *levels, const int *ops, const double *params, int n_entries,
+                              const int32_t *mask, int every, int capacity, int in_loop);
+int spd_model_qtape_off(spd_model_handle m);
+int spd_model_qtape_reset(spd_model_handle m);
+int spd_model_qtape_apply(spd_model_handle m, void *stream);
+int spd_model_qtape_compute(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_qtape_read(spd_model_handle m, int entry, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_qtape_rows(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_qtape_info(spd_model_handle m, int *r, int *n_entries, int *every, int *capacity, long long *taken, int *in_loop, long long *applied);
+int spd_qtape_host(const double *x, int r, const int *ops, const double *params, int n_entries, double *out);
 /* Spectra by total wavenumber and global means of the spectral state, recorded on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length, or computed on the state as it stands.  Plain sums over the spectral
  * coefficients of time level 1 (the level spd_model_spectral2grid exports): no transform.  A spectral field is complex [32 n][31 m],

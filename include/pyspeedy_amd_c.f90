@@ -14,7 +14,9 @@
 !! spectral state toward target fields inside the device loop (spd_model_nudge_*), and breeding: the rescaling of member
 !! perturbations against their control runs inside the device loop (spd_model_breed_*, spd_breed_check), orthonormalised on request,
 !! and assimilation: an ensemble square-root filter inside the device loop (spd_model_assim_*, spd_assim_check), and the
-!! verification tape: scores of an ensemble against a truth member inside the device loop (spd_model_verif_*, spd_verif_check)
+!! verification tape: scores of an ensemble against a truth member inside the device loop (spd_model_verif_*, spd_verif_check),
+!! and the quantile tape: minimum, maximum, quantiles and exceedance probabilities over the members at every grid point inside
+!! the device loop (spd_model_qtape_*, spd_qtape_check)
 module pyspeedy_amd_c
     use iso_c_binding
     implicit none
@@ -27,6 +29,7 @@ module pyspeedy_amd_c
     integer(c_int), parameter :: SPD_WIN_SUM = 0, SPD_WIN_MEAN = 1, SPD_WIN_MIN = 2, SPD_WIN_MAX = 3
     integer(c_int), parameter :: SPD_WIN_COUNT_ABOVE = 4, SPD_WIN_COUNT_BELOW = 5
     integer(c_int), parameter :: SPD_WINDOW_STEPS = 0, SPD_WINDOW_DAY = 1, SPD_WINDOW_MONTH = 2
+    integer(c_int), parameter :: SPD_Q_MIN = 0, SPD_Q_MAX = 1, SPD_Q_QUANTILE = 2, SPD_Q_PROB_ABOVE = 3, SPD_Q_PROB_BELOW = 4
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -705,6 +708,73 @@ module pyspeedy_amd_c
             integer(c_int), value :: r
             real(c_double), intent(out) :: out4(4)
             integer(c_int32_t), intent(out) :: hist66(66)
+        end function
+        ! the quantile tape: order statistics over a masked ensemble at every grid point, inside the device loop (in_loop = 1) or
+        ! once on the state as it stands (_apply) (pyspeedy_amd.h: spd_model_qtape_*).  An entry is names(k), levels(k) (0-based),
+        ! ops(k): SPD_Q_MIN (0) ... SPD_Q_PROB_BELOW (4), params(k): q or a threshold; mask: one integer(c_int32_t) per member
+        ! (0 or 1), or c_null_ptr for spd_qtape_check; entry 0-based; _read: real(c_double) (96, 48, nt) in device memory; _compute:
+        ! (96, 48, n_entries) in device memory; rows(6, *); spd_qtape_host: x(4608, r) -> out(4608, n_entries)
+        integer(c_int) function spd_qtape_check(names, levels, ops, params, n_entries, mask, members, every, capacity, in_loop) &
+                bind(C, name="spd_qtape_check")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), ops(*)
+            real(c_double), intent(in) :: params(*)
+            type(c_ptr), value :: mask
+            integer(c_int), value :: n_entries, members, every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_qtape_configure(model, names, levels, ops, params, n_entries, mask, every, capacity, &
+                in_loop) bind(C, name="spd_model_qtape_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model, mask
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), ops(*)
+            real(c_double), intent(in) :: params(*)
+            integer(c_int), value :: n_entries, every, capacity, in_loop
+        end function
+        integer(c_int) function spd_model_qtape_off(model) bind(C, name="spd_model_qtape_off")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_qtape_reset(model) bind(C, name="spd_model_qtape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_qtape_apply(model, stream) bind(C, name="spd_model_qtape_apply")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model, stream
+        end function
+        integer(c_int) function spd_model_qtape_compute(model, dst_device, dst_bytes, stream) bind(C, name="spd_model_qtape_compute")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_qtape_read(model, entry, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_qtape_read")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: entry, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_qtape_rows(model, rows, max_rows) bind(C, name="spd_model_qtape_rows")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_qtape_info(model, r, n_entries, every, capacity, taken, in_loop, applied) &
+                bind(C, name="spd_model_qtape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_int), intent(out) :: r, n_entries, every, capacity, in_loop
+            integer(c_long_long), intent(out) :: taken, applied
+        end function
+        integer(c_int) function spd_qtape_host(x, r, ops, params, n_entries, out) bind(C, name="spd_qtape_host")
+            import :: c_int, c_double
+            real(c_double), intent(in) :: x(*), params(*)
+            integer(c_int), intent(in) :: ops(*)
+            integer(c_int), value :: r, n_entries
+            real(c_double), intent(out) :: out(*)
         end function
         ! spectra by total wavenumber and global means of the spectral state, recorded inside spd_model_step calls or computed on
         ! the state as it stands (pyspeedy_amd.h: spd_model_spectra_*).  fp64; rows as the tape's; _read: (32[, 8], nt, count) for

@@ -22,6 +22,7 @@ SPD_ENS_MEAN, SPD_ENS_STD, SPD_ENS_M2 = 0, 1, 2  # kinds of spd_model_enstape_re
 SPD_ACC_SUM, SPD_ACC_MEAN, SPD_ACC_MIN, SPD_ACC_MAX = 0, 1, 2, 3  # ops of spd_model_acctape_configure / _read
 SPD_WIN_SUM, SPD_WIN_MEAN, SPD_WIN_MIN, SPD_WIN_MAX, SPD_WIN_COUNT_ABOVE, SPD_WIN_COUNT_BELOW = 0, 1, 2, 3, 4, 5  # ops of spd_model_wintape_*
 SPD_WINDOW_STEPS, SPD_WINDOW_DAY, SPD_WINDOW_MONTH = 0, 1, 2  # window kinds of spd_model_wintape_configure / spd_wintape_plan
+SPD_Q_MIN, SPD_Q_MAX, SPD_Q_QUANTILE, SPD_Q_PROB_ABOVE, SPD_Q_PROB_BELOW = 0, 1, 2, 3, 4  # ops of spd_model_qtape_configure
 
 
 class SpeedyHipError(RuntimeError):
@@ -222,6 +223,19 @@ _SIGNATURES = {
                                                                                  C.POINTER(C.c_longlong)]),
     "spd_verif_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                  C.POINTER(C.c_int32)]),
+    "spd_qtape_check": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int,
+                                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "spd_model_qtape_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                            C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),
+    "spd_model_qtape_off": (C.c_int, [C.c_void_p]),
+    "spd_model_qtape_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_qtape_apply": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "spd_model_qtape_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_qtape_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_qtape_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_qtape_info": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                                                                 C.POINTER(C.c_longlong)]),
+    "spd_qtape_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "spd_model_spectra_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int]),
     "spd_model_spectra_reset": (C.c_int, [C.c_void_p]),
     "spd_model_spectra_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 3),

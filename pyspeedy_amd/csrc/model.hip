@@ -748,6 +748,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->assim.alloc) (void)hipFree(m->assim.alloc);
     if (m->assim_xf.alloc) (void)hipFree(m->assim_xf.alloc);
     if (m->verif.alloc) (void)hipFree(m->verif.alloc);
+    if (m->qtape.alloc) (void)hipFree(m->qtape.alloc);
     if (m->ev_start) (void)hipEventDestroy(m->ev_start);
     if (m->ev_offset) (void)hipEventDestroy(m->ev_offset);
     if (m->h_err_sync) (void)hipHostFree(m->h_err_sync);
@@ -1326,6 +1327,8 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->assim.skipped = 0;
     m->verif.ring.clear();  // (... and no verification event)
     m->verif.validity.clear();
+    m->qtape.ring.clear();  // (... and no quantile sample)
+    m->qtape.validity.clear();
     // ---- land_model_init / sea_model_init: every member's boundary fields preprocessed where they lie (surface.hip)
     {
         LandSeaPtrs L{};
@@ -1806,18 +1809,26 @@ static int step_segment(spd_model *m, int nsteps, void *stream, bool record, con
 // the multiples of every looping consumer's `every`.  At a cut the verification's event (phase 0), if due, goes out first -- it
 // reads the state and writes none of it --, then the rescale or the analysis, if due, and behind an analysis that was applied
 // there the verification's phase 1.  An extra cut changes nothing else: a segment is a call of its own.
+//
+// The in-loop quantile tape is a fourth, cut at the multiples of its own `every`; its sample, if due, goes out
+// in front of the verification's phase 0: the state the step left, before any analysis.  It writes none of the state either.
 static int step_impl(spd_model *m, int nsteps, void *stream, bool record, const char *who) {
     const bool breeds = m && m->breed.loops(), assimilates = m && !breeds && m->assim.loops(), verifies = m && m->verif.loops();
-    if (!m || (!breeds && !assimilates && !verifies) || nsteps < 1) return step_segment(m, nsteps, stream, record, who, 0, nsteps);
+    const bool ranks = m && m->qtape.loops();
+    if (!m || (!breeds && !assimilates && !verifies && !ranks) || nsteps < 1) return step_segment(m, nsteps, stream, record, who, 0, nsteps);
     const int every = breeds ? m->breed.every : assimilates ? m->assim.every : 0, verif_every = verifies ? m->verif.every : 0;
+    const int qtape_every = ranks ? m->qtape.every : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const auto to_next = [&](int e) { return e - ((m->current_step % e) + e) % e; };  // steps to the next multiple of e
     for (int done = 0; done < nsteps;) {
         int len = nsteps - done;
         if (every) len = std::min(len, to_next(every));
         if (verif_every) len = std::min(len, to_next(verif_every));
+        if (qtape_every) len = std::min(len, to_next(qtape_every));
         if (int rc = step_segment(m, len, stream, record, who, done, nsteps)) return rc;
         done += len;
+        if (qtape_every && m->current_step % qtape_every == 0)
+            if (int rc = qtape_event(m, s, who)) return rc;
         const bool scored = verif_every && m->current_step % verif_every == 0;
         if (scored)
             if (int rc = verif_event(m, s, who, 0)) return rc;
@@ -1885,6 +1896,7 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
         if (m->projtape.on && m->projtape.validity.valid) m->projtape.validity.fail(i, *failed);
         if (m->assim.on && m->assim.validity.valid) m->assim.validity.fail(i, *failed);
         if (m->verif.on && m->verif.validity.valid) m->verif.validity.fail(i, *failed);
+        if (m->qtape.on && m->qtape.validity.valid) m->qtape.validity.fail(i, *failed);
     }
     if (accepted)  // a member's last accepted step: the one before its first failure, or the last of the call
         for (int i = 0; i < M; ++i)

@@ -2,7 +2,8 @@
 // the carving of an allocation that every in-loop feature's _configure and _read run around their own work; the front end of a
 // sample that the statistics and four of the tapes share (defined in model.hip).  model.hip holds the model's life, its registry,
 // the step loop and the rest of the C ABI; the host code of each in-loop feature lies behind its kernels in the feature's own file
-// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, verif.hip, plev.hip, derive.hip).
+// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, verif.hip, qtape.hip, plev.hip,
+// derive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,7 @@
 #include "wintape.hpp"
 #include "projtape.hpp"
 #include "verif.hpp"
+#include "qtape.hpp"
 #include "ring.hpp"
 #include "surface.hpp"
 
@@ -439,6 +441,33 @@ struct spd_model {
         VerifItem *items = nullptr;
         bool loops() const { return on && in_loop; }  // spd_model_step is issued in segments
     } verif;
+    // The quantile tape (spd_model_qtape_*): order statistics over the masked members per grid point -- minimum, maximum, quantiles,
+    // exceedance probabilities --, after every step that leaves the step counter at a multiple of `every` (qtape.hip).  It reads
+    // members of every member group and round, so a call with the in-loop quantile tape is issued as segments that end at those
+    // steps (step_impl), and the event goes out on the caller's stream behind the join, in front of every other joined consumer's
+    // event of the same step.  It writes nothing into the model.  One allocation of its own (hipMalloc): the ring
+    // [capacity][E][4608] doubles (`data`), slab, tables, the distinct planes with their sources, the entry descriptors sorted by
+    // plane, and the member list.
+    struct Qtape : SampleFront {
+        struct Entry {
+            int name, level, op;  // name: catalogue id; op: SPD_Q_*
+            double param;
+        };
+        bool on = false, in_loop = false;
+        int every = 0, nplanes = 0, r = 0;
+        SampleRing ring;  // of events since _configure / _reset; rows [6]: step counter, y, m, d, h, min of the sampled state
+        Validity validity;
+        long long applied = 0;  // events recorded since _configure: in-loop ones and calls of _apply
+        std::vector<Entry> entries;
+        std::vector<int> members;                 // a_0 < ... < a_(r-1)
+        std::vector<std::pair<int, int>> ranges;  // the masked members as (first, count) of consecutive indices
+        void *alloc = nullptr;
+        double *data = nullptr;
+        int *member_list = nullptr;
+        QtapePlane *planes = nullptr;
+        QtapeItem *items = nullptr;
+        bool loops() const { return on && in_loop; }  // spd_model_step is issued in segments
+    } qtape;
     // spd_model_assim_transform, which works without an assimilation configured: the transform's plane descriptors, a member list
     // and W [64][64] in a small allocation of their own, made at the first call.
     struct AssimTransform {

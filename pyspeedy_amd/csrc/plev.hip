@@ -135,6 +135,9 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
     if (m->verif.on && m->verif.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the verification tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_verif_off)");
+    if (m->qtape.on && m->qtape.holds_plev())
+        return m_fail(SPD_E_ARG, std::string(who) + ": the quantile tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_qtape_off)");
     spd_model::Plev &pl = m->plev;
     pl.n = n;
     for (int j = 0; j < kPlevMaxLevels; ++j) {

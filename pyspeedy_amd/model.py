@@ -1250,6 +1250,110 @@ class EnsembleModel:
                   "spd_model_verif_hist")
         return buf[..., :info["members"] + 2]
 
+    # ---- the quantile tape: the distribution over the members at every grid point (spd_model_qtape_*, include/pyspeedy_amd.h) --
+    QTAPE_OPS = {"min": _lib.SPD_Q_MIN, "max": _lib.SPD_Q_MAX, "quantile": _lib.SPD_Q_QUANTILE, "prob_above": _lib.SPD_Q_PROB_ABOVE,
+                 "prob_below": _lib.SPD_Q_PROB_BELOW}
+
+    def qtape_configure(self, entries, members, every, capacity=64, in_loop=True):
+        """Record order statistics over the members with mask 1 in `members` (2 ... 64 of them) at every grid point, after every
+        step that leaves current_step at a multiple of `every`, inside run() / run_checked() calls of any length (`in_loop`) or
+        only when qtape_apply() is called.  `entries` is a list (at most 64) of (name, level, op) or (name, level, op, param): name
+        any of STATS_VARIABLES (the pressure-level ones after plev_configure with its levels in hPa; precnv and precls included),
+        level a 0-based level of that name, op "min", "max", "quantile" (param: q within 0 ... 1), "prob_above" or "prob_below"
+        (param: a threshold in the unit tape() returns the name in -- t_grid in K, ps_grid and mslp in Pa; the share of the
+        members strictly above / below it).  Each value is formed from what a float64 tape holds, exactly as numpy's stable sort
+        and the documented interpolation give it, and goes to a ring of `capacity` events in device memory.
+        Writes nothing into the model.  Synchronises the device."""
+        rows = []
+        for entry in entries:
+            if len(entry) not in (3, 4):
+                raise ValueError("an entry is (name, level, op) or (name, level, op, param), got %r" % (entry,))
+            if entry[2] not in self.QTAPE_OPS:
+                raise ValueError("op must be one of 'min', 'max', 'quantile', 'prob_above', 'prob_below', got %r" % (entry[2],))
+            if entry[2] not in ("min", "max") and len(entry) != 4:
+                raise ValueError("op %r needs a parameter: (name, level, op, param)" % (entry[2],))
+            rows.append((str(entry[0]), int(entry[1]), entry[2], float(entry[3]) if len(entry) == 4 else 0.0))
+        mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
+        if mask.shape != (self.nmembers,):
+            raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
+        n = max(len(rows), 1)
+        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
+        levels = (C.c_int * n)(*[r[1] for r in rows])
+        ops = (C.c_int * n)(*[self.QTAPE_OPS[r[2]] for r in rows])
+        params = (C.c_double * n)(*[r[3] for r in rows])
+        with torch.cuda.device(self.sp.device):
+            rc = self._lib.spd_model_qtape_configure(self._m, names, levels, ops, params, len(rows), mask.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     int(every), int(capacity), int(bool(in_loop)))
+        if rc != 0:
+            text = (self._lib.spd_last_error() or b"?").decode()
+            if self.qtape_info()["members"] == 0:
+                self._qtape_entries = ()  # (refused behind the point where the earlier configuration went)
+            raise _lib.SpeedyHipError("spd_model_qtape_configure failed (%d): %s" % (rc, text))
+        self._qtape_entries = tuple(rows)
+
+    def qtape_off(self):
+        """Switch the quantile tape off and free everything it holds."""
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_qtape_off(self._m), "spd_model_qtape_off")
+        self._qtape_entries = ()
+
+    def qtape_reset(self):
+        """Empty the ring of quantile-tape events (no device work)."""
+        check(self._lib.spd_model_qtape_reset(self._m), "spd_model_qtape_reset")
+
+    def qtape_apply(self):
+        """One event on the state as it stands: a ring slot with every entry's plane; asynchronous on the current stream.
+        run(k); qtape_apply() is what the in-loop mode does at a scheduled step."""
+        check(self._lib.spd_model_qtape_apply(self._m, self._stream()), "spd_model_qtape_apply")
+
+    def qtape_compute(self):
+        """Every entry's plane of the state as it stands, without touching the ring: a float64 tensor [E][48][96] on the model's
+        device."""
+        out = torch.empty((self.qtape_info()["entries"], 48, 96), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_qtape_compute(self._m, C.c_void_p(out.data_ptr()), out.numel() * 8, self._stream()),
+                  "spd_model_qtape_compute")
+        return out
+
+    def qtape_info(self):
+        """dict(members, entries, every, capacity, taken, held, in_loop, applied): masked members r (0: off), the configuration,
+        events recorded since qtape_configure / qtape_reset and events the ring holds, the mode, and the events recorded since
+        qtape_configure."""
+        r, entries, every, capacity, in_loop = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        taken, applied = C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.spd_model_qtape_info(self._m, C.byref(r), C.byref(entries), C.byref(every), C.byref(capacity), C.byref(taken),
+                                             C.byref(in_loop), C.byref(applied)), "spd_model_qtape_info")
+        return dict(members=r.value, entries=entries.value, every=every.value, capacity=capacity.value, taken=int(taken.value),
+                    held=int(min(taken.value, capacity.value)), in_loop=bool(in_loop.value), applied=int(applied.value))
+
+    @property
+    def qtape_entries(self):
+        """The configured entries, a tuple of (name, level, op, param) in the order qtape() counts them in (empty: off)."""
+        return getattr(self, "_qtape_entries", ())
+
+    def _qtape_rows(self):
+        return self._ring_rows("spd_model_qtape_rows", self.qtape_info()["held"], 6)
+
+    def qtape_steps(self):
+        """The model's step counter at each held event, oldest first (numpy int array)."""
+        return self._row_steps(self._qtape_rows())
+
+    def qtape_times(self):
+        """The date of each held event's state, oldest first (a list of datetime)."""
+        return self._row_times(self._qtape_rows())
+
+    def qtape(self, entry, t0=0, nt=None):
+        """The events [t0, t0 + nt) of the held ones, oldest first, of the entry with index `entry` in qtape_entries: a float64
+        tensor [nt][48][96] on the model's device."""
+        info = self.qtape_info()
+        t0 = int(t0)
+        nt = info["held"] - t0 if nt is None else int(nt)
+        out = torch.empty((max(nt, 0), 48, 96), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_qtape_read(self._m, int(entry), t0, nt, C.c_void_p(out.data_ptr()), out.numel() * 8, self._stream()),
+                  "spd_model_qtape_read")
+        return out
+
     # ---- spectra by total wavenumber and global means of the spectral state (spd_model_spectra_*, include/pyspeedy_amd.h) -
     SPECTRA_NAMES = ("ke_rot_spectrum", "ke_div_spectrum", "t_spectrum", "q_spectrum", "lnps_spectrum", "t_mean", "q_mean",
                      "lnps_mean")

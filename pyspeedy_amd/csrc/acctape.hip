@@ -223,12 +223,8 @@ int spd_model_acctape_configure(spd_model_handle m, const char *const *names, co
 }
 
 int spd_model_acctape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: null model");
-    if (!m->acctape.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_reset: ") + kAccOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_acctape_reset: a checked multi-step call is in flight; end it first");
-    m->acctape.ring.clear();
+    if (int rc = ring_reset(m, "spd_model_acctape_reset", &spd_model::acctape, kAccOff)) return rc;
     m->acctape.window_start = -1;  // (the next window starts at the next step, which overwrites the accumulators: no device work)
-    m->acctape.validity.clear();
     return SPD_OK;
 }
 
@@ -245,11 +241,7 @@ int spd_model_acctape_info(spd_model_handle m, long long *taken, int *held, int 
 }
 
 int spd_model_acctape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_acctape_times: null model");
-    const spd_model::AccTape &ac = m->acctape;
-    if (!ac.on) return m_fail(SPD_E_ARG, std::string("spd_model_acctape_times: ") + kAccOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_acctape_times: bad destination");
-    return ac.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_acctape_times", &spd_model::acctape, kAccOff, rows, max_rows);
 }
 
 int spd_model_acctape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,

@@ -130,7 +130,7 @@ hipError_t assim_observe(spd_model *m, double *Y, hipStream_t s) {
     const spd_model::Assim &as = m->assim;
     const int E = static_cast<int>(as.entries.size());
     hipError_t e = hipSuccess;
-    for (const auto &range : as.ranges) {
+    for (const auto &range : as.set.ranges) {
         if (e == hipSuccess) e = sample_front(m, as, range.first, range.second, s);
         if (e == hipSuccess)
             e = run_projtape_sample(as.planes, as.nplanes, as.items, as.weights, as.slab, as.slab_fields, as.yraw, E, range.first, range.second,
@@ -141,15 +141,6 @@ hipError_t assim_observe(spd_model *m, double *Y, hipStream_t s) {
         e = hipGetLastError();
     }
     return e;
-}
-
-// a call that reads or moves the state of a model that is there
-int assim_call_allowed(const spd_model *m, const char *who, bool needs_configuration) {
-    if (int rc = usable(m, who)) return rc;
-    if (needs_configuration && !m->assim.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kAssimOff);
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    return SPD_OK;
 }
 
 // the checks of an observation table of E entries per row
@@ -224,38 +215,18 @@ int spd_assim_check(const double *weights, int n_patterns, const char *const *na
         return m_fail(SPD_E_ARG, std::string(who) + ": n_entries must be 1 ... " + std::to_string(kAssimMax) + ", got " + std::to_string(n_entries));
     if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
     if (!names || !levels || !patterns) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
-    for (int p = 0; p < n_patterns; ++p)
-        for (int q = 0; q < NG; ++q)
-            if (!std::isfinite(weights[static_cast<size_t>(p) * NG + q]))
-                return m_fail(SPD_E_ARG, std::string(who) + ": weight of pattern " + std::to_string(p) + " at point " + std::to_string(q) + " (row " +
-                                             std::to_string(q / IX) + ", column " + std::to_string(q % IX) + ") is not finite");
+    if (int rc = check_weight_maps(who, weights, n_patterns)) return rc;
     for (int k = 0; k < n_entries; ++k) {
-        const int id = names[k] ? stats_id(names[k]) : -1;
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, u_plev, v_plev, t_plev, q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
+        const int id = entry_id(who, names[k], "u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, u_plev, v_plev, t_plev, q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
+        if (id < 0) return SPD_E_ARG;
         if (cat_kind(id) == CAT_PRECIP)
             return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' (entry " + std::to_string(k) +
                                          ") cannot be assimilated: precnv and precls are outputs of the column physics, not functions of the state");
-        const int fixed = kStatsCatalogue[id].levels;
-        if (levels[k] < 0 || (fixed > 0 && levels[k] >= fixed))
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" + names[k] +
-                                         "') is out of range" + (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
-        if (patterns[k] < 0 || patterns[k] >= n_patterns)
-            return m_fail(SPD_E_ARG, std::string(who) + ": pattern " + std::to_string(patterns[k]) + " of entry " + std::to_string(k) + " ('" +
-                                         names[k] + "') is out of range (0 ... " + std::to_string(n_patterns - 1) + ")");
+        if (int rc = check_entry_level(who, k, names[k], id, levels[k])) return rc;
+        if (int rc = check_entry_pattern(who, k, names[k], patterns[k], n_patterns)) return rc;
     }
-    if (!mask) return SPD_OK;  // (the member mask needs the member count: checked once the model is known)
-    int r = 0;
-    for (int i = 0; i < members; ++i) {
-        if (mask[i] != 0 && mask[i] != 1)
-            return m_fail(SPD_E_ARG, std::string(who) + ": the mask of member " + std::to_string(i) + " (" + std::to_string(mask[i]) + ") is not 0 or 1");
-        r += mask[i];
-    }
-    if (r < 2 || r > kAssimMax)
-        return m_fail(SPD_E_ARG, std::string(who) + ": " + std::to_string(r) + " members are masked in: an analysis takes 2 ... " +
-                                     std::to_string(kAssimMax));
-    return SPD_OK;
+    // (the member mask needs the member count: checked once the model is known)
+    return mask ? check_member_mask(who, mask, members, kAssimMax, "an analysis takes") : SPD_OK;
 }
 
 int spd_model_assim_configure(spd_model_handle m, const double *weights, int n_patterns, const char *const *names, const int *levels,
@@ -266,15 +237,9 @@ int spd_model_assim_configure(spd_model_handle m, const double *weights, int n_p
     if (!mask) return m_fail(SPD_E_ARG, std::string(who) + ": null member mask");
     if (int rc = configure_allowed(m, who)) return rc;
     if (int rc = spd_assim_check(weights, n_patterns, names, levels, patterns, n_entries, mask, m->M, every, capacity, inflation, in_loop)) return rc;
-    std::vector<spd_model::Assim::Entry> entries;
-    for (int k = 0; k < n_entries; ++k) {
-        entries.push_back({stats_id(names[k]), levels[k], patterns[k]});
-        if (!cat_needs_levels(entries[k].name)) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
-        if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-        if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" + names[k] +
-                                         "') is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
-    }
+    std::vector<PatternEntry> entries;
+    for (int k = 0; k < n_entries; ++k) entries.push_back({stats_id(names[k]), levels[k], patterns[k]});
+    if (int rc = check_plev_entries(m, who, names, entries)) return rc;
     if (in_loop && m->breed.on && m->breed.in_loop)
         return m_fail(SPD_E_ARG, std::string(who) + ": in-loop assimilation cannot be configured while in-loop breeding (spd_model_breed_configure) is: "
                                                     "both cut the call at their own steps; switch one of them off or to in_loop = 0");
@@ -285,34 +250,19 @@ int spd_model_assim_configure(spd_model_handle m, const double *weights, int n_p
     next.every = every;
     next.inflation = inflation;
     next.npatterns = n_patterns;
-    for (int i = 0; i < m->M; ++i)
-        if (mask[i]) {
-            if (next.ranges.empty() || next.ranges.back().first + next.ranges.back().second != i) next.ranges.push_back({i, 0});
-            ++next.ranges.back().second;
-            next.members.push_back(i);
-        }
-    next.r = static_cast<int>(next.members.size());
+    next.set = member_set(mask, m->M);
+    next.r = static_cast<int>(next.set.members.size());
     const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity), E = static_cast<size_t>(n_entries);
-    // the sample plan and the projection kernel's lists, as spd_model_projtape_configure builds them
-    std::vector<int> ids;
-    for (const auto &e : entries)
-        if (std::find(ids.begin(), ids.end(), e.name) == ids.end()) ids.push_back(e.name);
+    // the sample plan and the projection kernel's lists, as the projection tape builds them
+    const EntryPlanes table = entry_planes(entries);
     SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    std::vector<std::pair<int, int>> distinct;  // (name, level)
-    std::vector<int> plane_of(E);
-    for (size_t k = 0; k < E; ++k) {
-        const std::pair<int, int> key{entries[k].name, entries[k].level};
-        const auto at = std::find(distinct.begin(), distinct.end(), key);
-        plane_of[k] = static_cast<int>(at - distinct.begin());
-        if (at == distinct.end()) distinct.push_back(key);
-    }
+    plan_sample(m, table.ids, next, plan);
     const std::vector<AssimPlane> xplanes = assim_planes(m);
     // one allocation: ring | patterns | slab | tables[2] | plane descriptors | entry list | yraw | Y | W | member list | transform planes
     const size_t per_slot = E * 4 * sizeof(double);
     if (slots > (static_cast<size_t>(-1) / 2) / per_slot) return m_fail(SPD_E_ARG, std::string(who) + ": the ring's size does not fit size_t");
     const size_t ring = sample_up(slots * per_slot), maps = sample_up(static_cast<size_t>(n_patterns) * NG * sizeof(double));
-    const size_t desc = sample_up(distinct.size() * sizeof(ProjTapePlane)), list = sample_up(E * sizeof(ProjTapeItem));
+    const size_t desc = sample_up(table.distinct.size() * sizeof(ProjTapePlane)), list = sample_up(E * sizeof(ProjTapeItem));
     const size_t yraw = sample_up(M * E * sizeof(double)), ybytes = sample_up(E * kAssimMax * sizeof(double));
     const size_t wbytes = sample_up(kAssimMax * kAssimMax * sizeof(double)), mbytes = sample_up(kAssimMax * sizeof(int));
     const size_t xbytes = sample_up(xplanes.size() * sizeof(AssimPlane));
@@ -339,21 +289,18 @@ int spd_model_assim_configure(spd_model_handle m, const double *weights, int n_p
     if (e == hipSuccess) e = build_sample_front(m, plan, next, sources);
     std::vector<ProjTapePlane> host_planes;
     std::vector<ProjTapeItem> host_items;
-    for (size_t q = 0; q < distinct.size(); ++q) {
-        const int id = distinct[q].first, level = distinct[q].second;
-        const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
-        ProjTapePlane d{};
-        d.source = sources[var->first_plane + static_cast<size_t>(level)];  // (precnv / precls are refused: every plane comes from the slab)
+    for (size_t q = 0; q < table.distinct.size(); ++q) {
+        ProjTapePlane d{};  // (precnv / precls are refused: every plane comes from the slab)
+        d.source = plane_source(plan, sources, table.distinct[q].first, table.distinct[q].second);
         d.first = static_cast<int>(host_items.size());
-        for (size_t k = 0; k < E; ++k)
-            if (plane_of[k] == static_cast<int>(q)) host_items.push_back({entries[k].pattern, static_cast<int>(k)});
+        table.each_entry_of(q, [&](int k) { host_items.push_back({entries[k].pattern, k}); });
         d.count = static_cast<int>(host_items.size()) - d.first;
         host_planes.push_back(d);
     }
     if (e == hipSuccess) e = hipMemcpy(next.weights, weights, static_cast<size_t>(n_patterns) * NG * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(ProjTapePlane), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(next.items, host_items.data(), host_items.size() * sizeof(ProjTapeItem), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(next.member_list, next.members.data(), next.members.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.member_list, next.set.members.data(), next.set.members.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(next.xplanes, xplanes.data(), xplanes.size() * sizeof(AssimPlane), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return upload_failed(who, e, p);
@@ -390,7 +337,7 @@ int spd_model_assim_set_observations(spd_model_handle m, const int32_t *steps, i
 int spd_model_assim_apply(spd_model_handle m, void *stream) {
     const char *who = "spd_model_assim_apply";
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = assim_call_allowed(m, who, true)) return rc;
+    if (int rc = state_call_allowed(m, who, m->assim.on, kAssimOff)) return rc;
     M_HIP(hipSetDevice(m->ctx->device));
     return assim_event(m, static_cast<hipStream_t>(stream), who, false);
 }
@@ -398,7 +345,7 @@ int spd_model_assim_apply(spd_model_handle m, void *stream) {
 int spd_model_assim_compute(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream) {
     const char *who = "spd_model_assim_compute";
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = assim_call_allowed(m, who, true)) return rc;
+    if (int rc = state_call_allowed(m, who, m->assim.on, kAssimOff)) return rc;
     const spd_model::Assim &as = m->assim;
     const size_t need = as.entries.size() * as.r * sizeof(double);
     if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
@@ -423,7 +370,7 @@ int spd_model_assim_transform(spd_model_handle m, const int32_t *members, int r,
         for (int j = 0; j < i; ++j)
             if (members[i] == members[j]) return m_fail(SPD_E_ARG, std::string(who) + ": member " + std::to_string(members[i]) + " is named twice");
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = assim_call_allowed(m, who, false)) return rc;
+    if (int rc = state_call_allowed(m, who, true, kAssimOff)) return rc;
     for (int i = 0; i < r; ++i)
         if (members[i] < 0 || members[i] >= m->M)
             return m_fail(SPD_E_ARG, std::string(who) + ": member " + std::to_string(members[i]) + " is out of range (0 ... " + std::to_string(m->M - 1) + ")");
@@ -477,13 +424,8 @@ int spd_model_assim_read(spd_model_handle m, int t0, int nt, void *dst_device, s
     if (int rc = held_range(who, as.ring, t0, nt, "event")) return rc;
     const size_t per = as.entries.size() * 4, need = static_cast<size_t>(nt) * per * sizeof(double);
     if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
-    if (nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    // (the spectra's gather with one "member" whose entry is the E x 4 values of a slot)
-    const hipError_t e = run_spectra_gather(as.data, static_cast<double *>(dst_device), static_cast<int>(per), static_cast<long>(per), 1, nt,
-                                            as.ring.slot_of_held(t0), as.ring.capacity, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
+    // (one block per slot: the E x 4 values)
+    return gather_slots(m, who, as.data, per, per, 1, t0, nt, as.ring, dst_device, stream);
 }
 
 int spd_model_assim_weights(spd_model_handle m, void *w_device, size_t w_bytes, void *y_device, size_t y_bytes, void *stream) {
@@ -503,19 +445,11 @@ int spd_model_assim_weights(spd_model_handle m, void *w_device, size_t w_bytes, 
 }
 
 int spd_model_assim_rows(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_assim_rows: null model");
-    const spd_model::Assim &as = m->assim;
-    if (!as.on) return m_fail(SPD_E_ARG, std::string("spd_model_assim_rows: ") + kAssimOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_assim_rows: bad destination");
-    return as.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_assim_rows", &spd_model::assim, kAssimOff, rows, max_rows);
 }
 
 int spd_model_assim_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_assim_reset: null model");
-    if (!m->assim.on) return m_fail(SPD_E_ARG, std::string("spd_model_assim_reset: ") + kAssimOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_assim_reset: a checked multi-step call is in flight; end it first");
-    m->assim.ring.clear();
-    m->assim.validity.clear();
+    if (int rc = ring_reset(m, "spd_model_assim_reset", &spd_model::assim, kAssimOff)) return rc;
     m->assim.skipped = 0;
     return SPD_OK;
 }

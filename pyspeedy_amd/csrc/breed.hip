@@ -781,11 +781,7 @@ int spd_model_breed_read(spd_model_handle m, int what, int t0, int nt, void *dst
 }
 
 int spd_model_breed_rows(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_breed_rows: null model");
-    const spd_model::Breed &br = m->breed;
-    if (!br.on) return m_fail(SPD_E_ARG, std::string("spd_model_breed_rows: ") + kBreedOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_breed_rows: bad destination");
-    return br.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_breed_rows", &spd_model::breed, kBreedOff, rows, max_rows);
 }
 
 int spd_model_breed_reset(spd_model_handle m) {

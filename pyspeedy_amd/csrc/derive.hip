@@ -201,7 +201,7 @@ int spd_model_derive_compute(spd_model_handle m, const char *const *names, int n
             if (n > 0 || !derive_on_plev(v)) asked |= 1 << v;
     for (int k = 0; k < n_names; ++k)
         if (n == 0 && derive_on_plev(derive_id(names[k])))
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+            return levels_first(who, names[k]);
     M_HIP(hipSetDevice(m->ctx->device));
     spd_model::Derive &dr = m->derive;
     const size_t M = static_cast<size_t>(m->M);
@@ -275,7 +275,7 @@ int spd_model_derive_read(spd_model_handle m, const char *name, int first, int c
     if (int rc = member_range(m, first, count, who)) return rc;
     const spd_model::Derive &dr = m->derive;
     if (derive_on_plev(v) && m->plev.n == 0)
-        return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' needs target levels (spd_model_plev_configure) first");
+        return levels_first(who, name);
     if (!dr.have[v]) return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' has not been computed (spd_model_derive_compute)");
     const size_t per = static_cast<size_t>(derive_name_levels(v, m->plev.n)) * NG, need = static_cast<size_t>(count) * per * sizeof(double);
     if (dst_bytes < need) return m_fail(SPD_E_SIZE, std::string(who) + ": destination too small (" + std::to_string(need) + " bytes needed)");

@@ -180,7 +180,7 @@ int spd_model_enstape_configure(spd_model_handle m, const char *const *names, in
     if (int rc = configure_allowed(m, who)) return rc;
     for (size_t k = 0; k < ids.size(); ++k)
         if (cat_needs_levels(ids[k]) && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+            return levels_first(who, names[k]);
     spd_model::EnsTape &et = m->enstape;
     if (int rc = retire(m, et)) return rc;
     if (n_names == 0) return SPD_OK;  // off
@@ -231,12 +231,7 @@ int spd_model_enstape_configure(spd_model_handle m, const char *const *names, in
 }
 
 int spd_model_enstape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: null model");
-    if (!m->enstape.on) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: no ensemble tape configured (spd_model_enstape_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_enstape_reset: a checked multi-step call is in flight; end it first");
-    m->enstape.ring.clear();  // (the next sample opens the partials of slot 0 anew)
-    m->enstape.validity.clear();
-    return SPD_OK;
+    return ring_reset(m, "spd_model_enstape_reset", &spd_model::enstape, "no ensemble tape configured (spd_model_enstape_configure)");
 }
 
 int spd_model_enstape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *members) {
@@ -252,11 +247,7 @@ int spd_model_enstape_info(spd_model_handle m, long long *taken, int *held, int 
 }
 
 int spd_model_enstape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_enstape_times: null model");
-    const spd_model::EnsTape &et = m->enstape;
-    if (!et.on) return m_fail(SPD_E_ARG, "spd_model_enstape_times: no ensemble tape configured (spd_model_enstape_configure)");
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_enstape_times: bad destination");
-    return et.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_enstape_times", &spd_model::enstape, "no ensemble tape configured (spd_model_enstape_configure)", rows, max_rows);
 }
 
 int spd_model_enstape_read(spd_model_handle m, const char *name, int kind, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {

@@ -316,11 +316,8 @@ namespace spd {
 int sample_ids(const char *who, const char *const *names, int n_names, std::vector<int> &ids) {
     if (n_names < 0 || (n_names > 0 && !names)) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of variable names");
     for (int k = 0; k < n_names; ++k) {
-        const int id = names[k] ? stats_id(names[k]) : -1;
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                         "q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
+        const int id = entry_id(who, names[k], SPD_CATALOGUE_LIST);
+        if (id < 0) return SPD_E_ARG;
         if (std::find(ids.begin(), ids.end(), id) != ids.end())
             return m_fail(SPD_E_ARG, std::string(who) + ": variable '" + names[k] + "' named twice");
         ids.push_back(id);

@@ -34,6 +34,7 @@
 #include "verif.hpp"
 #include "qtape.hpp"
 #include "ring.hpp"
+#include "entry_front.hpp"
 #include "surface.hpp"
 
 using namespace spd;  // (every file that includes this header is written inside or against namespace spd)
@@ -41,6 +42,11 @@ using namespace spd;  // (every file that includes this header is written inside
 namespace spd {
 constexpr int NG = IX * IL;
 constexpr size_t C = 2;  // doubles per complex
+
+// an entry of the projection tape, the assimilation and the verification tape: a plane under a weight map
+struct PatternEntry {
+    int name, level, pattern;  // name: catalogue id
+};
 
 struct RegEntry {
     void *ptr;            // device base
@@ -320,14 +326,11 @@ struct spd_model {
     // tables, the descriptors of the distinct planes and the entry list sorted by plane (projtape.hpp).  Slots, and the step and
     // date of each sample: `ring`.
     struct ProjTape : SampleFront {
-        struct Entry {
-            int name, level, pattern;  // name: catalogue id
-        };
         bool on = false;
         int every = 1, npatterns = 0, nplanes = 0;
         SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
         Validity validity;
-        std::vector<Entry> entries;
+        std::vector<PatternEntry> entries;
         void *alloc = nullptr;
         double *data = nullptr, *weights = nullptr;
         ProjTapePlane *planes = nullptr;
@@ -392,18 +395,14 @@ struct spd_model {
     // the one-slot projection ring [M][E] (`yraw`), Y [E][r], W [64][64], the member list and the transform's plane descriptors.
     // The observation table is host state: the row of an event travels to the weights kernel by value.
     struct Assim : SampleFront {
-        struct Entry {
-            int name, level, pattern;  // name: catalogue id
-        };
         bool on = false, in_loop = false;
         int every = 0, npatterns = 0, nplanes = 0, r = 0;
         double inflation = 1.0;
         SampleRing ring;  // of executed events since _configure / _reset; rows [6]: step counter, y, m, d, h, min of an event's state
         Validity validity;
         long long applied = 0, skipped = 0;  // events executed since _configure; in-loop events without a row since _configure / _reset
-        std::vector<Entry> entries;
-        std::vector<int> members;                   // a_0 < ... < a_(r-1)
-        std::vector<std::pair<int, int>> ranges;    // the masked members as (first, count) of consecutive indices
+        std::vector<PatternEntry> entries;
+        MemberSet set;                              // the masked members (r of them) and their runs
         std::vector<int> obs_steps;                 // [T], strictly ascending
         std::vector<double> obs_yo, obs_var;        // [T][E]
         void *alloc = nullptr;
@@ -423,17 +422,13 @@ struct spd_model {
     // distinct planes' sources, the entry list, the member list, and the point kernel's scratch [planes][4][4608] doubles
     // (`point`) and [planes][4608] int32 (`bin`).
     struct Verif : SampleFront {
-        struct Entry {
-            int name, level, pattern;  // name: catalogue id
-        };
         bool on = false, in_loop = false;
         int every = 0, npatterns = 0, nplanes = 0, r = 0, truth = -1;
         SampleRing ring;  // of events since _configure / _reset; rows [7]: step counter, y, m, d, h, min of the state, analysis (0 / 1)
         Validity validity;
         long long applied = 0;  // events recorded since _configure: in-loop ones and calls of _apply
-        std::vector<Entry> entries;
-        std::vector<int> members;                 // a_0 < ... < a_(r-1)
-        std::vector<std::pair<int, int>> ranges;  // the masked members and the truth as (first, count) of consecutive indices
+        std::vector<PatternEntry> entries;
+        MemberSet set;  // the masked members (r of them); the runs cover the truth as well
         void *alloc = nullptr;
         double *data = nullptr, *weights = nullptr, *point = nullptr;
         int *counts = nullptr, *bin = nullptr, *member_list = nullptr;
@@ -459,8 +454,7 @@ struct spd_model {
         Validity validity;
         long long applied = 0;  // events recorded since _configure: in-loop ones and calls of _apply
         std::vector<Entry> entries;
-        std::vector<int> members;                 // a_0 < ... < a_(r-1)
-        std::vector<std::pair<int, int>> ranges;  // the masked members as (first, count) of consecutive indices
+        MemberSet set;  // the masked members (r of them) and their runs
         void *alloc = nullptr;
         double *data = nullptr;
         int *member_list = nullptr;
@@ -669,6 +663,110 @@ inline void carve_front(Carve &carve, const SamplePlan &plan, spd_model::SampleF
     front.slab = carve.take<double>(plan.slab_bytes);
     front.table[0] = carve.take<FieldDesc>(plan.table_bytes);
     front.table[1] = carve.take<FieldDesc>(plan.table_bytes);
+}
+
+// ---- the entry recorders (projection tape, assimilation, verification tape, quantile tape): the checks of their lists, one per
+// check so that each _configure keeps its documented order; the tables built from the lists are entry_front.hpp's ----
+#define SPD_CATALOGUE_LIST \
+    "u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, q_plev, z_plev, mslp)" SPD_DERIVED_TAIL
+// the catalogue id of an entry's name, or -1 behind m_fail; list: the names the recorder takes, from behind the opening bracket
+inline int entry_id(const char *who, const char *name, const char *list) {
+    const int id = name ? stats_id(name) : -1;
+    if (id < 0) m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (name ? name : "(null)") + "' (" + list);
+    return id;
+}
+inline std::string entry_text(int k, const char *name) { return "entry " + std::to_string(k) + " ('" + name + "')"; }
+// (against the name's fixed count; a pressure-level name's count is the model's: check_plev_entries)
+inline int check_entry_level(const char *who, int k, const char *name, int id, int level) {
+    const int fixed = kStatsCatalogue[id].levels;
+    if (level < 0 || (fixed > 0 && level >= fixed))
+        return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(level) + " of " + entry_text(k, name) + " is out of range" +
+                                     (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
+    return SPD_OK;
+}
+inline int check_entry_pattern(const char *who, int k, const char *name, int pattern, int n_patterns) {
+    if (pattern < 0 || pattern >= n_patterns)
+        return m_fail(SPD_E_ARG, std::string(who) + ": pattern " + std::to_string(pattern) + " of " + entry_text(k, name) +
+                                     " is out of range (0 ... " + std::to_string(n_patterns - 1) + ")");
+    return SPD_OK;
+}
+// weights: [n_patterns][4608], finite
+inline int check_weight_maps(const char *who, const double *weights, int n_patterns) {
+    for (int p = 0; p < n_patterns; ++p)
+        for (int q = 0; q < NG; ++q)
+            if (!std::isfinite(weights[static_cast<size_t>(p) * NG + q]))
+                return m_fail(SPD_E_ARG, std::string(who) + ": weight of pattern " + std::to_string(p) + " at point " + std::to_string(q) + " (row " +
+                                             std::to_string(q / IX) + ", column " + std::to_string(q % IX) + ") is not finite");
+    return SPD_OK;
+}
+// mask: [members] of 0 / 1 with 2 ... max ones; takes: who takes that many ("the scores take")
+inline int check_member_mask(const char *who, const int32_t *mask, int members, int max, const char *takes) {
+    int r = 0;
+    for (int i = 0; i < members; ++i) {
+        if (mask[i] != 0 && mask[i] != 1)
+            return m_fail(SPD_E_ARG, std::string(who) + ": the mask of member " + std::to_string(i) + " (" + std::to_string(mask[i]) + ") is not 0 or 1");
+        r += mask[i];
+    }
+    if (r < 2 || r > max)
+        return m_fail(SPD_E_ARG, std::string(who) + ": " + std::to_string(r) + " members are masked in: " + takes + " 2 ... " + std::to_string(max));
+    return SPD_OK;
+}
+// a name on the target levels of spd_model_plev_configure while there are none
+inline int levels_first(const char *who, const char *name) {
+    return m_fail(SPD_E_ARG, std::string(who) + ": '" + name + "' needs target levels (spd_model_plev_configure) first");
+}
+// once the model is known: the entries on the target levels of spd_model_plev_configure (entries: anything with .name and .level)
+template <class Entry>
+int check_plev_entries(const spd_model *m, const char *who, const char *const *names, const std::vector<Entry> &entries) {
+    for (size_t k = 0; k < entries.size(); ++k) {
+        if (!cat_needs_levels(entries[k].name)) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
+        if (m->plev.n == 0) return levels_first(who, names[k]);
+        if (kStatsCatalogue[entries[k].name].levels == 0 && entries[k].level >= m->plev.n)
+            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(entries[k].level) + " of " + entry_text(static_cast<int>(k), names[k]) +
+                                         " is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
+    }
+    return SPD_OK;
+}
+// where a plane of a planned name is read from; sources: as build_sample_front left them
+inline const SampleSource &plane_source(const SamplePlan &plan, const std::vector<SampleSource> &sources, int name, int level) {
+    const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == name; });
+    return sources[var->first_plane + static_cast<size_t>(level)];
+}
+// a call that reads or moves the state of a model that is there: usable, the feature on, initialised, no checked call in flight
+inline int state_call_allowed(const spd_model *m, const char *who, bool on, const char *off) {
+    if (int rc = usable(m, who)) return rc;
+    if (!on) return m_fail(SPD_E_ARG, std::string(who) + ": " + off);
+    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    return SPD_OK;
+}
+// _reset and _rows / _times of a ring recorder (`feature`: its member of spd_model, with on, ring and validity); no device work
+template <class Feature>
+int ring_reset(spd_model *m, const char *who, Feature spd_model::*feature, const char *off) {
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (!(m->*feature).on) return m_fail(SPD_E_ARG, std::string(who) + ": " + off);
+    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
+    (m->*feature).ring.clear();
+    (m->*feature).validity.clear();
+    return SPD_OK;
+}
+template <class Feature>
+int ring_rows(const spd_model *m, const char *who, Feature spd_model::*feature, const char *off, int32_t *rows, int max_rows) {
+    if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
+    if (!(m->*feature).on) return m_fail(SPD_E_ARG, std::string(who) + ": " + off);
+    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, std::string(who) + ": bad destination");
+    return (m->*feature).ring.copy_rows(rows, max_rows);
+}
+// The held slots [t0, t0 + nt) of a ring [slot][slot_stride] into dst [members][nt][per]: of each slot, `members` runs of `per`
+// doubles from ring_base on, one behind the other (the spectra's gather; a ring of one block per slot is one "member")
+inline int gather_slots(const spd_model *m, const char *who, const double *ring_base, size_t per, size_t slot_stride, int members, int t0, int nt,
+                        const SampleRing &ring, void *dst, void *stream) {
+    if (members == 0 || nt == 0) return SPD_OK;
+    M_HIP(hipSetDevice(m->ctx->device));
+    const hipError_t e = run_spectra_gather(ring_base, static_cast<double *>(dst), static_cast<int>(per), static_cast<long>(slot_stride), members, nt,
+                                            ring.slot_of_held(t0), ring.capacity, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    return SPD_OK;
 }
 
 }  // namespace spd

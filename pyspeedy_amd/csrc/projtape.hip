@@ -122,7 +122,7 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
                                  const int *patterns, int n_entries, int every, int capacity) {
     const char *who = "spd_model_projtape_configure";
     // (the arguments first, in the header's order: nothing in this block needs the device or a model; n_entries = 0 is "off")
-    std::vector<spd_model::ProjTape::Entry> entries;
+    std::vector<PatternEntry> entries;
     if (n_entries != 0) {
         if (every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": every must be at least 1");
         if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
@@ -134,38 +134,19 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
                                          std::to_string(n_entries));
         if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
         if (!names || !levels || !patterns) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
-        for (int p = 0; p < n_patterns; ++p)
-            for (int q = 0; q < NG; ++q)
-                if (!std::isfinite(weights[static_cast<size_t>(p) * NG + q]))
-                    return m_fail(SPD_E_ARG, std::string(who) + ": weight of pattern " + std::to_string(p) + " at point " + std::to_string(q) +
-                                                 " (row " + std::to_string(q / IX) + ", column " + std::to_string(q % IX) + ") is not finite");
+        if (int rc = check_weight_maps(who, weights, n_patterns)) return rc;
         for (int k = 0; k < n_entries; ++k) {
-            const int id = names[k] ? stats_id(names[k]) : -1;
-            if (id < 0)
-                return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                             "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                             "q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
+            const int id = entry_id(who, names[k], SPD_CATALOGUE_LIST);
+            if (id < 0) return SPD_E_ARG;
             entries.push_back({id, levels[k], patterns[k]});
         }
-        // (a level is checked here against the name's fixed count; a pressure-level name's count is the model's, below)
         for (int k = 0; k < n_entries; ++k) {
-            const int fixed = kStatsCatalogue[entries[k].name].levels;
-            if (levels[k] < 0 || (fixed > 0 && levels[k] >= fixed))
-                return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
-                                             names[k] + "') is out of range" + (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
-            if (patterns[k] < 0 || patterns[k] >= n_patterns)
-                return m_fail(SPD_E_ARG, std::string(who) + ": pattern " + std::to_string(patterns[k]) + " of entry " + std::to_string(k) + " ('" +
-                                             names[k] + "') is out of range (0 ... " + std::to_string(n_patterns - 1) + ")");
+            if (int rc = check_entry_level(who, k, names[k], entries[k].name, levels[k])) return rc;
+            if (int rc = check_entry_pattern(who, k, names[k], patterns[k], n_patterns)) return rc;
         }
     }
     if (int rc = configure_allowed(m, who)) return rc;
-    for (int k = 0; k < n_entries; ++k) {
-        if (!cat_needs_levels(entries[k].name)) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
-        if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-        if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" +
-                                         names[k] + "') is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
-    }
+    if (int rc = check_plev_entries(m, who, names, entries)) return rc;
     spd_model::ProjTape &pt = m->projtape;
     if (int rc = retire(m, pt)) return rc;
     if (n_entries == 0) return SPD_OK;  // off
@@ -173,26 +154,16 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
     next.every = every;
     next.npatterns = n_patterns;
     const size_t M = static_cast<size_t>(m->M), slots = static_cast<size_t>(capacity), E = static_cast<size_t>(n_entries);
-    // the sample plan: the names among the entries in the order they first appear (the front end transforms a name's every level)
-    std::vector<int> ids;
-    for (const auto &e : entries)
-        if (std::find(ids.begin(), ids.end(), e.name) == ids.end()) ids.push_back(e.name);
+    // the sample plan over the names among the entries (the front end transforms a name's every level), and the entries sorted by
+    // distinct plane (stable: the caller's order within a plane)
+    const EntryPlanes table = entry_planes(entries);
     SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    // the distinct planes in the order they first appear, and the entries sorted by plane (stable: the caller's order within a plane)
-    std::vector<std::pair<int, int>> distinct;  // (name, level)
-    std::vector<int> plane_of(E);
-    for (size_t k = 0; k < E; ++k) {
-        const std::pair<int, int> key{entries[k].name, entries[k].level};
-        const auto at = std::find(distinct.begin(), distinct.end(), key);
-        plane_of[k] = static_cast<int>(at - distinct.begin());
-        if (at == distinct.end()) distinct.push_back(key);
-    }
+    plan_sample(m, table.ids, next, plan);
     // one allocation: ring | patterns | slab | tables[2] | plane descriptors | entry list
     const size_t per_slot = M * E * sizeof(double);
     if (slots > (static_cast<size_t>(-1) / 2) / per_slot) return m_fail(SPD_E_ARG, std::string(who) + ": the size of the series does not fit size_t");
     const size_t ring = sample_up(slots * per_slot), maps = sample_up(static_cast<size_t>(n_patterns) * NG * sizeof(double));
-    const size_t desc = sample_up(distinct.size() * sizeof(ProjTapePlane)), list = sample_up(E * sizeof(ProjTapeItem));
+    const size_t desc = sample_up(table.distinct.size() * sizeof(ProjTapePlane)), list = sample_up(E * sizeof(ProjTapeItem));
     const size_t total = ring + maps + plan.slab_bytes + 2 * plan.table_bytes + desc + list;
     void *p = nullptr;
     if (hipMalloc(&p, total) != hipSuccess) {  // the projection tape is off; the model is as usable as before
@@ -212,14 +183,11 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
     hipError_t e = build_sample_front(m, plan, next, sources);
     std::vector<ProjTapePlane> host_planes;
     std::vector<ProjTapeItem> host_items;
-    for (size_t q = 0; q < distinct.size(); ++q) {
-        const int id = distinct[q].first, level = distinct[q].second;
-        const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == id; });
+    for (size_t q = 0; q < table.distinct.size(); ++q) {
         ProjTapePlane d{};
-        d.source = sources[var->first_plane + static_cast<size_t>(level)];
+        d.source = plane_source(plan, sources, table.distinct[q].first, table.distinct[q].second);
         d.first = static_cast<int>(host_items.size());
-        for (size_t k = 0; k < E; ++k)
-            if (plane_of[k] == static_cast<int>(q)) host_items.push_back({entries[k].pattern, static_cast<int>(k)});
+        table.each_entry_of(q, [&](int k) { host_items.push_back({entries[k].pattern, k}); });
         d.count = static_cast<int>(host_items.size()) - d.first;
         host_planes.push_back(d);
     }
@@ -235,14 +203,7 @@ int spd_model_projtape_configure(spd_model_handle m, const double *weights, int 
     return SPD_OK;
 }
 
-int spd_model_projtape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: null model");
-    if (!m->projtape.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_reset: ") + kProjOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_projtape_reset: a checked multi-step call is in flight; end it first");
-    m->projtape.ring.clear();
-    m->projtape.validity.clear();
-    return SPD_OK;
-}
+int spd_model_projtape_reset(spd_model_handle m) { return ring_reset(m, "spd_model_projtape_reset", &spd_model::projtape, kProjOff); }
 
 int spd_model_projtape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *n_patterns, int *n_entries) {
     if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_info: null model");
@@ -258,11 +219,7 @@ int spd_model_projtape_info(spd_model_handle m, long long *taken, int *held, int
 }
 
 int spd_model_projtape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_projtape_times: null model");
-    const spd_model::ProjTape &pt = m->projtape;
-    if (!pt.on) return m_fail(SPD_E_ARG, std::string("spd_model_projtape_times: ") + kProjOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_projtape_times: bad destination");
-    return pt.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_projtape_times", &spd_model::projtape, kProjOff, rows, max_rows);
 }
 
 int spd_model_projtape_read(spd_model_handle m, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
@@ -275,14 +232,8 @@ int spd_model_projtape_read(spd_model_handle m, int first, int count, int t0, in
     const size_t per = pt.entries.size();
     const size_t need = static_cast<size_t>(count) * static_cast<size_t>(nt) * per * sizeof(double);
     if (int rc = destination_fits(who, dst_device, dst_bytes, need, sizeof(double))) return rc;
-    if (count == 0 || nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
     // (the ring is [slot][M][E] as a spectra ring is [slot][M][per]: the same gather)
-    const hipError_t e = run_spectra_gather(pt.data + static_cast<size_t>(first) * per, static_cast<double *>(dst_device), static_cast<int>(per),
-                                            static_cast<long>(static_cast<size_t>(m->M) * per), count, nt, pt.ring.slot_of_held(t0),
-                                            pt.ring.capacity, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
+    return gather_slots(m, who, pt.data + static_cast<size_t>(first) * per, per, static_cast<size_t>(m->M) * per, count, t0, nt, pt.ring, dst_device, stream);
 }
 
 }  // extern "C"

@@ -99,7 +99,7 @@ const char *const kQtapeInvalid = "the quantile tape is invalid until spd_model_
 hipError_t qtape_planes(spd_model *m, double *out, hipStream_t s) {
     const spd_model::Qtape &qt = m->qtape;
     hipError_t e = hipSuccess;
-    for (const auto &range : qt.ranges)
+    for (const auto &range : qt.set.ranges)
         if (e == hipSuccess) e = sample_front(m, qt, range.first, range.second, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(qtape_point_kernel, dim3(kTiles, qt.nplanes), dim3(kT), 0, s, qt.planes, qt.items, qt.member_list, qt.r, qt.slab,
@@ -107,15 +107,6 @@ hipError_t qtape_planes(spd_model *m, double *out, hipStream_t s) {
         e = hipGetLastError();
     }
     return e;
-}
-
-// a call that reads the state of a model that is there
-int qtape_call_allowed(const spd_model *m, const char *who) {
-    if (int rc = usable(m, who)) return rc;
-    if (!m->qtape.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kQtapeOff);
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    return SPD_OK;
 }
 static_assert(SPD_Q_MIN == kQtapeMin && SPD_Q_MAX == kQtapeMaxOp && SPD_Q_QUANTILE == kQtapeQuantile && SPD_Q_PROB_ABOVE == kQtapeProbAbove &&
                   SPD_Q_PROB_BELOW == kQtapeProbBelow,
@@ -150,16 +141,10 @@ int spd_qtape_check(const char *const *names, const int *levels, const int *ops,
                                      std::to_string(n_entries));
     if (!names || !levels || !ops || !params) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
     for (int k = 0; k < n_entries; ++k) {
-        const int id = names[k] ? stats_id(names[k]) : -1;
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                         "q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
-        const int fixed = kStatsCatalogue[id].levels;
-        const std::string entry = "entry " + std::to_string(k) + " ('" + names[k] + "')";
-        if (levels[k] < 0 || (fixed > 0 && levels[k] >= fixed))
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of " + entry + " is out of range" +
-                                         (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
+        const int id = entry_id(who, names[k], SPD_CATALOGUE_LIST);
+        if (id < 0) return SPD_E_ARG;
+        if (int rc = check_entry_level(who, k, names[k], id, levels[k])) return rc;
+        const std::string entry = entry_text(k, names[k]);
         if (ops[k] < SPD_Q_MIN || ops[k] > SPD_Q_PROB_BELOW)
             return m_fail(SPD_E_ARG, std::string(who) + ": unknown op " + std::to_string(ops[k]) + " of " + entry +
                                          " (SPD_Q_MIN 0, SPD_Q_MAX 1, SPD_Q_QUANTILE 2, SPD_Q_PROB_ABOVE 3, SPD_Q_PROB_BELOW 4)");
@@ -168,17 +153,8 @@ int spd_qtape_check(const char *const *names, const int *levels, const int *ops,
         if ((ops[k] == SPD_Q_PROB_ABOVE || ops[k] == SPD_Q_PROB_BELOW) && !std::isfinite(params[k]))
             return m_fail(SPD_E_ARG, std::string(who) + ": the threshold of " + entry + " is not finite");
     }
-    if (!mask) return SPD_OK;  // (the member mask needs the member count: checked once the model is known)
-    int r = 0;
-    for (int i = 0; i < members; ++i) {
-        if (mask[i] != 0 && mask[i] != 1)
-            return m_fail(SPD_E_ARG, std::string(who) + ": the mask of member " + std::to_string(i) + " (" + std::to_string(mask[i]) + ") is not 0 or 1");
-        r += mask[i];
-    }
-    if (r < 2 || r > kQtapeMax)
-        return m_fail(SPD_E_ARG, std::string(who) + ": " + std::to_string(r) + " members are masked in: the order statistics take 2 ... " +
-                                     std::to_string(kQtapeMax));
-    return SPD_OK;
+    // (the member mask needs the member count: checked once the model is known)
+    return mask ? check_member_mask(who, mask, members, kQtapeMax, "the order statistics take") : SPD_OK;
 }
 
 int spd_model_qtape_configure(spd_model_handle m, const char *const *names, const int *levels, const int *ops, const double *params, int n_entries,
@@ -190,42 +166,21 @@ int spd_model_qtape_configure(spd_model_handle m, const char *const *names, cons
     if (int rc = configure_allowed(m, who)) return rc;
     if (int rc = spd_qtape_check(names, levels, ops, params, n_entries, mask, m->M, every, capacity, in_loop)) return rc;
     std::vector<spd_model::Qtape::Entry> entries;
-    for (int k = 0; k < n_entries; ++k) {
-        entries.push_back({stats_id(names[k]), levels[k], ops[k], params[k]});
-        if (!cat_needs_levels(entries[k].name)) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
-        if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-        if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" + names[k] +
-                                         "') is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
-    }
+    for (int k = 0; k < n_entries; ++k) entries.push_back({stats_id(names[k]), levels[k], ops[k], params[k]});
+    if (int rc = check_plev_entries(m, who, names, entries)) return rc;
     spd_model::Qtape &qt = m->qtape;
     if (int rc = retire(m, qt)) return rc;
     spd_model::Qtape next;
     next.in_loop = in_loop != 0;
     next.every = every;
-    for (int i = 0; i < m->M; ++i) {
-        if (!mask[i]) continue;
-        next.members.push_back(i);
-        if (next.ranges.empty() || next.ranges.back().first + next.ranges.back().second != i) next.ranges.push_back({i, 0});
-        ++next.ranges.back().second;
-    }
-    next.r = static_cast<int>(next.members.size());
+    next.set = member_set(mask, m->M);
+    next.r = static_cast<int>(next.set.members.size());
     const size_t slots = static_cast<size_t>(capacity), E = static_cast<size_t>(n_entries);
-    // the sample plan and the distinct planes, as spd_model_verif_configure builds them
-    std::vector<int> ids;
-    for (const auto &e : entries)
-        if (std::find(ids.begin(), ids.end(), e.name) == ids.end()) ids.push_back(e.name);
+    // the sample plan and the distinct planes with their entries, as the projection tape builds them
+    const EntryPlanes table = entry_planes(entries);
     SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    std::vector<std::pair<int, int>> distinct;  // (name, level)
-    std::vector<int> plane_of;
-    for (size_t k = 0; k < E; ++k) {
-        const std::pair<int, int> key{entries[k].name, entries[k].level};
-        const auto at = std::find(distinct.begin(), distinct.end(), key);
-        plane_of.push_back(static_cast<int>(at - distinct.begin()));
-        if (at == distinct.end()) distinct.push_back(key);
-    }
-    const size_t P = distinct.size();
+    plan_sample(m, table.ids, next, plan);
+    const size_t P = table.distinct.size();
     // one allocation: ring | slab | tables[2] | planes | entry descriptors | member list
     const size_t per_slot = E * NG * sizeof(double);
     if (slots > (static_cast<size_t>(-1) / 2) / per_slot) return m_fail(SPD_E_ARG, std::string(who) + ": the ring's size does not fit size_t");
@@ -252,20 +207,18 @@ int spd_model_qtape_configure(spd_model_handle m, const char *const *names, cons
     std::vector<QtapePlane> host_planes;
     std::vector<QtapeItem> host_items;
     for (size_t q = 0; q < P; ++q) {
-        const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == distinct[q].first; });
-        QtapePlane plane{sources[var->first_plane + static_cast<size_t>(distinct[q].second)], static_cast<int>(host_items.size()), 0};
-        for (size_t k = 0; k < E; ++k) {
-            if (plane_of[k] != static_cast<int>(q)) continue;
+        QtapePlane plane{plane_source(plan, sources, table.distinct[q].first, table.distinct[q].second), static_cast<int>(host_items.size()), 0};
+        table.each_entry_of(q, [&](int k) {
             QtapeItem it = qtape_item(entries[k].op, entries[k].param, next.r);
-            it.entry = static_cast<int>(k);
+            it.entry = k;
             host_items.push_back(it);
             ++plane.count;
-        }
+        });
         host_planes.push_back(plane);
     }
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(QtapePlane), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(next.items, host_items.data(), host_items.size() * sizeof(QtapeItem), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(next.member_list, next.members.data(), next.members.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.member_list, next.set.members.data(), next.set.members.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return upload_failed(who, e, p);
     next.nplanes = static_cast<int>(host_planes.size());
@@ -282,19 +235,12 @@ int spd_model_qtape_off(spd_model_handle m) {
     return retire(m, m->qtape);
 }
 
-int spd_model_qtape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_qtape_reset: null model");
-    if (!m->qtape.on) return m_fail(SPD_E_ARG, std::string("spd_model_qtape_reset: ") + kQtapeOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_qtape_reset: a checked multi-step call is in flight; end it first");
-    m->qtape.ring.clear();
-    m->qtape.validity.clear();
-    return SPD_OK;
-}
+int spd_model_qtape_reset(spd_model_handle m) { return ring_reset(m, "spd_model_qtape_reset", &spd_model::qtape, kQtapeOff); }
 
 int spd_model_qtape_apply(spd_model_handle m, void *stream) {
     const char *who = "spd_model_qtape_apply";
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = qtape_call_allowed(m, who)) return rc;
+    if (int rc = state_call_allowed(m, who, m->qtape.on, kQtapeOff)) return rc;
     M_HIP(hipSetDevice(m->ctx->device));
     return qtape_event(m, static_cast<hipStream_t>(stream), who);
 }
@@ -302,7 +248,7 @@ int spd_model_qtape_apply(spd_model_handle m, void *stream) {
 int spd_model_qtape_compute(spd_model_handle m, void *dst_device, size_t dst_bytes, void *stream) {
     const char *who = "spd_model_qtape_compute";
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = qtape_call_allowed(m, who)) return rc;
+    if (int rc = state_call_allowed(m, who, m->qtape.on, kQtapeOff)) return rc;
     if (int rc = destination_fits(who, dst_device, dst_bytes, m->qtape.entries.size() * NG * sizeof(double), sizeof(double))) return rc;
     M_HIP(hipSetDevice(m->ctx->device));
     const hipError_t e = qtape_planes(m, static_cast<double *>(dst_device), static_cast<hipStream_t>(stream));
@@ -323,21 +269,12 @@ int spd_model_qtape_read(spd_model_handle m, int entry, int t0, int nt, void *ds
         return m_fail(SPD_E_ARG, std::string(who) + ": entry " + std::to_string(entry) + " is out of range (0 ... " + std::to_string(E - 1) + ")");
     if (int rc = held_range(who, qt.ring, t0, nt, "event")) return rc;
     if (int rc = destination_fits(who, dst_device, dst_bytes, static_cast<size_t>(nt) * NG * sizeof(double), sizeof(double))) return rc;
-    if (nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    // (the spectra's gather with one "member" whose values are the entry's plane: a strided device copy)
-    const hipError_t e = run_spectra_gather(qt.data + static_cast<size_t>(entry) * NG, static_cast<double *>(dst_device), NG, static_cast<long>(E) * NG, 1,
-                                            nt, qt.ring.slot_of_held(t0), qt.ring.capacity, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
+    // (one "member" whose values are the entry's plane: a strided device copy)
+    return gather_slots(m, who, qt.data + static_cast<size_t>(entry) * NG, NG, static_cast<size_t>(E) * NG, 1, t0, nt, qt.ring, dst_device, stream);
 }
 
 int spd_model_qtape_rows(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_qtape_rows: null model");
-    const spd_model::Qtape &qt = m->qtape;
-    if (!qt.on) return m_fail(SPD_E_ARG, std::string("spd_model_qtape_rows: ") + kQtapeOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_qtape_rows: bad destination");
-    return qt.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_qtape_rows", &spd_model::qtape, kQtapeOff, rows, max_rows);
 }
 
 int spd_model_qtape_info(spd_model_handle m, int *r, int *n_entries, int *every, int *capacity, long long *taken, int *in_loop, long long *applied) {

@@ -211,12 +211,7 @@ int spd_model_spectra_configure(spd_model_handle m, const char *const *names, in
 }
 
 int spd_model_spectra_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: null model");
-    if (!m->spectra.on) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: no spectra configured (spd_model_spectra_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_spectra_reset: a checked multi-step call is in flight; end it first");
-    m->spectra.ring.clear();
-    m->spectra.validity.clear();
-    return SPD_OK;
+    return ring_reset(m, "spd_model_spectra_reset", &spd_model::spectra, "no spectra configured (spd_model_spectra_configure)");
 }
 
 int spd_model_spectra_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every) {
@@ -231,11 +226,7 @@ int spd_model_spectra_info(spd_model_handle m, long long *taken, int *held, int 
 }
 
 int spd_model_spectra_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_spectra_times: null model");
-    const spd_model::Spectra &sp = m->spectra;
-    if (!sp.on) return m_fail(SPD_E_ARG, "spd_model_spectra_times: no spectra configured (spd_model_spectra_configure)");
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_spectra_times: bad destination");
-    return sp.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_spectra_times", &spd_model::spectra, "no spectra configured (spd_model_spectra_configure)", rows, max_rows);
 }
 
 int spd_model_spectra_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,

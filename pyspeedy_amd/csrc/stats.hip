@@ -116,7 +116,7 @@ int spd_model_stats_configure(spd_model_handle m, const char *const *names, int 
     if (int rc = configure_allowed(m, who)) return rc;
     for (size_t k = 0; k < ids.size(); ++k)
         if (cat_needs_levels(ids[k]) && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+            return levels_first(who, names[k]);
     spd_model::Stats &st = m->stats;
     if (int rc = retire(m, st)) return rc;
     if (n_names == 0) return SPD_OK;  // off

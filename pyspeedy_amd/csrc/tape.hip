@@ -111,7 +111,7 @@ int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n
     if (int rc = configure_allowed(m, who)) return rc;
     for (size_t k = 0; k < ids.size(); ++k)
         if (cat_needs_levels(ids[k]) && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+            return levels_first(who, names[k]);
     spd_model::Tape &tp = m->tape;
     if (int rc = retire(m, tp)) return rc;
     if (n_names == 0) return SPD_OK;  // off
@@ -162,12 +162,7 @@ int spd_model_tape_configure(spd_model_handle m, const char *const *names, int n
 }
 
 int spd_model_tape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_reset: null model");
-    if (!m->tape.on) return m_fail(SPD_E_ARG, "spd_model_tape_reset: no tape configured (spd_model_tape_configure)");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_tape_reset: a checked multi-step call is in flight; end it first");
-    m->tape.ring.clear();
-    m->tape.validity.clear();
-    return SPD_OK;
+    return ring_reset(m, "spd_model_tape_reset", &spd_model::tape, "no tape configured (spd_model_tape_configure)");
 }
 
 int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *dtype) {
@@ -183,11 +178,7 @@ int spd_model_tape_info(spd_model_handle m, long long *taken, int *held, int *ca
 }
 
 int spd_model_tape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_tape_times: null model");
-    const spd_model::Tape &tp = m->tape;
-    if (!tp.on) return m_fail(SPD_E_ARG, "spd_model_tape_times: no tape configured (spd_model_tape_configure)");
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_tape_times: bad destination");
-    return tp.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_tape_times", &spd_model::tape, "no tape configured (spd_model_tape_configure)", rows, max_rows);
 }
 
 int spd_model_tape_read(spd_model_handle m, const char *name, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,

@@ -142,7 +142,7 @@ hipError_t verif_scores(spd_model *m, double *scores, int *counts, bool blank, h
     const spd_model::Verif &vf = m->verif;
     const int E = static_cast<int>(vf.entries.size());
     hipError_t e = hipSuccess;
-    for (const auto &range : vf.ranges)
+    for (const auto &range : vf.set.ranges)
         if (e == hipSuccess) e = sample_front(m, vf, range.first, range.second, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(verif_point_kernel, dim3(kTiles, vf.nplanes), dim3(kT), 0, s, vf.planes, vf.member_list, vf.r, vf.truth, vf.slab,
@@ -154,15 +154,6 @@ hipError_t verif_scores(spd_model *m, double *scores, int *counts, bool blank, h
         e = hipGetLastError();
     }
     return e;
-}
-
-// a call that reads the state of a model that is there
-int verif_call_allowed(const spd_model *m, const char *who) {
-    if (int rc = usable(m, who)) return rc;
-    if (!m->verif.on) return m_fail(SPD_E_ARG, std::string(who) + ": " + kVerifOff);
-    if (!m->initialized) return m_fail(SPD_E_ARG, std::string(who) + ": model state not initialized");
-    if (m->steps_pending) return m_fail(SPD_E_ARG, std::string(who) + ": a checked multi-step call is in flight; end it first");
-    return SPD_OK;
 }
 }  // namespace
 
@@ -201,35 +192,15 @@ int spd_verif_check(const double *weights, int n_patterns, const char *const *na
                                      std::to_string(n_entries));
     if (!weights) return m_fail(SPD_E_ARG, std::string(who) + ": null weights");
     if (!names || !levels || !patterns) return m_fail(SPD_E_ARG, std::string(who) + ": bad list of entries");
-    for (int p = 0; p < n_patterns; ++p)
-        for (int q = 0; q < NG; ++q)
-            if (!std::isfinite(weights[static_cast<size_t>(p) * NG + q]))
-                return m_fail(SPD_E_ARG, std::string(who) + ": weight of pattern " + std::to_string(p) + " at point " + std::to_string(q) + " (row " +
-                                             std::to_string(q / IX) + ", column " + std::to_string(q % IX) + ") is not finite");
+    if (int rc = check_weight_maps(who, weights, n_patterns)) return rc;
     for (int k = 0; k < n_entries; ++k) {
-        const int id = names[k] ? stats_id(names[k]) : -1;
-        if (id < 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": unknown variable '" + (names[k] ? names[k] : "(null)") +
-                                         "' (u_grid, v_grid, t_grid, q_grid, phi_grid, ps_grid, precnv, precls, u_plev, v_plev, t_plev, "
-                                         "q_plev, z_plev, mslp)" SPD_DERIVED_TAIL);
-        const int fixed = kStatsCatalogue[id].levels;
-        if (levels[k] < 0 || (fixed > 0 && levels[k] >= fixed))
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" + names[k] +
-                                         "') is out of range" + (fixed > 0 ? " (0 ... " + std::to_string(fixed - 1) + ")" : ""));
-        if (patterns[k] < 0 || patterns[k] >= n_patterns)
-            return m_fail(SPD_E_ARG, std::string(who) + ": pattern " + std::to_string(patterns[k]) + " of entry " + std::to_string(k) + " ('" +
-                                         names[k] + "') is out of range (0 ... " + std::to_string(n_patterns - 1) + ")");
+        const int id = entry_id(who, names[k], SPD_CATALOGUE_LIST);
+        if (id < 0) return SPD_E_ARG;
+        if (int rc = check_entry_level(who, k, names[k], id, levels[k])) return rc;
+        if (int rc = check_entry_pattern(who, k, names[k], patterns[k], n_patterns)) return rc;
     }
     if (!mask) return SPD_OK;  // (the member mask needs the member count: checked once the model is known)
-    int r = 0;
-    for (int i = 0; i < members; ++i) {
-        if (mask[i] != 0 && mask[i] != 1)
-            return m_fail(SPD_E_ARG, std::string(who) + ": the mask of member " + std::to_string(i) + " (" + std::to_string(mask[i]) + ") is not 0 or 1");
-        r += mask[i];
-    }
-    if (r < 2 || r > kVerifMax)
-        return m_fail(SPD_E_ARG, std::string(who) + ": " + std::to_string(r) + " members are masked in: the scores take 2 ... " +
-                                     std::to_string(kVerifMax));
+    if (int rc = check_member_mask(who, mask, members, kVerifMax, "the scores take")) return rc;
     if (truth < 0 || truth >= members)
         return m_fail(SPD_E_ARG, std::string(who) + ": the truth member " + std::to_string(truth) + " is out of range (0 ... " +
                                      std::to_string(members - 1) + ")");
@@ -246,15 +217,9 @@ int spd_model_verif_configure(spd_model_handle m, const double *weights, int n_p
     if (!mask) return m_fail(SPD_E_ARG, std::string(who) + ": null member mask");
     if (int rc = configure_allowed(m, who)) return rc;
     if (int rc = spd_verif_check(weights, n_patterns, names, levels, patterns, n_entries, mask, m->M, truth, every, capacity, in_loop)) return rc;
-    std::vector<spd_model::Verif::Entry> entries;
-    for (int k = 0; k < n_entries; ++k) {
-        entries.push_back({stats_id(names[k]), levels[k], patterns[k]});
-        if (!cat_needs_levels(entries[k].name)) continue;  // (mslp, of one level, is the pressure-level kernel's as well)
-        if (m->plev.n == 0) return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
-        if (kStatsCatalogue[entries[k].name].levels == 0 && levels[k] >= m->plev.n)
-            return m_fail(SPD_E_ARG, std::string(who) + ": level " + std::to_string(levels[k]) + " of entry " + std::to_string(k) + " ('" + names[k] +
-                                         "') is out of range (0 ... " + std::to_string(m->plev.n - 1) + ")");
-    }
+    std::vector<PatternEntry> entries;
+    for (int k = 0; k < n_entries; ++k) entries.push_back({stats_id(names[k]), levels[k], patterns[k]});
+    if (int rc = check_plev_entries(m, who, names, entries)) return rc;
     spd_model::Verif &vf = m->verif;
     if (int rc = retire(m, vf)) return rc;
     spd_model::Verif next;
@@ -262,30 +227,16 @@ int spd_model_verif_configure(spd_model_handle m, const double *weights, int n_p
     next.every = every;
     next.npatterns = n_patterns;
     next.truth = truth;
-    for (int i = 0; i < m->M; ++i) {
-        if (mask[i]) next.members.push_back(i);
-        if (mask[i] || i == truth) {
-            if (next.ranges.empty() || next.ranges.back().first + next.ranges.back().second != i) next.ranges.push_back({i, 0});
-            ++next.ranges.back().second;
-        }
-    }
-    next.r = static_cast<int>(next.members.size());
+    next.set = member_set(mask, m->M, truth);  // (the front end prepares the truth's planes as well)
+    next.r = static_cast<int>(next.set.members.size());
     const size_t slots = static_cast<size_t>(capacity), E = static_cast<size_t>(n_entries);
-    // the sample plan and the distinct planes, as spd_model_projtape_configure builds them
-    std::vector<int> ids;
-    for (const auto &e : entries)
-        if (std::find(ids.begin(), ids.end(), e.name) == ids.end()) ids.push_back(e.name);
+    // the sample plan and the distinct planes, as the projection tape builds them; the entries stay in the caller's order
+    const EntryPlanes table = entry_planes(entries);
     SamplePlan plan;
-    plan_sample(m, ids, next, plan);
-    std::vector<std::pair<int, int>> distinct;  // (name, level)
+    plan_sample(m, table.ids, next, plan);
     std::vector<VerifItem> host_items;
-    for (size_t k = 0; k < E; ++k) {
-        const std::pair<int, int> key{entries[k].name, entries[k].level};
-        const auto at = std::find(distinct.begin(), distinct.end(), key);
-        host_items.push_back({static_cast<int>(at - distinct.begin()), entries[k].pattern});
-        if (at == distinct.end()) distinct.push_back(key);
-    }
-    const size_t P = distinct.size();
+    for (size_t k = 0; k < E; ++k) host_items.push_back({table.plane_of[k], entries[k].pattern});
+    const size_t P = table.distinct.size();
     // one allocation: score ring | count ring | patterns | slab | tables[2] | plane sources | entry list | member list | point | bin
     const size_t per_slot = 2 * E * 4 * sizeof(double), per_slot_counts = 2 * E * kVerifCounts * sizeof(int);
     if (slots > (static_cast<size_t>(-1) / 2) / per_slot_counts) return m_fail(SPD_E_ARG, std::string(who) + ": the ring's size does not fit size_t");
@@ -315,14 +266,11 @@ int spd_model_verif_configure(spd_model_handle m, const double *weights, int n_p
     std::vector<SampleSource> sources;  // (per plane of plan.vars, in their order)
     if (e == hipSuccess) e = build_sample_front(m, plan, next, sources);
     std::vector<SampleSource> host_planes;
-    for (const auto &key : distinct) {
-        const auto var = std::find_if(plan.vars.begin(), plan.vars.end(), [&](const SamplePlan::Var &v) { return v.id == key.first; });
-        host_planes.push_back(sources[var->first_plane + static_cast<size_t>(key.second)]);
-    }
+    for (const auto &key : table.distinct) host_planes.push_back(plane_source(plan, sources, key.first, key.second));
     if (e == hipSuccess) e = hipMemcpy(next.weights, weights, static_cast<size_t>(n_patterns) * NG * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(next.planes, host_planes.data(), host_planes.size() * sizeof(SampleSource), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(next.items, host_items.data(), host_items.size() * sizeof(VerifItem), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(next.member_list, next.members.data(), next.members.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(next.member_list, next.set.members.data(), next.set.members.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return upload_failed(who, e, p);
     next.nplanes = static_cast<int>(host_planes.size());
@@ -339,19 +287,12 @@ int spd_model_verif_off(spd_model_handle m) {
     return retire(m, m->verif);
 }
 
-int spd_model_verif_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_verif_reset: null model");
-    if (!m->verif.on) return m_fail(SPD_E_ARG, std::string("spd_model_verif_reset: ") + kVerifOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_verif_reset: a checked multi-step call is in flight; end it first");
-    m->verif.ring.clear();
-    m->verif.validity.clear();
-    return SPD_OK;
-}
+int spd_model_verif_reset(spd_model_handle m) { return ring_reset(m, "spd_model_verif_reset", &spd_model::verif, kVerifOff); }
 
 int spd_model_verif_apply(spd_model_handle m, void *stream) {
     const char *who = "spd_model_verif_apply";
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = verif_call_allowed(m, who)) return rc;
+    if (int rc = state_call_allowed(m, who, m->verif.on, kVerifOff)) return rc;
     M_HIP(hipSetDevice(m->ctx->device));
     return verif_event(m, static_cast<hipStream_t>(stream), who, 0);
 }
@@ -359,7 +300,7 @@ int spd_model_verif_apply(spd_model_handle m, void *stream) {
 int spd_model_verif_compute(spd_model_handle m, void *scores_device, size_t scores_bytes, void *hist_device, size_t hist_bytes, void *stream) {
     const char *who = "spd_model_verif_compute";
     if (!m) return m_fail(SPD_E_ARG, std::string(who) + ": null model");
-    if (int rc = verif_call_allowed(m, who)) return rc;
+    if (int rc = state_call_allowed(m, who, m->verif.on, kVerifOff)) return rc;
     const size_t E = m->verif.entries.size();
     if (int rc = destination_fits(who, scores_device, scores_bytes, E * 4 * sizeof(double), sizeof(double))) return rc;
     if (int rc = destination_fits(who, hist_device, hist_bytes, E * kVerifCounts * sizeof(int32_t), sizeof(int32_t))) return rc;
@@ -379,13 +320,7 @@ static int verif_gather(spd_model_handle m, const char *who, const void *ring, s
     if (int rc = read_allowed(m, who, vf.on, kVerifOff, vf.validity, kVerifInvalid)) return rc;
     if (int rc = held_range(who, vf.ring, t0, nt, "event")) return rc;
     if (int rc = destination_fits(who, dst_device, dst_bytes, static_cast<size_t>(nt) * per * sizeof(double), align)) return rc;
-    if (nt == 0) return SPD_OK;
-    M_HIP(hipSetDevice(m->ctx->device));
-    // (the spectra's gather with one "member" whose entry is the values of a slot)
-    const hipError_t e = run_spectra_gather(static_cast<const double *>(ring), static_cast<double *>(dst_device), static_cast<int>(per),
-                                            static_cast<long>(per), 1, nt, vf.ring.slot_of_held(t0), vf.ring.capacity, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return m_fail(SPD_E_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    return SPD_OK;
+    return gather_slots(m, who, static_cast<const double *>(ring), per, per, 1, t0, nt, vf.ring, dst_device, stream);
 }
 
 int spd_model_verif_read(spd_model_handle m, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream) {
@@ -404,11 +339,7 @@ int spd_model_verif_hist(spd_model_handle m, int t0, int nt, void *dst_device, s
 }
 
 int spd_model_verif_rows(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_verif_rows: null model");
-    const spd_model::Verif &vf = m->verif;
-    if (!vf.on) return m_fail(SPD_E_ARG, std::string("spd_model_verif_rows: ") + kVerifOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_verif_rows: bad destination");
-    return vf.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_verif_rows", &spd_model::verif, kVerifOff, rows, max_rows);
 }
 
 int spd_model_verif_info(spd_model_handle m, int *r, int *truth, int *n_entries, int *every, int *capacity, long long *taken, int *in_loop,

@@ -259,7 +259,7 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
     if (int rc = configure_allowed(m, who)) return rc;
     for (int k = 0; k < n_entries; ++k)
         if (win_needs_levels(entries[k].name) && m->plev.n == 0)
-            return m_fail(SPD_E_ARG, std::string(who) + ": '" + names[k] + "' needs target levels (spd_model_plev_configure) first");
+            return levels_first(who, names[k]);
     spd_model::WinTape &wt = m->wintape;
     if (int rc = retire(m, wt)) return rc;
     if (n_entries == 0) return SPD_OK;  // off
@@ -368,13 +368,9 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
 }
 
 int spd_model_wintape_reset(spd_model_handle m) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: null model");
-    if (!m->wintape.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_reset: ") + kWinOff);
-    if (m->steps_pending) return m_fail(SPD_E_ARG, "spd_model_wintape_reset: a checked multi-step call is in flight; end it first");
-    m->wintape.ring.clear();
+    if (int rc = ring_reset(m, "spd_model_wintape_reset", &spd_model::wintape, kWinOff)) return rc;
     m->wintape.window_start = -1;  // (the next window starts at the next step; its first sample overwrites the accumulators: no device work)
     m->wintape.samples = 0;
-    m->wintape.validity.clear();
     return SPD_OK;
 }
 
@@ -394,11 +390,7 @@ int spd_model_wintape_info(spd_model_handle m, long long *taken, int *held, int 
 }
 
 int spd_model_wintape_times(spd_model_handle m, int32_t *rows, int max_rows) {
-    if (!m) return m_fail(SPD_E_ARG, "spd_model_wintape_times: null model");
-    const spd_model::WinTape &wt = m->wintape;
-    if (!wt.on) return m_fail(SPD_E_ARG, std::string("spd_model_wintape_times: ") + kWinOff);
-    if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, "spd_model_wintape_times: bad destination");
-    return wt.ring.copy_rows(rows, max_rows);
+    return ring_rows(m, "spd_model_wintape_times", &spd_model::wintape, kWinOff, rows, max_rows);
 }
 
 int spd_model_wintape_read(spd_model_handle m, const char *name, int op, int first, int count, int t0, int nt, void *dst_device,

@@ -29,6 +29,40 @@ BC_MAP = (("orog", "orog"), ("fmask_orig", "lsm"), ("alb0", "alb"), ("veg_high",
           ("sst12", "sst"), ("sea_ice_frac12", "icec"))
 
 
+# ---- what the *_configure methods and the ring readers of EnsembleModel share ----
+def _c_array(ctype, values):
+    """a ctypes array of `values` (of one element where there are none: the library is never handed a null list)"""
+    values = list(values)
+    return (ctype * max(len(values), 1))(*values)
+
+
+def _c_names(names):
+    return _c_array(C.c_char_p, [n.encode() for n in names])
+
+
+def _pattern_rows(entries):
+    """the (name, level, pattern) entries of the projection tape, the assimilation and the verification tape"""
+    rows = []
+    for entry in entries:
+        if len(entry) != 3:
+            raise ValueError("an entry is (name, level, pattern), got %r" % (entry,))
+        rows.append((str(entry[0]), int(entry[1]), int(entry[2])))
+    return rows
+
+
+def _weight_maps(weights, checked=True):
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if checked and (w.ndim != 3 or w.shape[1:] != (48, 96)):
+        raise ValueError("weights must be [P][48][96], got shape %r" % (w.shape,))
+    return w
+
+
+def _held_span(info, t0, nt):
+    """(t0, nt) of a ring reader: nt = None is every held sample from t0 on"""
+    t0 = int(t0)
+    return t0, info["held"] - t0 if nt is None else int(nt)
+
+
 class EnsembleModel:
     def __init__(self, spectral, nmembers):
         self.sp = spectral
@@ -348,7 +382,7 @@ class EnsembleModel:
         run() / run_checked() calls of any length; per member and grid point the mean and, with `variance`, the unbiased time
         variance.  Starts a new averaging period; an empty list switches sampling off.  Synchronises the device."""
         names = [str(v) for v in variables]
-        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        arr = _c_names(names)
         check(self._lib.spd_model_stats_configure(self._m, arr, len(names), int(every), int(bool(variance))),
               "spd_model_stats_configure")
 
@@ -408,7 +442,7 @@ class EnsembleModel:
         if key not in self.TAPE_DTYPES:
             raise ValueError("dtype must be 'float32' or 'float64', got %r" % (dtype,))
         names = [str(v) for v in variables]
-        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        arr = _c_names(names)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_tape_configure(self._m, arr, len(names), int(every), int(capacity), self.TAPE_DTYPES[key][0]),
                   "spd_model_tape_configure")
@@ -426,6 +460,21 @@ class EnsembleModel:
               "spd_model_tape_info")
         name = [k for k, v in self.TAPE_DTYPES.items() if v[0] == dtype.value][0]
         return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, dtype=name)
+
+    # ---- shared by the recorders that take a member mask, and by those that remember their entries ----
+    def _member_mask(self, members):
+        mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
+        if mask.shape != (self.nmembers,):
+            raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
+        return mask
+
+    def _configure_refused(self, symbol, rc, gone, attr):
+        """a _configure call returned non-zero: the remembered entries go if the refusal came behind the point where the earlier
+        configuration went (`gone()`), and the library's text is raised"""
+        text = (self._lib.spd_last_error() or b"?").decode()
+        if gone():
+            setattr(self, attr, ())
+        raise _lib.SpeedyHipError("%s failed (%d): %s" % (symbol, rc, text))
 
     # ---- the rows a ring keeps beside its slots (csrc/ring.hpp): step and date of each held sample, window or event, oldest first ----
     def _ring_rows(self, symbol, held, width):
@@ -460,8 +509,7 @@ class EnsembleModel:
         [count][nt][levels][48][96] ([count][nt][48][96] for one-level names) on the model's device in the tape's dtype."""
         first, count = self._range(first, count)
         info = self.tape_info
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         dtype = self.TAPE_DTYPES[info["dtype"]][1]
         out = torch.empty((count, max(nt, 0)) + self._stats_shape(name), dtype=dtype, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
@@ -477,7 +525,7 @@ class EnsembleModel:
         float64 -- two planes per sample and member group, whatever the number of members.  Empties the ring; an empty list
         switches it off and frees it.  Synchronises the device."""
         names = [str(v) for v in variables]
-        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        arr = _c_names(names)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_enstape_configure(self._m, arr, len(names), int(every), int(capacity)),
                   "spd_model_enstape_configure")
@@ -507,8 +555,7 @@ class EnsembleModel:
         return self._row_times(self._enstape_rows())
 
     def _enstape_read(self, name, kind, t0, nt):
-        t0 = int(t0)
-        nt = self.enstape_info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(self.enstape_info, t0, nt)
         out = torch.empty((max(nt, 0),) + self._stats_shape(name), dtype=torch.float64, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_enstape_read(self._m, name.encode(), kind, t0, nt, C.c_void_p(out.data_ptr()), out.numel() * 8,
@@ -548,8 +595,7 @@ class EnsembleModel:
         if key not in self.TAPE_DTYPES:
             raise ValueError("dtype must be 'float32' or 'float64', got %r" % (dtype,))
         pairs = [(str(n), self._acctape_op(op)) for n, op in entries]
-        names = (C.c_char_p * max(len(pairs), 1))(*[n.encode() for n, _ in pairs])
-        ops = (C.c_int * max(len(pairs), 1))(*[op for _, op in pairs])
+        names, ops = _c_names(n for n, _ in pairs), _c_array(C.c_int, (op for _, op in pairs))
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_acctape_configure(self._m, names, ops, len(pairs), int(every), int(capacity),
                                                         self.TAPE_DTYPES[key][0]), "spd_model_acctape_configure")
@@ -589,8 +635,7 @@ class EnsembleModel:
         dtype."""
         first, count = self._range(first, count)
         info = self.acctape_info
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         dtype = self.TAPE_DTYPES[info["dtype"]][1]
         inner = (3, 48, 96) if name in self.ACCTAPE_THREE_PLANES else (48, 96)
         out = torch.empty((count, max(nt, 0)) + inner, dtype=dtype, device=self.sp.device)
@@ -643,9 +688,8 @@ class EnsembleModel:
             if counts and len(entry) != 3:
                 raise ValueError("op %r needs a threshold: (name, op, threshold)" % (entry[1],))
             rows.append((str(entry[0]), op, float(entry[2]) if counts else 0.0))
-        names = (C.c_char_p * max(len(rows), 1))(*[n.encode() for n, _, _ in rows])
-        ops = (C.c_int * max(len(rows), 1))(*[op for _, op, _ in rows])
-        thresholds = (C.c_double * max(len(rows), 1))(*[t for _, _, t in rows])
+        names, ops = _c_names(r[0] for r in rows), _c_array(C.c_int, (r[1] for r in rows))
+        thresholds = _c_array(C.c_double, (r[2] for r in rows))
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_wintape_configure(self._m, names, ops, thresholds, len(rows), kind, every, int(sample_every),
                                                         int(capacity), self.TAPE_DTYPES[key][0]), "spd_model_wintape_configure")
@@ -688,8 +732,7 @@ class EnsembleModel:
         [count][nt][levels][48][96] ([count][nt][48][96] for one-level names) on the model's device in the ring's dtype."""
         first, count = self._range(first, count)
         info = self.wintape_info
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         dtype = self.TAPE_DTYPES[info["dtype"]][1]
         shape = self._stats_shape({"wspd_grid": "u_grid", "wspd_plev": "u_plev"}.get(name, name))
         out = torch.empty((count, max(nt, 0)) + shape, dtype=dtype, device=self.sp.device)
@@ -709,26 +752,16 @@ class EnsembleModel:
         entry's sum over the 4608 points of weight times the value a float64 tape holds is formed on the device in a fixed,
         documented order and kept for every member in a ring of the last `capacity` samples.  Empties the
         ring; an empty list switches the recorder off and frees it.  Synchronises the device."""
-        rows = []
-        for entry in entries:
-            if len(entry) != 3:
-                raise ValueError("an entry is (name, level, pattern), got %r" % (entry,))
-            rows.append((str(entry[0]), int(entry[1]), int(entry[2])))
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        if rows and (w.ndim != 3 or w.shape[1:] != (48, 96)):
-            raise ValueError("weights must be [P][48][96], got shape %r" % (w.shape,))
-        n = max(len(rows), 1)
-        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
-        levels = (C.c_int * n)(*[r[1] for r in rows])
-        patterns = (C.c_int * n)(*[r[2] for r in rows])
+        rows = _pattern_rows(entries)
+        w = _weight_maps(weights, checked=bool(rows))
+        names, levels = _c_names(r[0] for r in rows), _c_array(C.c_int, (r[1] for r in rows))
+        patterns = _c_array(C.c_int, (r[2] for r in rows))
         with torch.cuda.device(self.sp.device):
             rc = self._lib.spd_model_projtape_configure(self._m, w.ctypes.data_as(C.POINTER(C.c_double)), w.shape[0] if rows else 0, names,
                                                         levels, patterns, len(rows), int(every), int(capacity))
         if rc != 0:
-            text = (self._lib.spd_last_error() or b"?").decode()
-            if self._lib.spd_model_projtape_info(self._m, None, None, None, None, None, None) != 0:
-                self._projtape_entries = ()  # (refused behind the point where the earlier configuration went)
-            raise _lib.SpeedyHipError("spd_model_projtape_configure failed (%d): %s" % (rc, text))
+            off = lambda: self._lib.spd_model_projtape_info(self._m, None, None, None, None, None, None) != 0  # noqa: E731
+            self._configure_refused("spd_model_projtape_configure", rc, off, "_projtape_entries")
         self._projtape_entries = tuple(rows)
 
     def projtape_reset(self):
@@ -766,8 +799,7 @@ class EnsembleModel:
         tensor [count][nt][E] on the model's device, E in the order of projtape_entries."""
         first, count = self._range(first, count)
         info = self.projtape_info
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         out = torch.empty((count, max(nt, 0), info["entries"]), dtype=torch.float64, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_projtape_read(self._m, first, count, t0, nt, C.c_void_p(out.data_ptr()), out.numel() * 8,
@@ -795,12 +827,8 @@ class EnsembleModel:
             if n in self.NUDGE_NAMES and g.shape != (rows, 32):
                 raise ValueError("gains of %s must have the shape (%d, 32), got %s" % (n, rows, g.shape))
             table[k, :g.shape[0]] = g
-        mask = None
-        if members is not None:
-            mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
-            if mask.shape != (self.nmembers,):
-                raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
-        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        mask = None if members is None else self._member_mask(members)
+        arr = _c_names(names)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_nudge_configure(self._m, arr, len(names), table.ctypes.data_as(C.POINTER(C.c_double)),
                                                       None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -956,8 +984,7 @@ class EnsembleModel:
     def breed(self, t0=0, nt=None):
         """The events [t0, t0 + nt) of the held ones, oldest first: dict(amplitude, factor) of float64 tensors [nt][members] on
         the model's device -- the A before each rescale (0.0 for members that are not bred) and the s (1.0 for those)."""
-        t0 = int(t0)
-        nt = self.breed_info()["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(self.breed_info(), t0, nt)
         out = {}
         with torch.cuda.device(self.sp.device):
             for what, name in enumerate(("amplitude", "factor")):
@@ -1012,21 +1039,11 @@ class EnsembleModel:
         bools) per member with 2 ... 64 ones; a member with 0 -- a nature run -- is never touched.  `inflation` >= 1 multiplies
         the prior perturbations.  Every executed event writes the prior mean, prior variance, innovation and a used flag of each
         entry to a ring of `capacity` events (assim()).  Land and sea temperatures are not updated.  Synchronises the device."""
-        rows = []
-        for entry in entries:
-            if len(entry) != 3:
-                raise ValueError("an entry is (name, level, pattern), got %r" % (entry,))
-            rows.append((str(entry[0]), int(entry[1]), int(entry[2])))
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        if w.ndim != 3 or w.shape[1:] != (48, 96):
-            raise ValueError("weights must be [P][48][96], got shape %r" % (w.shape,))
-        mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
-        if mask.shape != (self.nmembers,):
-            raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
-        n = max(len(rows), 1)
-        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
-        levels = (C.c_int * n)(*[r[1] for r in rows])
-        patterns = (C.c_int * n)(*[r[2] for r in rows])
+        rows = _pattern_rows(entries)
+        w = _weight_maps(weights)
+        mask = self._member_mask(members)
+        names, levels = _c_names(r[0] for r in rows), _c_array(C.c_int, (r[1] for r in rows))
+        patterns = _c_array(C.c_int, (r[2] for r in rows))
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_assim_configure(self._m, w.ctypes.data_as(C.POINTER(C.c_double)), w.shape[0], names, levels, patterns,
                                                       len(rows), mask.ctypes.data_as(C.POINTER(C.c_int32)), int(every), int(capacity),
@@ -1100,8 +1117,7 @@ class EnsembleModel:
         [nt][E] on the model's device -- the prior ensemble mean and sample variance of each entry as the serial filter met it,
         the innovation yo - mean (0.0 for a missing observation) and 1.0 / 0.0 for an entry that was / was not used."""
         info = self.assim_info()
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         buf = torch.empty((max(nt, 0), info["entries"], 4), dtype=torch.float64, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_assim_read(self._m, t0, nt, C.c_void_p(buf.data_ptr()), buf.numel() * 8, self._stream()),
@@ -1140,30 +1156,17 @@ class EnsembleModel:
         the points whose weight is not zero, each in a fixed, documented order, go to a ring of `capacity`
         events -- before and, where an in-loop analysis was applied at the same step, after it.  Writes nothing into the model.
         Synchronises the device."""
-        rows = []
-        for entry in entries:
-            if len(entry) != 3:
-                raise ValueError("an entry is (name, level, pattern), got %r" % (entry,))
-            rows.append((str(entry[0]), int(entry[1]), int(entry[2])))
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        if w.ndim != 3 or w.shape[1:] != (48, 96):
-            raise ValueError("weights must be [P][48][96], got shape %r" % (w.shape,))
-        mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
-        if mask.shape != (self.nmembers,):
-            raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
-        n = max(len(rows), 1)
-        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
-        levels = (C.c_int * n)(*[r[1] for r in rows])
-        patterns = (C.c_int * n)(*[r[2] for r in rows])
+        rows = _pattern_rows(entries)
+        w = _weight_maps(weights)
+        mask = self._member_mask(members)
+        names, levels = _c_names(r[0] for r in rows), _c_array(C.c_int, (r[1] for r in rows))
+        patterns = _c_array(C.c_int, (r[2] for r in rows))
         with torch.cuda.device(self.sp.device):
             rc = self._lib.spd_model_verif_configure(self._m, w.ctypes.data_as(C.POINTER(C.c_double)), w.shape[0], names, levels, patterns,
                                                      len(rows), mask.ctypes.data_as(C.POINTER(C.c_int32)), int(truth), int(every),
                                                      int(capacity), int(bool(in_loop)))
         if rc != 0:
-            text = (self._lib.spd_last_error() or b"?").decode()
-            if self.verif_info()["members"] == 0:
-                self._verif_entries = ()  # (refused behind the point where the earlier configuration went)
-            raise _lib.SpeedyHipError("spd_model_verif_configure failed (%d): %s" % (rc, text))
+            self._configure_refused("spd_model_verif_configure", rc, lambda: self.verif_info()["members"] == 0, "_verif_entries")
         self._verif_entries = tuple(rows)
 
     def verif_off(self):
@@ -1226,8 +1229,7 @@ class EnsembleModel:
         state an in-loop analysis left at the same step (NaN where there was none) -- with rmse = sqrt(mse), spread =
         sqrt(variance), and analysis, an int32 tensor [nt]: 1 where phase 1 is filled."""
         info = self.verif_info()
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         buf = torch.empty((max(nt, 0), 2, info["entries"], 4), dtype=torch.float64, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_verif_read(self._m, t0, nt, C.c_void_p(buf.data_ptr()), buf.numel() * 8, self._stream()),
@@ -1242,8 +1244,7 @@ class EnsembleModel:
         of points with a non-zero weight whose truth lies above exactly k members, k = 0 ... r, without equalling any, then the
         number of points where it equals one (ties); -1 in a phase that was not filled."""
         info = self.verif_info()
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         buf = torch.empty((max(nt, 0), 2, info["entries"], 66), dtype=torch.int32, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_verif_hist(self._m, t0, nt, C.c_void_p(buf.data_ptr()), buf.numel() * 4, self._stream()),
@@ -1273,22 +1274,14 @@ class EnsembleModel:
             if entry[2] not in ("min", "max") and len(entry) != 4:
                 raise ValueError("op %r needs a parameter: (name, level, op, param)" % (entry[2],))
             rows.append((str(entry[0]), int(entry[1]), entry[2], float(entry[3]) if len(entry) == 4 else 0.0))
-        mask = np.ascontiguousarray(np.asarray(members).astype(np.int32))
-        if mask.shape != (self.nmembers,):
-            raise ValueError("members must have one entry per member (%d), got shape %s" % (self.nmembers, mask.shape))
-        n = max(len(rows), 1)
-        names = (C.c_char_p * n)(*[r[0].encode() for r in rows])
-        levels = (C.c_int * n)(*[r[1] for r in rows])
-        ops = (C.c_int * n)(*[self.QTAPE_OPS[r[2]] for r in rows])
-        params = (C.c_double * n)(*[r[3] for r in rows])
+        mask = self._member_mask(members)
+        names, levels = _c_names(r[0] for r in rows), _c_array(C.c_int, (r[1] for r in rows))
+        ops, params = _c_array(C.c_int, (self.QTAPE_OPS[r[2]] for r in rows)), _c_array(C.c_double, (r[3] for r in rows))
         with torch.cuda.device(self.sp.device):
             rc = self._lib.spd_model_qtape_configure(self._m, names, levels, ops, params, len(rows), mask.ctypes.data_as(C.POINTER(C.c_int32)),
                                                      int(every), int(capacity), int(bool(in_loop)))
         if rc != 0:
-            text = (self._lib.spd_last_error() or b"?").decode()
-            if self.qtape_info()["members"] == 0:
-                self._qtape_entries = ()  # (refused behind the point where the earlier configuration went)
-            raise _lib.SpeedyHipError("spd_model_qtape_configure failed (%d): %s" % (rc, text))
+            self._configure_refused("spd_model_qtape_configure", rc, lambda: self.qtape_info()["members"] == 0, "_qtape_entries")
         self._qtape_entries = tuple(rows)
 
     def qtape_off(self):
@@ -1346,8 +1339,7 @@ class EnsembleModel:
         """The events [t0, t0 + nt) of the held ones, oldest first, of the entry with index `entry` in qtape_entries: a float64
         tensor [nt][48][96] on the model's device."""
         info = self.qtape_info()
-        t0 = int(t0)
-        nt = info["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(info, t0, nt)
         out = torch.empty((max(nt, 0), 48, 96), dtype=torch.float64, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_qtape_read(self._m, int(entry), t0, nt, C.c_void_p(out.data_ptr()), out.numel() * 8, self._stream()),
@@ -1373,7 +1365,7 @@ class EnsembleModel:
             for n in self.SPECTRA_DERIVED.get(str(v), (str(v),)):
                 if n not in names:
                     names.append(n)
-        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        arr = _c_names(names)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_spectra_configure(self._m, arr, len(names), int(every), int(capacity)),
                   "spd_model_spectra_configure")
@@ -1422,8 +1414,7 @@ class EnsembleModel:
         if name in self.SPECTRA_DERIVED:
             return self._spectra_derive(name, *(self.spectra(n, first, count, t0, nt) for n in self.SPECTRA_DERIVED[name]))
         first, count = self._range(first, count)
-        t0 = int(t0)
-        nt = self.spectra_info()["held"] - t0 if nt is None else int(nt)
+        t0, nt = _held_span(self.spectra_info(), t0, nt)
         shape = self._SPECTRA_SHAPES.get(name, (1,))  # (an unknown name: the library says which ones it knows)
         out = torch.empty((count, max(nt, 0)) + shape, dtype=torch.float64, device=self.sp.device)
         with torch.cuda.device(self.sp.device):
@@ -1443,7 +1434,7 @@ class EnsembleModel:
         first, count = self._range(first, count)
         sizes = [count * int(np.prod(self._SPECTRA_SHAPES.get(n, (1,)))) for n in stored]
         buf = torch.empty(sum(sizes), dtype=torch.float64, device=self.sp.device)
-        arr = (C.c_char_p * max(len(stored), 1))(*[n.encode() for n in stored])
+        arr = _c_names(stored)
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_spectra_compute(self._m, arr, len(stored), first, count, C.c_void_p(buf.data_ptr()),
                                                       buf.numel() * 8, self._stream()), "spd_model_spectra_compute")
@@ -1462,7 +1453,7 @@ class EnsembleModel:
         decreasing; results keep this order.  An empty list clears them.  Refused while statistics of a pressure-level variable
         are configured."""
         pa = [float(p) * 100.0 for p in levels_hpa]
-        arr = (C.c_double * max(len(pa), 1))(*pa)
+        arr = _c_array(C.c_double, pa)
         check(self._lib.spd_model_plev_configure(self._m, arr, len(pa)), "spd_model_plev_configure")
 
     @property
@@ -1483,7 +1474,7 @@ class EnsembleModel:
         brought up to date (spectral2grid() of those members); without, they are used as they are."""
         names = list(self.PLEV_VARIABLES) if names is None else [str(v) for v in names]
         first, count = self._range(first, count)
-        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        arr = _c_names(names)
         out = {}
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_plev_compute(self._m, arr, len(names), first, count, int(bool(refresh)), self._stream()),
@@ -1512,7 +1503,7 @@ class EnsembleModel:
             names = [v for v in self.DERIVED_VARIABLES if not v.endswith("_plev") or self.plev_levels]
         names = [str(v) for v in names]
         first, count = self._range(first, count)
-        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        arr = _c_names(names)
         out = {}
         with torch.cuda.device(self.sp.device):
             check(self._lib.spd_model_derive_compute(self._m, arr, len(names), first, count, int(bool(refresh)), self._stream()),

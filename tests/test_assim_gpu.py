@@ -396,3 +396,32 @@ def test_nudging_in_the_loop_beside_assimilation_is_its_host_loop(spectral, bc, 
     assert got[0][2] == got[1][2] == STEPS
     assert differing(got[1][0], got[0][0]) == [] and same_ring(got[1][1], got[0][1])
     assert got[0][1]["steps"] == list(ROWS)
+
+
+# an interleaved list that comes back to planes it has left (t_grid 7 and z_plev 1, not adjacent) and mixes sigma-level,
+# pressure-level and mslp names (precnv is refused here)
+MIXED = (("t_grid", 7, 0), ("z_plev", 1, 1), ("t_grid", 7, 2), ("mslp", 0, 1), ("z_plev", 1, 3), ("u_grid", 0, 2), ("t_grid", 7, 3))
+
+
+def test_an_entry_is_a_function_of_its_own_plane_and_pattern(spectral, bc, maps):
+    """assim_compute() under MIXED and, on the same state, under the same entries with equal planes adjacent: entry for entry the
+    same bits.  Holds the table of distinct planes (csrc/entry_front.hpp) to the order of the caller's list; the mask has two runs."""
+    planes = [e[:2] for e in MIXED]
+    order = sorted(range(len(MIXED)), key=lambda k: planes.index(planes[k]))
+    assert order != list(range(len(MIXED)))
+    from pyspeedy_amd.model import EnsembleModel
+    model = EnsembleModel(spectral, 4)
+    try:
+        model.set_bc(bc)
+        perturb(model)
+        model.plev_configure([850.0, 500.0])
+        model.run(3)
+        got = []
+        for entries in (MIXED, [MIXED[k] for k in order]):
+            model.assim_configure(maps, entries, (1, 0, 1, 1), EVERY, capacity=2, in_loop=False)
+            got.append(model.assim_compute().cpu().numpy())  # [E][r]
+        assert got[0].shape == (len(MIXED), 3) and np.isfinite(got[0]).all()
+        assert np.array_equal(bits(got[0][order]), bits(got[1])), np.argwhere(got[0][order] != got[1]).tolist()
+        assert len(np.unique(got[0])) == got[0].size  # (no two entries or members agree)
+    finally:
+        model.close()

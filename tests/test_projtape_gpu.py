@@ -408,3 +408,36 @@ def test_shapes_dtype_device_and_levels(spectral, bc, weights):
     expected = np.stack([ref.project(many[p], t_low) for p in range(64)], axis=2)
     assert np.array_equal(got[:, :, :64].cpu().numpy(), expected)  # (sixteen batches of four entries on one plane)
     model.close()
+
+
+# an interleaved list that comes back to planes it has left (t_grid 7, z_plev 1 and precnv twice or three times, not adjacent) and
+# mixes sigma-level, pressure-level, mslp and precipitation names
+MIXED = (("t_grid", 7, 0), ("z_plev", 1, 1), ("precnv", 0, 0), ("t_grid", 7, RANDOM), ("mslp", 0, 1), ("z_plev", 1, 0), ("u_grid", 0, RANDOM),
+         ("precnv", 0, 1), ("t_grid", 7, 1))
+
+
+def by_plane(entries):
+    """the order that puts the entries of one plane next to each other: planes as they first appear, the list's order within one"""
+    planes = [e[:2] for e in entries]
+    return sorted(range(len(entries)), key=lambda k: planes.index(planes[k]))
+
+
+def test_an_entry_is_a_function_of_its_own_plane_and_pattern(spectral, bc, weights):
+    """The sample of step 4 under MIXED, and on a twin brought to the same step under the same entries with equal planes adjacent:
+    entry for entry the same bits, for every member.  Holds the table of distinct planes (csrc/entry_front.hpp) to the order of
+    the caller's list."""
+    order = by_plane(MIXED)
+    assert order != list(range(len(MIXED))) and sorted(order) == list(range(len(MIXED)))
+    got = []
+    for entries in (MIXED, [MIXED[k] for k in order]):
+        model, _ = perturbed(spectral, bc, 4, levels=[850.0, 500.0])
+        model.run(3)
+        model.projtape_configure(weights, entries, 4, 1)
+        model.run(1)  # (a one-step call that ends on a sample)
+        assert model.projtape_steps().tolist() == [4]
+        got.append(model.projtape().cpu().numpy()[:, 0])  # [members][E]
+        model.close()
+    mixed, sorted_ = got
+    assert mixed.shape == (4, len(MIXED)) and np.isfinite(mixed).all()
+    assert np.array_equal(mixed[:, order].view(np.uint64), sorted_.view(np.uint64)), np.argwhere(mixed[:, order] != sorted_).tolist()
+    assert len(np.unique(mixed[:, [0, 1, 3, 4, 5, 6, 8]])) == 4 * 7  # (the planes but precnv: no two entries or members agree)

@@ -436,3 +436,35 @@ def test_refusals_and_lifecycle(spectral, bc):
     finally:
         model.close()
         other.close()
+
+
+# an interleaved list that comes back to planes it has left (t_grid 7, z_plev 1 and precnv, not adjacent) and mixes sigma-level,
+# pressure-level, mslp and precipitation names
+MIXED = (("t_grid", 7, "min"), ("z_plev", 1, "quantile", 0.5), ("precnv", 0, "prob_above", 0.0), ("t_grid", 7, "max"),
+         ("mslp", 0, "quantile", 0.25), ("z_plev", 1, "min"), ("u_grid", 0, "quantile", 0.9), ("precnv", 0, "max"),
+         ("t_grid", 7, "quantile", 0.5))
+
+
+def test_an_entry_is_a_function_of_its_own_plane_and_parameters(spectral, bc):
+    """qtape_compute() under MIXED and, on the same state, under the same entries with equal planes adjacent: entry for entry the
+    same bits at every point.  Holds the table of distinct planes (csrc/entry_front.hpp) to the order of the caller's list; the
+    mask has two runs."""
+    planes = [e[:2] for e in MIXED]
+    order = sorted(range(len(MIXED)), key=lambda k: planes.index(planes[k]))
+    assert order != list(range(len(MIXED)))
+    from pyspeedy_amd.model import EnsembleModel
+    model = EnsembleModel(spectral, 4)
+    try:
+        model.set_bc(bc)
+        perturb(model)
+        model.plev_configure([850.0, 500.0])
+        model.run(3)
+        got = []
+        for entries in (MIXED, [MIXED[k] for k in order]):
+            model.qtape_configure(entries, (1, 0, 1, 1), EVERY, capacity=2, in_loop=False)
+            got.append(model.qtape_compute().cpu().numpy())  # [E][48][96]
+        assert got[0].shape == (len(MIXED), 48, 96) and np.isfinite(got[0]).all()
+        assert np.array_equal(bits(got[0][order]), bits(got[1])), [k for k in range(len(MIXED)) if (got[0][order[k]] != got[1][k]).any()]
+        assert (got[0][0] < got[0][8]).any() and (got[0][8] < got[0][3]).any() and (got[0][5] <= got[0][1]).all()  # (min, median, max)
+    finally:
+        model.close()

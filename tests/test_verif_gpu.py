@@ -387,3 +387,37 @@ def test_refusals_and_lifecycle(spectral, bc, maps):
         assert model.verif_info()["taken"] == 0 and model.verif_info()["members"] == 3
     finally:
         model.close()
+
+
+# an interleaved list that comes back to planes it has left (t_grid 7, z_plev 1 and precnv, not adjacent) and mixes sigma-level,
+# pressure-level, mslp and precipitation names
+MIXED = (("t_grid", 7, 0), ("z_plev", 1, 1), ("precnv", 0, 0), ("t_grid", 7, 2), ("mslp", 0, 1), ("z_plev", 1, 0), ("u_grid", 0, 2),
+         ("precnv", 0, 1), ("t_grid", 7, 1))
+
+
+def test_an_entry_is_a_function_of_its_own_plane_and_pattern(spectral, bc, maps):
+    """verif_compute() under MIXED and, on the same state, under the same entries with equal planes adjacent: entry for entry the
+    same bits in every score and the same histogram.  Holds the table of distinct planes (csrc/entry_front.hpp) to the order of the
+    caller's list; the truth, member 2, lies between the two runs of the mask."""
+    planes = [e[:2] for e in MIXED]
+    order = sorted(range(len(MIXED)), key=lambda k: planes.index(planes[k]))
+    assert order != list(range(len(MIXED)))
+    from pyspeedy_amd.model import EnsembleModel
+    model = EnsembleModel(spectral, 5)
+    try:
+        model.set_bc(bc)
+        perturb(model)
+        model.plev_configure([850.0, 500.0])
+        model.run(3)
+        got = []
+        for entries in (MIXED, [MIXED[k] for k in order]):
+            model.verif_configure(maps, entries, (1, 1, 0, 1, 1), 2, EVERY, capacity=2, in_loop=False)
+            got.append({k: v.cpu().numpy() for k, v in model.verif_compute().items()})
+        for name in ref.NAMES:
+            assert got[0][name].shape == (len(MIXED),)
+            assert np.array_equal(bits(got[0][name][order]), bits(got[1][name])), (name, got[0][name][order], got[1][name])
+        assert got[0]["hist"].shape == (len(MIXED), 6) and np.array_equal(got[0]["hist"][order], got[1]["hist"])
+        dry = [k for k, e in enumerate(MIXED) if e[0] != "precnv"]
+        assert len(np.unique(got[0]["mse"][dry])) == len(dry) and (got[0]["hist"].sum(axis=1) > 0).all()
+    finally:
+        model.close()

@@ -727,6 +727,71 @@ int spd_model_projtape_reset(spd_model_handle m);
 int spd_model_projtape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *n_patterns, int *n_entries);
 int spd_model_projtape_times(spd_model_handle m, int32_t *rows, int max_rows);
 int spd_model_projtape_read(spd_model_handle m, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
+/* The track tape: the minimum or maximum of a plane of the state's grid-space fields over a region, where it lies and two sub-grid
+ * offsets, per member, inside spd_model_step / spd_model_step_checked_begin calls of any length -- how deep the low is and where,
+ * the track of a storm, the jet or rain maximum -- as 32 bytes per entry, member and sample instead of a taped plane and an argmin
+ * on the host.  The operator is not linear: no weight map of the projection tape expresses it.  Off unless configured; a model
+ * without it issues exactly the launches it issued before.
+ * Configuration.  R regions, 1 <= R <= 64: the projection tape's weight maps (fp64 [48][96], finite, shared by all members); a point
+ * belongs to a region where its weight is not zero (the device keeps one byte per point), and a region without a point is refused.
+ * E entries (name, level, region, op, radius), 1 <= E <= 1024: name and level exactly as the projection tape takes them, region an
+ * index into the maps, op SPD_TRACK_MIN or SPD_TRACK_MAX, radius 0 ... 24 grid points (0: the entry never follows).
+ * Value.  x[p], p = 96 j + i, row 0 southernmost, is exactly what an fp64 tape of that name holds at that level after the sampled
+ * step, in export units (precnv / precls widened from float first under physics_storage32; a sampled step stores the
+ * diagnostics-only outputs when either is an entry).  For member m and entry e, with the follow-state last[m][e] = q:
+ *   1. candidates: the points of the region whose value is not NaN; if radius > 0 and q >= 0, only those with |j - j_q| <= radius
+ *      and a circular distance of i and i_q <= radius (rows end at 0 and 47, longitude wraps).  q lies in the region.
+ *   2. winner: the candidate with the smallest (MIN) or largest (MAX) value, infinities as numbers; among equal values the smallest
+ *      p.  Without a candidate (every region point NaN): value NaN, index -1, offsets 0.
+ *   3. offsets from the winner's four neighbours in the plane, candidates or not, every operation rounded on its own:
+ *      a = x[j][(i + 95) % 96], b = x[p], c = x[j][(i + 1) % 96];  den = (a - 2 b) + c;  num = 0.5 (a - c);  di = num / den where
+ *      den is finite and not zero and the quotient is finite, else 0; then clamped to [-0.5, 0.5].  dj likewise from rows j - 1 and
+ *      j + 1; dj = 0 on rows 0 and 47.
+ *   4. the ring slot gets four doubles (value, p, di, dj), and last[m][e] = p (-1 when nothing was found).
+ * The order (value, p) is total, so the result does not depend on the launch plan (member groups, rounds, checked or plain
+ * calls), and a numpy restatement reproduces it bit for bit.  Sampling is the tape's: after every step that leaves the absolute
+ * step counter at a multiple of `every`, with the recorder's own slab and tables, behind the projection tape's launch of that step on
+ * each member group's stream.  Sample n (from 1 since the last reset) lies in slot (n - 1) % capacity of the ring [slot][M][E][4].
+ * The follow-state is int32 [M][E] in device memory, -1 (follows nothing: the next sample looks at the whole region) after
+ * _configure, _reset and spd_model_init.
+ *   _configure  regions[n_regions][48][96] (host memory), names / levels / region_of / ops / radii[n_entries]; allocates (one hipMalloc
+ *               of the recorder's own, synchronises the device) and empties the ring; n_entries = 0 switches the recorder off and
+ *               frees it (the other arguments are then not looked at).  SPD_E_ARG, checked in this order before a model or a device
+ *               is needed: every < 1; capacity < 1; n_regions outside 1 ... 64; n_entries outside 0 ... 1024; null regions; a null
+ *               list; a weight that is not finite (the message names pattern and point); a region without a point; an unknown name
+ *               (with the catalogue's list); per entry a level below 0 or, for a name of fixed level count, beyond it, then a region
+ *               index outside the maps ("pattern ..."), then an op that is neither constant, then a radius outside 0 ... 24; then a null
+ *               model or a checked call in flight; then a pressure-level name (mslp included) before spd_model_plev_configure or with
+ *               a level beyond the configured count.  SPD_E_DEVICE with the number of bytes asked for when the allocation fails: the
+ *               recorder is then off and the model as usable as before.  spd_model_plev_configure is refused while the recorder
+ *               holds a pressure-level name.
+ *   _reset      empties the ring and sets the follow-state to -1 (synchronises the device).  spd_model_init does the same.
+ *   _info       taken: samples since the last reset; held = min(taken, capacity); any pointer may be NULL.
+ *   _times      rows[held][6] for the held samples, oldest first, as the projection tape's.  Returns the number of rows written.
+ *   _read       members [first, first + count) and samples [t0, t0 + nt) of the held ones, oldest first, of every entry in the
+ *               configured order into dst_device[count][nt][n_entries][4] doubles, stream-ordered; dst_device must be 8-byte
+ *               aligned.  SPD_E_SIZE when dst_bytes is too small.  Fails like the projection tape's while a checked call is in
+ *               flight and after one that reported a failed range check, until _reset or spd_model_init.
+ *   _positions  the follow-state of members [first, first + count) into dst[count][n_entries] (host memory, room for `max` values;
+ *               SPD_E_SIZE when that is too few); synchronises the device; returns the number of values written.
+ *   _seed       src[count][n_entries] (host memory) becomes the follow-state of those members: -1 or 0 ... 4607, a point of the
+ *               entry's region (SPD_E_ARG otherwise, nothing is written); synchronises the device.  Seeding is how a caller picks
+ *               WHICH low an entry with radius > 0 follows.
+ *   spd_track_point_host  steps 1 ... 3 for one plane as the device runs them, compiled for the host: plane[4608], mask[4608] bytes
+ *               (non-zero: in the region), prev -1 or 0 ... 4607, radius 0 ... 24 -> out4 = value, p, di, dj.
+ * spd_model_copy_member does not carry the recorder, and the outer boundary (spd_parallel_step*) does not keep it across the
+ * models it merges and splits. */
+#define SPD_TRACK_MIN 0
+#define SPD_TRACK_MAX 1
+int spd_model_tracktape_configure(spd_model_handle m, const double *regions, int n_regions, const char *const *names, const int *levels,
+                                  const int *region_of, const int *ops, const int *radii, int n_entries, int every, int capacity);
+int spd_model_tracktape_reset(spd_model_handle m);
+int spd_model_tracktape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *every, int *n_regions, int *n_entries);
+int spd_model_tracktape_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_tracktape_read(spd_model_handle m, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes, void *stream);
+int spd_model_tracktape_positions(spd_model_handle m, int first, int count, int32_t *dst, int max);
+int spd_model_tracktape_seed(spd_model_handle m, int first, int count, const int32_t *src);
+int spd_track_point_host(const double *plane, const unsigned char *mask, int prev, int radius, int op, double *out4);
 /* Nudging: operator-split Newtonian relaxation of the spectral state toward target fields, on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length (in-loop mode) or once on the state as it stands (_apply): replay experiments,
  * spectral nudging of the large scales, the cheapest form of data assimilation.  The only thing in the device loop that WRITES the

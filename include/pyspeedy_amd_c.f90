@@ -30,6 +30,7 @@ module pyspeedy_amd_c
     integer(c_int), parameter :: SPD_WIN_COUNT_ABOVE = 4, SPD_WIN_COUNT_BELOW = 5
     integer(c_int), parameter :: SPD_WINDOW_STEPS = 0, SPD_WINDOW_DAY = 1, SPD_WINDOW_MONTH = 2
     integer(c_int), parameter :: SPD_Q_MIN = 0, SPD_Q_MAX = 1, SPD_Q_QUANTILE = 2, SPD_Q_PROB_ABOVE = 3, SPD_Q_PROB_BELOW = 4
+    integer(c_int), parameter :: SPD_TRACK_MIN = 0, SPD_TRACK_MAX = 1
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -421,6 +422,64 @@ module pyspeedy_amd_c
             type(c_ptr), value :: model, dst_device, stream
             integer(c_int), value :: first, count, t0, nt
             integer(c_size_t), value :: dst_bytes
+        end function
+        ! the track tape: the minimum or maximum of single planes of the state's grid-space fields over regions and where it lies,
+        ! followed from sample to sample (pyspeedy_amd.h: spd_model_tracktape_*).  regions(96, 48, n_regions); an entry is names(k)
+        ! at the 0-based level levels(k) over the 0-based region region_of(k), ops(k) SPD_TRACK_MIN / SPD_TRACK_MAX, radii(k) 0 ... 24;
+        ! rows(6, *): as the tape's; _read: real(c_double) (4, n_entries, nt, count); _positions / _seed: (n_entries, count), 0-based
+        ! points 96 j + i or -1; spd_track_point_host: plane(96, 48), mask(96, 48) of bytes, out4(4)
+        integer(c_int) function spd_model_tracktape_configure(model, regions, n_regions, names, levels, region_of, ops, radii, &
+                n_entries, every, capacity) bind(C, name="spd_model_tracktape_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model
+            real(c_double), intent(in) :: regions(*)
+            type(c_ptr), intent(in) :: names(*)
+            integer(c_int), intent(in) :: levels(*), region_of(*), ops(*), radii(*)
+            integer(c_int), value :: n_regions, n_entries, every, capacity
+        end function
+        integer(c_int) function spd_model_tracktape_reset(model) bind(C, name="spd_model_tracktape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_tracktape_info(model, taken, held, capacity, every, n_regions, n_entries) &
+                bind(C, name="spd_model_tracktape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken
+            integer(c_int), intent(out) :: held, capacity, every, n_regions, n_entries
+        end function
+        integer(c_int) function spd_model_tracktape_times(model, rows, max_rows) bind(C, name="spd_model_tracktape_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(6, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_tracktape_read(model, first, count, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_tracktape_read")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: first, count, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_model_tracktape_positions(model, first, count, dst, max) &
+                bind(C, name="spd_model_tracktape_positions")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int), value :: first, count, max
+            integer(c_int32_t), intent(out) :: dst(*)
+        end function
+        integer(c_int) function spd_model_tracktape_seed(model, first, count, src) bind(C, name="spd_model_tracktape_seed")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int), value :: first, count
+            integer(c_int32_t), intent(in) :: src(*)
+        end function
+        integer(c_int) function spd_track_point_host(plane, mask, prev, radius, op, out4) bind(C, name="spd_track_point_host")
+            import :: c_int, c_double, c_signed_char
+            real(c_double), intent(in) :: plane(*)
+            integer(c_signed_char), intent(in) :: mask(*)
+            integer(c_int), value :: prev, radius, op
+            real(c_double), intent(out) :: out4(4)
         end function
         ! nudging: relaxation of the spectral state toward target fields behind every step of spd_model_step (in_loop = 1) or once on
         ! the state as it stands (_apply) (pyspeedy_amd.h: spd_model_nudge_*).  names: any of vor, div, t, tr, ps; gains(32, 8,

@@ -23,6 +23,7 @@ SPD_ACC_SUM, SPD_ACC_MEAN, SPD_ACC_MIN, SPD_ACC_MAX = 0, 1, 2, 3  # ops of spd_m
 SPD_WIN_SUM, SPD_WIN_MEAN, SPD_WIN_MIN, SPD_WIN_MAX, SPD_WIN_COUNT_ABOVE, SPD_WIN_COUNT_BELOW = 0, 1, 2, 3, 4, 5  # ops of spd_model_wintape_*
 SPD_WINDOW_STEPS, SPD_WINDOW_DAY, SPD_WINDOW_MONTH = 0, 1, 2  # window kinds of spd_model_wintape_configure / spd_wintape_plan
 SPD_Q_MIN, SPD_Q_MAX, SPD_Q_QUANTILE, SPD_Q_PROB_ABOVE, SPD_Q_PROB_BELOW = 0, 1, 2, 3, 4  # ops of spd_model_qtape_configure
+SPD_TRACK_MIN, SPD_TRACK_MAX = 0, 1  # ops of spd_model_tracktape_configure
 
 
 class SpeedyHipError(RuntimeError):
@@ -171,6 +172,15 @@ _SIGNATURES = {
     "spd_model_projtape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 5),
     "spd_model_projtape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
     "spd_model_projtape_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_tracktape_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_char_p)] + [C.POINTER(C.c_int)] * 4 +
+                                      [C.c_int, C.c_int, C.c_int]),
+    "spd_model_tracktape_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_tracktape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 5),
+    "spd_model_tracktape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_tracktape_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_model_tracktape_positions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_tracktape_seed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "spd_track_point_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "spd_model_nudge_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int,
                                             C.c_int]),
     "spd_model_nudge_set_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),

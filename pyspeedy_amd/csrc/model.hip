@@ -739,6 +739,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->acctape.alloc) (void)hipFree(m->acctape.alloc);
     if (m->wintape.alloc) (void)hipFree(m->wintape.alloc);
     if (m->projtape.alloc) (void)hipFree(m->projtape.alloc);
+    if (m->tracktape.alloc) (void)hipFree(m->tracktape.alloc);
     if (m->nudge.alloc) (void)hipFree(m->nudge.alloc);
     if (m->breed.alloc) (void)hipFree(m->breed.alloc);
     if (m->breed.ortho.alloc) (void)hipFree(m->breed.ortho.alloc);
@@ -1319,6 +1320,9 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->wintape.validity.clear();
     m->projtape.ring.clear();  // (... and an empty projection tape)
     m->projtape.validity.clear();
+    m->tracktape.ring.clear();  // (... and an empty track tape that follows nothing)
+    m->tracktape.validity.clear();
+    M_HIP(tracktape_unseed(m));
     m->assim.ring.clear();  // (... and no assimilation event)
     m->assim.validity.clear();
     m->assim.skipped = 0;
@@ -1454,7 +1458,7 @@ struct Segment {
     double tau_co2;  // the CO2 absorptivity the record was made with
     HostState start;
     long long nudged0;
-    SampleCursor stats, tape, spectra, enstape, acctape, wintape, projtape;
+    SampleCursor stats, tape, spectra, enstape, acctape, wintape, projtape, tracktape;
     OpenWindows open0, open;
     int rc = SPD_OK;
     bool launched, device_failed;  // a launch of this segment went out / a device call of it failed
@@ -1471,7 +1475,7 @@ struct Segment {
         a[6] = m->cal.month_idx;
     }
     void rewind() {  // a round begins
-        for (SampleCursor *c : {&stats, &tape, &spectra, &enstape, &acctape, &wintape, &projtape}) c->rewind();
+        for (SampleCursor *c : {&stats, &tape, &spectra, &enstape, &acctape, &wintape, &projtape, &tracktape}) c->rewind();
         open = open0;
     }
 };
@@ -1522,6 +1526,7 @@ static int plan_segment(Segment &sg) {
     sg.spectra = SampleCursor(m->spectra.ring.taken);
     sg.enstape = SampleCursor(m->enstape.ring.taken);
     sg.projtape = SampleCursor(m->projtape.ring.taken);
+    sg.tracktape = SampleCursor(m->tracktape.ring.taken);
     spd_model::AccTape &ac = m->acctape;
     if (ac.on && (ac.window_start < 0 || ac.window_start > m->current_step)) ac.window_start = m->current_step;
     sg.acctape = SampleCursor(ac.ring.taken);
@@ -1540,7 +1545,7 @@ struct StepPlan {
     bool new_day;
     ZonalDevice zd;  // (new_day) the day's zonal forcing
     int sw, diag, fresh;
-    long long stats_n, tape_n, spectra_n, enstape_n, projtape_n;  // the sample a recorder takes behind this step; 0: it is not due
+    long long stats_n, tape_n, spectra_n, enstape_n, projtape_n, tracktape_n;  // the sample a recorder takes behind this step; 0: it is not due
     bool fold_enstape, acc_close, run_geo;
     int acc_step, acc_slot;  // the accumulation tape reads the diagnostics-only outputs of EVERY step: number acc_step of its window
     // the window tape: what this step does to the open window (sample number win_k of it, 0: none; win_n samples at a close)
@@ -1588,8 +1593,10 @@ static StepPlan decide_step(Segment &sg, int round, int it) {
     p.win_n = sg.open.win.samples + (p.win.sample ? 1 : 0);
     if (p.win.sample || p.win.close) p.win_slot = wt.ring.slot(sg.wintape.open());
     if (m->projtape.on && due_after(c, m->projtape.every)) p.projtape_n = sg.projtape.next();
+    if (m->tracktape.on && due_after(c, m->tracktape.every)) p.tracktape_n = sg.tracktape.next();
     p.diag = (m->diag_every_step || it == sg.nsteps - 1 || (p.stats_n && m->stats.precip) || (p.tape_n && m->tape.precip) ||
-              (p.fold_enstape && m->enstape.precip) || ac.on || (p.win.sample && wt.precip) || (p.projtape_n && m->projtape.precip)) ? 1 : 0;
+              (p.fold_enstape && m->enstape.precip) || ac.on || (p.win.sample && wt.precip) || (p.projtape_n && m->projtape.precip) ||
+              (p.tracktape_n && m->tracktape.precip)) ? 1 : 0;
     // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
     // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
     // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
@@ -1663,6 +1670,8 @@ static void issue_group(Segment &sg, const StepPlan &p, int round, int it, int g
         sg.check_launch(wintape_step(m, first, count, p.win_k, p.win.close ? 1 : 0, p.win_n, p.win_slot, s), "window tape: ");
     if (sg.rc == SPD_OK && p.projtape_n)  // behind the window tape's launch, on the same stream
         sg.check_launch(projtape_sample(m, first, count, p.projtape_n, s), "projection tape: ");
+    if (sg.rc == SPD_OK && p.tracktape_n)  // behind the projection tape's launch, on the same stream
+        sg.check_launch(tracktape_sample(m, first, count, p.tracktape_n, s), "track tape: ");
 }
 
 // The host side after a step that went out for every group of the round: every round moves the model's counter and date and its own
@@ -1681,6 +1690,7 @@ static void commit_step(Segment &sg, const StepPlan &p, bool first_round, int it
     if (p.spectra_n) sg.spectra.commit(m->spectra.ring, first_round, m->current_step, p.next);
     if (p.enstape_n) sg.enstape.commit(m->enstape.ring, first_round, m->current_step, p.next);
     if (p.projtape_n) sg.projtape.commit(m->projtape.ring, first_round, m->current_step, p.next);
+    if (p.tracktape_n) sg.tracktape.commit(m->tracktape.ring, first_round, m->current_step, p.next);
     if (p.acc_close) {  // the window is closed and the next one starts at the step counter as it stands now
         spd_model::AccTape &ac = m->acctape;
         sg.acctape.next();
@@ -1891,6 +1901,7 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
         if (m->acctape.on && m->acctape.validity.valid) m->acctape.validity.fail(i, *failed);
         if (m->wintape.on && m->wintape.validity.valid) m->wintape.validity.fail(i, *failed);
         if (m->projtape.on && m->projtape.validity.valid) m->projtape.validity.fail(i, *failed);
+        if (m->tracktape.on && m->tracktape.validity.valid) m->tracktape.validity.fail(i, *failed);
         if (m->assim.on && m->assim.validity.valid) m->assim.validity.fail(i, *failed);
         if (m->verif.on && m->verif.validity.valid) m->verif.validity.fail(i, *failed);
         if (m->qtape.on && m->qtape.validity.valid) m->qtape.validity.fail(i, *failed);

@@ -2,7 +2,7 @@
 // the carving of an allocation that every in-loop feature's _configure and _read run around their own work; the front end of a
 // sample that the statistics and four of the tapes share (defined in model.hip).  model.hip holds the model's life, its registry,
 // the step loop and the rest of the C ABI; the host code of each in-loop feature lies behind its kernels in the feature's own file
-// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, nudge.hip, breed.hip, assim.hip, verif.hip, qtape.hip, plev.hip,
+// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, tracktape.hip, nudge.hip, breed.hip, assim.hip, verif.hip, qtape.hip, plev.hip,
 // derive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +31,7 @@
 #include "assim.hpp"
 #include "wintape.hpp"
 #include "projtape.hpp"
+#include "tracktape.hpp"
 #include "verif.hpp"
 #include "qtape.hpp"
 #include "ring.hpp"
@@ -336,6 +337,29 @@ struct spd_model {
         ProjTapePlane *planes = nullptr;
         ProjTapeItem *items = nullptr;
     } projtape;
+    // The track tape (spd_model_tracktape_*): the minimum or maximum of single planes of the state's grid-space fields over regions,
+    // where it lies and two sub-grid offsets -- four doubles per entry, member and sample --, optionally followed from sample to
+    // sample inside a window round the last position.  Sampled by the tape's rule (its own `every`, slab and tables) behind the
+    // projection tape's launch.  One allocation of its own (hipMalloc): the ring [slot][M][E][4] doubles, the regions [R][4608]
+    // bytes, the follow-state `last` [M][E] int32 (-1: follows nothing), slab, tables, the descriptors of the distinct planes and
+    // the entry list sorted by plane (tracktape.hpp).  Slots, and the step and date of each sample: `ring`.
+    struct TrackTape : SampleFront {
+        struct Entry {
+            int name, level, region, op, radius;  // name: catalogue id; op: SPD_TRACK_*
+        };
+        bool on = false;
+        int every = 1, nregions = 0, nplanes = 0;
+        SampleRing ring;  // rows [6]: absolute step after the sampled step, year, month, day, hour, minute
+        Validity validity;
+        std::vector<Entry> entries;
+        std::vector<unsigned char> host_masks;  // [R][4608]: the regions as the device holds them (a seed is checked against them)
+        void *alloc = nullptr;
+        double *data = nullptr;
+        unsigned char *masks = nullptr;
+        int *last = nullptr;
+        TrackTapePlane *planes = nullptr;
+        TrackTapeItem *items = nullptr;
+    } tracktape;
     // Nudging (spd_model_nudge_*): relaxation of the spectral state toward target fields, the one thing in the device loop that
     // WRITES the state.  In the in-loop mode a launch follows the step_range of every member group on the group's stream, in front
     // of the last step's range check and of every recorder (nudge.hip); spd_model_nudge_apply is the same launch once, on the state

@@ -132,6 +132,9 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
     if (m->projtape.on && m->projtape.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the projection tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_projtape_configure)");
+    if (m->tracktape.on && m->tracktape.holds_plev())
+        return m_fail(SPD_E_ARG, std::string(who) + ": the track tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_tracktape_configure)");
     if (m->verif.on && m->verif.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the verification tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_verif_off)");

@@ -806,6 +806,129 @@ class EnsembleModel:
                                                     self._stream()), "spd_model_projtape_read")
         return out
 
+    # ---- the track tape: extremes of fields over regions and their positions (spd_model_tracktape_*, include/pyspeedy_amd.h) --
+    TRACK_OPS = {"min": _lib.SPD_TRACK_MIN, "max": _lib.SPD_TRACK_MAX}
+
+    def tracktape_configure(self, regions, entries, every, capacity):
+        """Record the minimum or maximum of grid-space fields over regions, and where it lies, inside run() / run_checked() calls
+        of any length.  `regions` is array-like [R][48][96] (1 <= R <= 64, finite): the projection tape's weight maps
+        (pyspeedy_amd.projection_weights), a point belongs to a region where its weight is not zero; `entries` is a list of
+        (name, level, region, op, radius): name and level as projtape_configure takes them, region an index into `regions`, op
+        "min" or "max" (or SPD_TRACK_MIN / SPD_TRACK_MAX), radius 0 ... 24 grid points.  After every step that leaves
+        current_step at a multiple of `every`, each entry's extreme over its region of the plane a float64 tape holds is found on
+        the device for every member and kept as (value, p, di, dj) in a ring of the last `capacity` samples: p = 96 j + i the
+        winner's point (the lowest among equal values; -1 and NaN where every value of the region is NaN), di and dj sub-grid
+        offsets in [-0.5, 0.5] from the parabola through its neighbours.  An entry with radius > 0 follows its
+        feature: once it holds a position (its last winner, or a seed: tracktape_seed), it looks only at the points of the region
+        within `radius` rows and columns of it.  Empties the ring and un-seeds; an empty list switches the recorder off and frees
+        it.  Synchronises the device."""
+        rows = []
+        for entry in entries:
+            if len(entry) != 5:
+                raise ValueError("an entry is (name, level, region, op, radius), got %r" % (entry,))
+            op = entry[3]
+            if isinstance(op, str):
+                if op not in self.TRACK_OPS:
+                    raise ValueError("op must be one of %s, got %r" % (", ".join(self.TRACK_OPS), op))
+                op = self.TRACK_OPS[op]
+            rows.append((str(entry[0]), int(entry[1]), int(entry[2]), int(op), int(entry[4])))
+        w = _weight_maps(regions, checked=bool(rows))
+        names = _c_names(r[0] for r in rows)
+        levels, region_of, ops, radii = (_c_array(C.c_int, (r[k] for r in rows)) for k in (1, 2, 3, 4))
+        with torch.cuda.device(self.sp.device):
+            rc = self._lib.spd_model_tracktape_configure(self._m, w.ctypes.data_as(C.POINTER(C.c_double)), w.shape[0] if rows else 0, names,
+                                                         levels, region_of, ops, radii, len(rows), int(every), int(capacity))
+        if rc != 0:
+            off = lambda: self._lib.spd_model_tracktape_info(self._m, None, None, None, None, None, None) != 0  # noqa: E731
+            self._configure_refused("spd_model_tracktape_configure", rc, off, "_tracktape_entries")
+        self._tracktape_entries = tuple(rows)
+
+    def tracktape_off(self):
+        """Switch the track tape off and free it (no-op when it is off)."""
+        self.tracktape_configure([], [], 0, 0)
+
+    def tracktape_reset(self):
+        """Empty the track tape and un-seed it: the next sample is the first, and every entry looks at its whole region."""
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_tracktape_reset(self._m), "spd_model_tracktape_reset")
+
+    @property
+    def tracktape_info(self):
+        """dict(taken, held, capacity, every, regions, entries): samples since the last reset, samples the ring holds (min(taken,
+        capacity)), and the configuration."""
+        taken, held, capacity, every, regions, entries = C.c_longlong(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._lib.spd_model_tracktape_info(self._m, C.byref(taken), C.byref(held), C.byref(capacity), C.byref(every),
+                                                 C.byref(regions), C.byref(entries)), "spd_model_tracktape_info")
+        return dict(taken=int(taken.value), held=held.value, capacity=capacity.value, every=every.value, regions=regions.value,
+                    entries=entries.value)
+
+    @property
+    def tracktape_entries(self):
+        """The configured entries, a tuple of (name, level, region, op, radius) with op as SPD_TRACK_MIN / SPD_TRACK_MAX, in the
+        order of tracktape()'s entry axis (empty: off)."""
+        return getattr(self, "_tracktape_entries", ())
+
+    def _tracktape_rows(self):
+        return self._ring_rows("spd_model_tracktape_times", self.tracktape_info["held"], 6)
+
+    def tracktape_steps(self):
+        """The model's step counter after each held sample's step, oldest first (numpy int array)."""
+        return self._row_steps(self._tracktape_rows())
+
+    def tracktape_times(self):
+        """The date of each held sample's state, oldest first (a list of datetime)."""
+        return self._row_times(self._tracktape_rows())
+
+    def tracktape(self, first=0, count=None, t0=0, nt=None):
+        """Members [first, first + count) and samples [t0, t0 + nt) of the held ones (oldest first) of every entry: a float64
+        tensor [count][nt][E][4] on the model's device, E in the order of tracktape_entries, the last axis (value, p, di, dj)."""
+        first, count = self._range(first, count)
+        info = self.tracktape_info
+        t0, nt = _held_span(info, t0, nt)
+        out = torch.empty((count, max(nt, 0), info["entries"], 4), dtype=torch.float64, device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_tracktape_read(self._m, first, count, t0, nt, C.c_void_p(out.data_ptr()), out.numel() * 8,
+                                                     self._stream()), "spd_model_tracktape_read")
+        return out
+
+    def tracktape_positions(self, first=0, count=None):
+        """The follow-state of members [first, first + count): a numpy int32 array [count][E] of points p = 96 j + i, -1 where an
+        entry follows nothing.  Synchronises the device."""
+        first, count = self._range(first, count)
+        out = np.full((count, self.tracktape_info["entries"]), -1, dtype=np.int32)
+        with torch.cuda.device(self.sp.device):
+            n = self._lib.spd_model_tracktape_positions(self._m, first, count, out.ctypes.data_as(C.POINTER(C.c_int32)), out.size)
+        if n < 0:
+            check(n, "spd_model_tracktape_positions")
+        return out
+
+    def tracktape_seed(self, positions, first=0):
+        """Set the follow-state of the members from `first` on: `positions` is array-like [count][E] of points p = 96 j + i inside
+        each entry's region, or -1 (follow nothing until the next sample).  Seeding picks WHICH low an entry with radius > 0
+        follows.  Synchronises the device."""
+        src = np.ascontiguousarray(positions, dtype=np.int32)
+        if src.ndim != 2 or src.shape[1] != self.tracktape_info["entries"]:
+            raise ValueError("positions must be [count][%d], got shape %r" % (self.tracktape_info["entries"], src.shape))
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_tracktape_seed(self._m, int(first), src.shape[0], src.ctypes.data_as(C.POINTER(C.c_int32))),
+                  "spd_model_tracktape_seed")
+
+    @staticmethod
+    def tracktape_lonlat(track):
+        """(lon, lat) in degrees of tracktape()'s output (a tensor or array [..., 4]): lon = 3.75 (i + di) mod 360, lat linear
+        between the winner's row of ProjectionWeights.lat and the neighbouring row in the direction of dj, by |dj|.  NaN where
+        nothing was found (p = -1)."""
+        track = track.cpu().numpy() if torch.is_tensor(track) else np.asarray(track, dtype=np.float64)
+        lats = _lib.projection_weights().lat
+        p, di, dj = track[..., 1], track[..., 2], track[..., 3]
+        found = p >= 0
+        at = np.where(found, p, 0).astype(np.int64)
+        j, i = at // 96, at % 96
+        lon = np.mod(3.75 * (i + di), 360.0)
+        toward = np.clip(j + np.where(dj < 0, -1, 1), 0, 47)
+        lat = lats[j] + np.abs(dj) * (lats[toward] - lats[j])
+        return np.where(found, lon, np.nan), np.where(found, lat, np.nan)
+
     # ---- nudging: relaxation of the spectral state toward target fields (spd_model_nudge_*, include/pyspeedy_amd.h) ---------
     NUDGE_NAMES = ("vor", "div", "t", "tr", "ps")
 

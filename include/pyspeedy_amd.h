@@ -792,6 +792,90 @@ int spd_model_tracktape_read(spd_model_handle m, int first, int count, int t0, i
 int spd_model_tracktape_positions(spd_model_handle m, int first, int count, int32_t *dst, int max);
 int spd_model_tracktape_seed(spd_model_handle m, int first, int count, const int32_t *src);
 int spd_track_point_host(const double *plane, const unsigned char *mask, int prev, int radius, int op, double *out4);
+/* The filter tape: window means, covariances and last values of TIME-FILTERED grid-space fields, formed on the device inside
+ * spd_model_step / spd_model_step_checked_begin calls of any length: the variance of the 2-6-day band-passed z_plev at 500 hPa (the
+ * storm track), the transient eddy fluxes v'T' and u'v' of band-passed winds and temperature, the variance of a 10-day low-passed
+ * field.  A recursive filter keeps two planes of state per second-order section, not a window of samples.  An eighth sampled
+ * recorder, independent of the others (its own front end, slab, tables and allocation); it joins no member groups and writes nothing
+ * into the model; off unless configured, and with it off no launch of a step changes.
+ * Filters.  1 ... 8 filters, each a cascade of 1 ... 4 second-order sections.  A section is five fp64 numbers b0, b1, b2, a1, a2
+ * (a0 = 1): sections[sum of n_sections][5], filter after filter; n_sections[n_filters].  A section is refused unless all five are
+ * finite and it is stable: |a2| < 1 and |a1| < 1 + a2.  The library forms each section's zero-frequency gain once on the host,
+ * every operation rounded on its own: g = ((b0 + b1) + b2) / ((1 + a1) + a2).
+ * Filtered planes.  A filtered plane is one (name, level, filter) among the entries; each distinct combination is filtered once, at
+ * most 32 of them.  Names: the fourteen of the tape and the fourteen derived names (the pressure-level ones after
+ * spd_model_plev_configure); levels are 0-based levels of the name, by the projection tape's rules.  The value x fed in is exactly
+ * what an fp64 tape of that name holds (export units; precnv / precls widened from their stored precision).
+ * The filter step, per filtered plane and point, for filter sample k; k counts from 1 since _configure, _reset, spd_model_init or a
+ * step counter set by spd_model_mark_initialized / spd_model_set_control.  The sections run in order, each section's y the next
+ * section's x; every operation below is one correctly rounded IEEE operation, nothing is fused.
+ *   k = 1, the steady state of a constant input, so that a field with a large mean does not ring:
+ *       y = g x;  s1 = y - b0 x;  s2 = b2 x - a2 y
+ *   k > 1, transposed direct form II, both state updates from the state before this sample:
+ *       y = b0 x + s1;  s1 <- (b1 x - a1 y) + s2;  s2 <- b2 x - a2 y
+ * Spin-up.  Samples with k <= spinup update the filters and are counted in no window.
+ * Entries.  1 ... 64 entries (name_a, level_a, filter, op[, name_b, level_b]); names_b may be NULL, and names_b[k] NULL or "" means
+ * that entry k names no second field (levels_b[k] is then not read).
+ *   SPD_FIL_MEAN  value y_a; the window's result is the sum of the counted values in sample order, starting from the first counted
+ *                 value itself, divided once by their number n at the close
+ *   SPD_FIL_COV   value y_a * y_b (one multiplication), both through the entry's filter; without a second field b = a, a variance;
+ *                 summed and divided as SPD_FIL_MEAN.  It is a second moment about ZERO: for a filter that passes the mean (a
+ *                 low-pass) the caller subtracts the product of the two SPD_FIL_MEAN entries.
+ *   SPD_FIL_LAST  y_a of the window's last counted sample; with a window equal to the sampling interval the recorder is a tape of
+ *                 the filtered field
+ * A window without a counted sample closes as quiet NaN under all three ops.  Window number w (from 1 since the last reset) lies in
+ * ring slot (w - 1) % capacity; the ring holds, per entry, [slot][members][4608] elements, SPD_TAPE_F64 (the fp64 results) or
+ * SPD_TAPE_F32 (each rounded to the nearest float).
+ * Sampling and windows are the window tape's, from the same code: a sample after every step that leaves the absolute step counter at
+ * a multiple of sample_every; SPD_WINDOW_STEPS / _DAY / _MONTH with `every` as spd_model_wintape_configure takes it; the first window
+ * starts at the model's current step; spd_wintape_plan tells a host which windows a run closes (its column 6 counts all samples, the
+ * recorder's the counted ones).  On a sampled step the diagnostics-only outputs are stored when precnv or precls is a name.
+ *   _configure  allocates ring, filter state, accumulators, slab and tables in one hipMalloc of its own (synchronises the device) and
+ *               empties the ring.  SPD_E_ARG, checked in this order before a model or a device is needed (spd_filtape_check runs
+ *               exactly these checks and nothing else): n_filters outside 1 ... 8 or a null list of filters; a filter with fewer
+ *               than 1 or more than 4 sections; per section, in order, a coefficient that is not finite, then a section that is not
+ *               stable; n_entries outside 1 ... 64 or a null list of entries; an unknown name (a's, then b's); then per entry
+ *               level_a, level_b, the filter index, the op, a second field on SPD_FIL_MEAN / SPD_FIL_LAST; more than 32 distinct
+ *               filtered planes; spinup < 0; the window kind, `every` and sample_every as the window tape refuses them;
+ *               capacity < 1; an unknown dtype.  Then a null model; a checked call in flight; a pressure-level name before
+ *               spd_model_plev_configure or a level beyond the configured ones.  SPD_E_DEVICE with the number of bytes asked for
+ *               when the allocation fails: the recorder is then off and the model as usable as before.
+ *               spd_model_plev_configure is refused while an entry names a pressure-level plane.
+ *   _off        switches the recorder off and frees it (synchronises the device).
+ *   _reset      empties the ring, starts a new window at the model's current step and restarts the filters: the next sample is
+ *               filter sample 1 (host only, no device work).  spd_model_init does the same.
+ *   _info       taken: windows closed since the last reset; held = min(taken, capacity); n_planes: distinct filtered planes;
+ *               filter_samples: k of the last sample; any pointer may be NULL.
+ *   _times      rows[held][8] for the held windows, oldest first: the absolute step counter after the window's last step, then
+ *               year, month, day, hour, minute of that state, then the number of counted samples and the number of steps in the
+ *               window (host memory).  Returns the number of rows written (at most max_rows).
+ *   _read       members [first, first + count) and windows [t0, t0 + nt) of the held ones, oldest first, of entry `entry` (0-based,
+ *               the caller's order) into dst_device[count][nt][48][96] in the ring's dtype, stream-ordered; dst_device must be
+ *               16-byte aligned.  SPD_E_SIZE when dst_bytes is too small.
+ *   spd_filtape_filter_host  the filter step as the device runs it, compiled for the host, over a scalar series from filter sample 1
+ *               on: sections[n_sections][5], x[n] -> y[n].  SPD_E_ARG for n_sections outside 1 ... 4, a null argument, a
+ *               coefficient that is not finite, a section that is not stable, n < 0.
+ * Reads fail (SPD_E_ARG, with the reason) while a checked call is in flight and after a checked call that reported a failed range
+ * check (the message names the member and the step): the series stays invalid until _reset or spd_model_init.
+ * spd_model_copy_member does not carry the recorder, and the outer boundary (spd_parallel_step*) does not keep it across the
+ * models it merges and splits. */
+#define SPD_FIL_MEAN 0
+#define SPD_FIL_COV 1
+#define SPD_FIL_LAST 2
+int spd_model_filtape_configure(spd_model_handle m, const double *sections, const int *n_sections, int n_filters, const char *const *names_a,
+                                const int *levels_a, const int *filters, const int *ops, const char *const *names_b, const int *levels_b,
+                                int n_entries, int window, int every, int sample_every, int spinup, int capacity, int dtype);
+int spd_model_filtape_off(spd_model_handle m);
+int spd_model_filtape_reset(spd_model_handle m);
+int spd_model_filtape_info(spd_model_handle m, long long *taken, int *held, int *capacity, int *window, int *every, int *sample_every,
+                           int *spinup, int *dtype, int *n_filters, int *n_planes, int *n_entries, long long *filter_samples);
+int spd_model_filtape_times(spd_model_handle m, int32_t *rows, int max_rows);
+int spd_model_filtape_read(spd_model_handle m, int entry, int first, int count, int t0, int nt, void *dst_device, size_t dst_bytes,
+                           void *stream);
+int spd_filtape_check(const double *sections, const int *n_sections, int n_filters, const char *const *names_a, const int *levels_a,
+                      const int *filters, const int *ops, const char *const *names_b, const int *levels_b, int n_entries, int window,
+                      int every, int sample_every, int spinup, int capacity, int dtype);
+int spd_filtape_filter_host(const double *sections, int n_sections, const double *x, int n, double *y);
 /* Nudging: operator-split Newtonian relaxation of the spectral state toward target fields, on the device inside spd_model_step /
  * spd_model_step_checked_begin calls of any length (in-loop mode) or once on the state as it stands (_apply): replay experiments,
  * spectral nudging of the large scales, the cheapest form of data assimilation.  The only thing in the device loop that WRITES the

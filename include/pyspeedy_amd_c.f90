@@ -31,6 +31,7 @@ module pyspeedy_amd_c
     integer(c_int), parameter :: SPD_WINDOW_STEPS = 0, SPD_WINDOW_DAY = 1, SPD_WINDOW_MONTH = 2
     integer(c_int), parameter :: SPD_Q_MIN = 0, SPD_Q_MAX = 1, SPD_Q_QUANTILE = 2, SPD_Q_PROB_ABOVE = 3, SPD_Q_PROB_BELOW = 4
     integer(c_int), parameter :: SPD_TRACK_MIN = 0, SPD_TRACK_MAX = 1
+    integer(c_int), parameter :: SPD_FIL_MEAN = 0, SPD_FIL_COV = 1, SPD_FIL_LAST = 2
 
     interface
         ! ---- context ------------------------------------------------------------------------------------------
@@ -480,6 +481,63 @@ module pyspeedy_amd_c
             integer(c_signed_char), intent(in) :: mask(*)
             integer(c_int), value :: prev, radius, op
             real(c_double), intent(out) :: out4(4)
+        end function
+        ! the filter tape: window means, covariances and last values of time-filtered planes of the state's grid-space fields
+        ! (pyspeedy_amd.h: spd_model_filtape_*).  sections(5, sum of n_sections): b0, b1, b2, a1, a2 of each second-order section,
+        ! filter after filter; an entry is names_a(k) at the 0-based level levels_a(k) through the 0-based filter filters(k) under
+        ! ops(k) SPD_FIL_*, with names_b(k) (c_null_ptr: none) at levels_b(k) for a covariance of two fields; rows(8, *): as the
+        ! window tape's with the counted samples; _read: (96, 48, nt, count) of one 0-based entry in the ring's dtype
+        integer(c_int) function spd_model_filtape_configure(model, sections, n_sections, n_filters, names_a, levels_a, filters, ops, &
+                names_b, levels_b, n_entries, window, every, sample_every, spinup, capacity, dtype) &
+                bind(C, name="spd_model_filtape_configure")
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: model
+            real(c_double), intent(in) :: sections(*)
+            integer(c_int), intent(in) :: n_sections(*), levels_a(*), filters(*), ops(*), levels_b(*)
+            type(c_ptr), intent(in) :: names_a(*), names_b(*)
+            integer(c_int), value :: n_filters, n_entries, window, every, sample_every, spinup, capacity, dtype
+        end function
+        integer(c_int) function spd_model_filtape_off(model) bind(C, name="spd_model_filtape_off")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_filtape_reset(model) bind(C, name="spd_model_filtape_reset")
+            import :: c_ptr, c_int
+            type(c_ptr), value :: model
+        end function
+        integer(c_int) function spd_model_filtape_info(model, taken, held, capacity, window, every, sample_every, spinup, dtype, &
+                n_filters, n_planes, n_entries, filter_samples) bind(C, name="spd_model_filtape_info")
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: model
+            integer(c_long_long), intent(out) :: taken, filter_samples
+            integer(c_int), intent(out) :: held, capacity, window, every, sample_every, spinup, dtype, n_filters, n_planes, n_entries
+        end function
+        integer(c_int) function spd_model_filtape_times(model, rows, max_rows) bind(C, name="spd_model_filtape_times")
+            import :: c_ptr, c_int, c_int32_t
+            type(c_ptr), value :: model
+            integer(c_int32_t), intent(out) :: rows(8, *)
+            integer(c_int), value :: max_rows
+        end function
+        integer(c_int) function spd_model_filtape_read(model, entry, first, count, t0, nt, dst_device, dst_bytes, stream) &
+                bind(C, name="spd_model_filtape_read")
+            import :: c_ptr, c_int, c_size_t
+            type(c_ptr), value :: model, dst_device, stream
+            integer(c_int), value :: entry, first, count, t0, nt
+            integer(c_size_t), value :: dst_bytes
+        end function
+        integer(c_int) function spd_filtape_check(sections, n_sections, n_filters, names_a, levels_a, filters, ops, names_b, levels_b, &
+                n_entries, window, every, sample_every, spinup, capacity, dtype) bind(C, name="spd_filtape_check")
+            import :: c_ptr, c_int, c_double
+            real(c_double), intent(in) :: sections(*)
+            integer(c_int), intent(in) :: n_sections(*), levels_a(*), filters(*), ops(*), levels_b(*)
+            type(c_ptr), intent(in) :: names_a(*), names_b(*)
+            integer(c_int), value :: n_filters, n_entries, window, every, sample_every, spinup, capacity, dtype
+        end function
+        integer(c_int) function spd_filtape_filter_host(sections, n_sections, x, n, y) bind(C, name="spd_filtape_filter_host")
+            import :: c_int, c_double
+            real(c_double), intent(in) :: sections(*), x(*)
+            integer(c_int), value :: n_sections, n
+            real(c_double), intent(out) :: y(*)
         end function
         ! nudging: relaxation of the spectral state toward target fields behind every step of spd_model_step (in_loop = 1) or once on
         ! the state as it stands (_apply) (pyspeedy_amd.h: spd_model_nudge_*).  names: any of vor, div, t, tr, ps; gains(32, 8,

@@ -5,10 +5,11 @@ hand-written HIP kernels behind the C ABI in include/pyspeedy_amd.h; this packag
 mirrors the reference's interfaces: the operator level (ModSpectral_t procedures, get_physical_tendencies), the f2py
 driver function set (speedy_driver) and the user-facing Speedy / SpeedyEns classes with their callbacks.
 """
-from ._lib import (IL, IX, IY, KX, MX, NX, TRUNC, SpeedyHipError, breed_weights, build, lib, nudge_gains, projection_weights, wintape_plan)  # noqa: F401
+from ._lib import (IL, IX, IY, KX, MX, NX, TRUNC, SpeedyHipError, breed_weights, build, butterworth_sections, lib, nudge_gains, projection_weights,
+                   wintape_plan)  # noqa: F401
 
 __all__ = ["ModSpectral", "ColumnPhysics", "Speedy", "SpeedyEns", "example_bc_file", "example_sst_anomaly_file",
-           "MODEL_STATE_DEF", "DEFAULT_OUTPUT_VARS", "SpeedyHipError", "build", "lib", "wintape_plan", "nudge_gains",
+           "MODEL_STATE_DEF", "DEFAULT_OUTPUT_VARS", "SpeedyHipError", "build", "lib", "wintape_plan", "butterworth_sections", "nudge_gains",
            "breed_weights", "projection_weights"]
 
 

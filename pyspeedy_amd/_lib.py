@@ -24,6 +24,7 @@ SPD_WIN_SUM, SPD_WIN_MEAN, SPD_WIN_MIN, SPD_WIN_MAX, SPD_WIN_COUNT_ABOVE, SPD_WI
 SPD_WINDOW_STEPS, SPD_WINDOW_DAY, SPD_WINDOW_MONTH = 0, 1, 2  # window kinds of spd_model_wintape_configure / spd_wintape_plan
 SPD_Q_MIN, SPD_Q_MAX, SPD_Q_QUANTILE, SPD_Q_PROB_ABOVE, SPD_Q_PROB_BELOW = 0, 1, 2, 3, 4  # ops of spd_model_qtape_configure
 SPD_TRACK_MIN, SPD_TRACK_MAX = 0, 1  # ops of spd_model_tracktape_configure
+SPD_FIL_MEAN, SPD_FIL_COV, SPD_FIL_LAST = 0, 1, 2  # ops of spd_model_filtape_configure
 
 
 class SpeedyHipError(RuntimeError):
@@ -75,6 +76,11 @@ class StreamProbeArgs(C.Structure):
         "reserved")] + [
         ("total_bytes", C.c_uint64)]
 
+
+# sections, n_sections, n_filters, names_a, levels_a, filters, ops, names_b, levels_b, n_entries, window, every, sample_every, spinup,
+# capacity, dtype of spd_model_filtape_configure / spd_filtape_check
+_FILTAPE_ARGS = ([C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_char_p)] + [C.POINTER(C.c_int)] * 3 +
+                 [C.POINTER(C.c_char_p), C.POINTER(C.c_int)] + [C.c_int] * 7)
 
 _SIGNATURES = {
     "spd_stream_probe": (C.c_int, [C.c_void_p, C.POINTER(StreamProbeArgs), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -181,6 +187,14 @@ _SIGNATURES = {
     "spd_model_tracktape_positions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "spd_model_tracktape_seed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "spd_track_point_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "spd_model_filtape_configure": (C.c_int, [C.c_void_p] + _FILTAPE_ARGS),
+    "spd_model_filtape_off": (C.c_int, [C.c_void_p]),
+    "spd_model_filtape_reset": (C.c_int, [C.c_void_p]),
+    "spd_model_filtape_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)] + [C.POINTER(C.c_int)] * 10 + [C.POINTER(C.c_longlong)]),
+    "spd_model_filtape_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    "spd_model_filtape_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spd_filtape_check": (C.c_int, _FILTAPE_ARGS),
+    "spd_filtape_filter_host": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "spd_model_nudge_configure": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int,
                                             C.c_int]),
     "spd_model_nudge_set_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
@@ -376,6 +390,78 @@ def wintape_plan(start, step0, nsteps, window, sample_every=1):
     if n < 0:
         check(n, "spd_wintape_plan")
     return rows[:n]
+
+
+def butterworth_sections(kind, order, periods, sample_interval):
+    """Second-order sections of a digital Butterworth filter for EnsembleModel.filtape_configure: a float64 array [S][5] of
+    (b0, b1, b2, a1, a2) with a0 = 1.  `kind` is "lowpass" (passes periods longer than `periods`), "highpass" (shorter) or
+    "bandpass" (`periods` = the two edge periods, in either order); periods and `sample_interval` are in the same unit (hours,
+    days, or samples with sample_interval = 1) and every period must be longer than two sample intervals.  `order` is the order N
+    of the analog prototype, 1 ... 8 (1 ... 4 for a band-pass, which has 2 N poles): |H|^2 = 1 / (1 + W^(2 N)), one half at the
+    edges.  Low- and high-pass have ceil(N / 2) sections, the band-pass N.  Bilinear transform with pre-warped edges, w = tan(pi *
+    sample_interval / period); every section is scaled to gain 1 at zero frequency (low-pass), at the Nyquist frequency (high-pass)
+    or at the band centre sqrt(w1 w2) (band-pass).  numpy only."""
+    import numpy as np
+    if kind not in ("lowpass", "highpass", "bandpass"):
+        raise ValueError("kind must be 'lowpass', 'highpass' or 'bandpass', got %r" % (kind,))
+    n = int(order)
+    if n != order or n < 1 or n > (4 if kind == "bandpass" else 8):
+        raise ValueError("order must be 1 ... %d for a %s, got %r" % (4 if kind == "bandpass" else 8, kind, order))
+    edges = np.atleast_1d(np.asarray(periods, dtype=np.float64))
+    if edges.shape != ((2,) if kind == "bandpass" else (1,)):
+        raise ValueError("periods must be %s for a %s, got %r" % ("two periods" if kind == "bandpass" else "one period", kind, periods))
+    dt = float(sample_interval)
+    if not dt > 0.0 or not np.all(np.isfinite(edges)) or not np.all(edges > 2.0 * dt):
+        raise ValueError("every period must be finite and longer than two sample intervals (%r), got %r" % (sample_interval, periods))
+    if kind == "bandpass" and edges[0] == edges[1]:
+        raise ValueError("the two periods of a bandpass must differ, got %r" % (periods,))
+    warped = np.sort(np.tan(np.pi * dt / edges))  # analog edge frequencies under s = (z - 1) / (z + 1), ascending
+    # the prototype's poles in the upper half plane, and the real one of an odd order
+    proto = [np.exp(0.5j * np.pi * (2 * k + n + 1) / n) for k in range((n + 1) // 2)]
+    if n % 2:
+        proto[-1] = complex(-1.0, 0.0)  # (exactly, so that what follows from it is exactly real)
+
+    def z_of(s_pole):
+        return (1.0 + s_pole) / (1.0 - s_pole)
+
+    def section(zeros, poles, at):
+        """the section with these zeros and poles (a conjugate or real pair, or one real pole), of gain 1 at z = `at`"""
+        b = np.real(np.poly(zeros))
+        a = np.real(np.poly(poles))
+        b = np.concatenate([b, np.zeros(3 - b.size)])
+        a = np.concatenate([a, np.zeros(3 - a.size)])
+        powers = np.array([1.0, 1.0 / at, 1.0 / (at * at)])
+        b = b * (abs(np.dot(a, powers)) / abs(np.dot(b, powers)))
+        return [b[0], b[1], b[2], a[1], a[2]]
+
+    out = []
+    if kind in ("lowpass", "highpass"):
+        low = kind == "lowpass"
+        zero, at = (-1.0, 1.0) if low else (1.0, -1.0)
+        for q in proto:
+            s_pole = warped[0] * q if low else warped[0] / q
+            if abs(q.imag) < 1e-12:
+                out.append(section([zero], [z_of(s_pole.real)], at))
+            else:
+                zp = z_of(s_pole)
+                out.append(section([zero, zero], [zp, np.conj(zp)], at))
+    else:
+        band, centre2 = warped[1] - warped[0], warped[0] * warped[1]
+        at = z_of(1j * np.sqrt(centre2))
+        for q in proto:  # s^2 - q B s + w0^2 = 0: two poles per prototype pole
+            root = np.sqrt(complex((q * band) ** 2 - 4.0 * centre2))
+            s_plus, s_minus = 0.5 * (q * band + root), 0.5 * (q * band - root)
+            if abs(q.imag) < 1e-12:
+                if abs(s_plus.imag) > 0.0:  # a conjugate pair
+                    zp = z_of(s_plus)
+                    out.append(section([1.0, -1.0], [zp, np.conj(zp)], at))
+                else:
+                    out.append(section([1.0, -1.0], [z_of(s_plus.real), z_of(s_minus.real)], at))
+            else:
+                for s_pole in (s_plus, s_minus):
+                    zp = z_of(s_pole)
+                    out.append(section([1.0, -1.0], [zp, np.conj(zp)], at))
+    return np.ascontiguousarray(out, dtype=np.float64)
 
 
 def nudge_gains(tau_hours, levels=None, l_max=31, taper=0):

@@ -740,6 +740,7 @@ int spd_model_destroy(spd_model_handle m) {
     if (m->wintape.alloc) (void)hipFree(m->wintape.alloc);
     if (m->projtape.alloc) (void)hipFree(m->projtape.alloc);
     if (m->tracktape.alloc) (void)hipFree(m->tracktape.alloc);
+    if (m->filtape.alloc) (void)hipFree(m->filtape.alloc);
     if (m->nudge.alloc) (void)hipFree(m->nudge.alloc);
     if (m->breed.alloc) (void)hipFree(m->breed.alloc);
     if (m->breed.ortho.alloc) (void)hipFree(m->breed.ortho.alloc);
@@ -1323,6 +1324,11 @@ int spd_model_init(spd_model_handle m, int year, int month, int day, int hour, i
     m->tracktape.ring.clear();  // (... and an empty track tape that follows nothing)
     m->tracktape.validity.clear();
     M_HIP(tracktape_unseed(m));
+    m->filtape.ring.clear();  // (... and a filter tape whose filters start again and whose first window starts at the first step)
+    m->filtape.window_start = -1;
+    m->filtape.samples = 0;
+    m->filtape.filter_samples = 0;
+    m->filtape.validity.clear();
     m->assim.ring.clear();  // (... and no assimilation event)
     m->assim.validity.clear();
     m->assim.skipped = 0;
@@ -1439,9 +1445,10 @@ static auto host_state(spd_model *m) {
 }
 using HostState = std::tuple<Calendar, int, int, bool, bool, bool, long long, double>;
 
-// the open windows of the accumulation tape (its first step) and of the window tape (its first step, its samples so far): put back
-// for every round like the host state, and written to the recorders by the first round only
-struct OpenWindows { int acc_start; WinOpen win; };
+// the open windows of the accumulation tape (its first step), of the window tape (its first step, its samples so far) and of the
+// filter tape (likewise, counted samples, and its filter samples so far): put back for every round like the host state, and written
+// to the recorders by the first round only
+struct OpenWindows { int acc_start; WinOpen win; WinOpen fil; long long fil_k; };
 
 // One segment of a call: what is decided before its first step, every recorder's cursor (every round takes the same samples and
 // writes the same slots, for its own members; the two window recorders count closed windows), and what became of its launches.
@@ -1458,7 +1465,7 @@ struct Segment {
     double tau_co2;  // the CO2 absorptivity the record was made with
     HostState start;
     long long nudged0;
-    SampleCursor stats, tape, spectra, enstape, acctape, wintape, projtape, tracktape;
+    SampleCursor stats, tape, spectra, enstape, acctape, wintape, projtape, tracktape, filtape;
     OpenWindows open0, open;
     int rc = SPD_OK;
     bool launched, device_failed;  // a launch of this segment went out / a device call of it failed
@@ -1475,7 +1482,7 @@ struct Segment {
         a[6] = m->cal.month_idx;
     }
     void rewind() {  // a round begins
-        for (SampleCursor *c : {&stats, &tape, &spectra, &enstape, &acctape, &wintape, &projtape, &tracktape}) c->rewind();
+        for (SampleCursor *c : {&stats, &tape, &spectra, &enstape, &acctape, &wintape, &projtape, &tracktape, &filtape}) c->rewind();
         open = open0;
     }
 };
@@ -1536,7 +1543,14 @@ static int plan_segment(Segment &sg) {
         wt.samples = 0;
     }
     sg.wintape = SampleCursor(wt.ring.taken);
-    sg.open0 = OpenWindows{ac.window_start, WinOpen{wt.window_start, wt.samples}};
+    spd_model::FilTape &ft = m->filtape;
+    if (ft.on && (ft.window_start < 0 || ft.window_start > m->current_step)) {  // (... and the filters start with filter sample 1)
+        ft.window_start = m->current_step;
+        ft.samples = 0;
+        ft.filter_samples = 0;
+    }
+    sg.filtape = SampleCursor(ft.ring.taken);
+    sg.open0 = OpenWindows{ac.window_start, WinOpen{wt.window_start, wt.samples}, WinOpen{ft.window_start, ft.samples}, ft.filter_samples};
     return SPD_OK;
 }
 
@@ -1553,6 +1567,12 @@ struct StepPlan {
     WinOpen win_after;
     int32_t win_row[8];
     int win_k, win_n, win_slot;
+    // the filter tape: what this step does to the filters and to the open window
+    FilDecision fil;
+    WinOpen fil_after;
+    long long fil_k_after;
+    int32_t fil_row[8];
+    int fil_slot;
     TauPlan tau;
     Calendar next;  // the date after the step
     TimeInterp w;
@@ -1594,9 +1614,15 @@ static StepPlan decide_step(Segment &sg, int round, int it) {
     if (p.win.sample || p.win.close) p.win_slot = wt.ring.slot(sg.wintape.open());
     if (m->projtape.on && due_after(c, m->projtape.every)) p.projtape_n = sg.projtape.next();
     if (m->tracktape.on && due_after(c, m->tracktape.every)) p.tracktape_n = sg.tracktape.next();
+    const spd_model::FilTape &ft = m->filtape;
+    p.fil_after = sg.open.fil;
+    p.fil_k_after = sg.open.fil_k;
+    if (ft.on)
+        p.fil = filtape_advance(WinSchedule{ft.window, ft.every, ft.sample_every}, ft.spinup, p.fil_after, p.fil_k_after, c + 1, p.next, p.fil_row);
+    if (p.fil.close) p.fil_slot = ft.ring.slot(sg.filtape.open());
     p.diag = (m->diag_every_step || it == sg.nsteps - 1 || (p.stats_n && m->stats.precip) || (p.tape_n && m->tape.precip) ||
               (p.fold_enstape && m->enstape.precip) || ac.on || (p.win.sample && wt.precip) || (p.projtape_n && m->projtape.precip) ||
-              (p.tracktape_n && m->tracktape.precip)) ? 1 : 0;
+              (p.tracktape_n && m->tracktape.precip) || (p.fil.sample && ft.precip)) ? 1 : 0;
     // The land / sea-ice coupling that follows the step (speedy.f90:72) happens at the date AFTER the step and for the
     // incremented step counter.  The interpolation weights of the climatologies change at midnight only: the first
     // coupling of a day (or of a state the host touched) interpolates, the others re-use what it stored (surface.hip).
@@ -1672,6 +1698,8 @@ static void issue_group(Segment &sg, const StepPlan &p, int round, int it, int g
         sg.check_launch(projtape_sample(m, first, count, p.projtape_n, s), "projection tape: ");
     if (sg.rc == SPD_OK && p.tracktape_n)  // behind the projection tape's launch, on the same stream
         sg.check_launch(tracktape_sample(m, first, count, p.tracktape_n, s), "track tape: ");
+    if (sg.rc == SPD_OK && (p.fil.sample || p.fil.close))  // behind the track tape's launch, on the same stream
+        sg.check_launch(filtape_step(m, first, count, p.fil, p.fil_slot, s), "filter tape: ");
 }
 
 // The host side after a step that went out for every group of the round: every round moves the model's counter and date and its own
@@ -1708,6 +1736,19 @@ static void commit_step(Segment &sg, const StepPlan &p, bool first_round, int it
         if (p.win.close) {
             sg.wintape.commit(wt.ring, true, m->current_step, p.next);
             std::memcpy(wt.ring.row(wt.ring.taken), p.win_row, sizeof(p.win_row));
+        }
+    }
+    spd_model::FilTape &ft = m->filtape;
+    sg.open.fil = p.fil_after;  // (the filter tape's open window and its filter samples with this step's, for every round alike)
+    sg.open.fil_k = p.fil_k_after;
+    if (p.fil.close) sg.filtape.next();
+    if (ft.on && first_round) {
+        ft.window_start = sg.open.fil.start;
+        ft.samples = sg.open.fil.samples;
+        ft.filter_samples = sg.open.fil_k;
+        if (p.fil.close) {
+            sg.filtape.commit(ft.ring, true, m->current_step, p.next);
+            std::memcpy(ft.ring.row(ft.ring.taken), p.fil_row, sizeof(p.fil_row));
         }
     }
 }
@@ -1902,6 +1943,7 @@ int spd_model_step_checked_end(spd_model_handle m, int32_t *first_failed_step, i
         if (m->wintape.on && m->wintape.validity.valid) m->wintape.validity.fail(i, *failed);
         if (m->projtape.on && m->projtape.validity.valid) m->projtape.validity.fail(i, *failed);
         if (m->tracktape.on && m->tracktape.validity.valid) m->tracktape.validity.fail(i, *failed);
+        if (m->filtape.on && m->filtape.validity.valid) m->filtape.validity.fail(i, *failed);
         if (m->assim.on && m->assim.validity.valid) m->assim.validity.fail(i, *failed);
         if (m->verif.on && m->verif.validity.valid) m->verif.validity.fail(i, *failed);
         if (m->qtape.on && m->qtape.validity.valid) m->qtape.validity.fail(i, *failed);
@@ -1977,6 +2019,7 @@ int spd_model_mark_initialized(spd_model_handle m, int current_step, int year, i
     m->current_step = current_step;
     m->acctape.window_start = -1;  // (the accumulation tape's open window does not continue across a step counter set by hand)
     m->wintape.window_start = -1;  // (... nor does the window tape's)
+    m->filtape.window_start = -1;  // (... nor the filter tape's, and its filters start again)
     m->surf_cache_valid = false;
     m->ablco2_ref = m->air_absortivity_co2;  // set_forcing(imode = 0), forcing.f90:40
     m->initialized = true;
@@ -2019,6 +2062,7 @@ int spd_model_set_control(spd_model_handle m, const spd_model_control *in) {
     m->current_step = in->current_step;
     m->acctape.window_start = -1;
     m->wintape.window_start = -1;
+    m->filtape.window_start = -1;
     m->land_coupling_flag = in->land_coupling_flag ? 1 : 0;
     m->sst_anomaly_flag = in->sst_anomaly_coupling_flag ? 1 : 0;
     m->increase_co2 = in->increase_co2 ? 1 : 0;

@@ -2,7 +2,7 @@
 // the carving of an allocation that every in-loop feature's _configure and _read run around their own work; the front end of a
 // sample that the statistics and four of the tapes share (defined in model.hip).  model.hip holds the model's life, its registry,
 // the step loop and the rest of the C ABI; the host code of each in-loop feature lies behind its kernels in the feature's own file
-// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, tracktape.hip, nudge.hip, breed.hip, assim.hip, verif.hip, qtape.hip, plev.hip,
+// (stats.hip, tape.hip, spectra.hip, enstape.hip, acctape.hip, wintape.hip, projtape.hip, tracktape.hip, filtape.hip, nudge.hip, breed.hip, assim.hip, verif.hip, qtape.hip, plev.hip,
 // derive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +32,7 @@
 #include "wintape.hpp"
 #include "projtape.hpp"
 #include "tracktape.hpp"
+#include "filtape.hpp"
 #include "verif.hpp"
 #include "qtape.hpp"
 #include "ring.hpp"
@@ -360,6 +361,32 @@ struct spd_model {
         TrackTapePlane *planes = nullptr;
         TrackTapeItem *items = nullptr;
     } tracktape;
+    // The filter tape (spd_model_filtape_*): window means, covariances and last values of time-filtered planes of the state's
+    // grid-space fields.  The tape's front end (its own slab and tables) and the filter launch follow every step that samples (the
+    // tape's rule with `sample_every`); the accumulate launch follows a counted sample -- one behind the `spinup` filter samples
+    // since _configure, _reset, spd_model_init or a step counter set by hand -- and a closing step (the window tape's schedule,
+    // filtape_advance), behind the track tape's launch.  One allocation of its own (hipMalloc): ring (per entry [slot][M][4608],
+    // float or double), the sections' state [M][F][S][2][4608], the filtered values [M][F][4608] and the accumulators [M][E][4608]
+    // (fp64), slab, tables, the descriptors of the filtered planes and of the entries (filtape.hpp).  The step the open window
+    // started at, its counted samples, the number of filter samples so far and the rows of the closed windows are host state.
+    struct FilTape : SampleFront {
+        struct Entry {
+            int name, level, filter, op, name_b, level_b;  // names: catalogue ids (name_b -1: none); op: SPD_FIL_*
+        };
+        bool on = false;
+        int window = SPD_WINDOW_STEPS, every = 1, sample_every = 1, spinup = 0, dtype = SPD_TAPE_F32;
+        int nfilters = 0, nplanes = 0, smax = 0;
+        int window_start = -1;          // absolute step counter the open window began at (-1: at the next step that runs, with filter sample 1)
+        int samples = 0;                // counted samples the open window holds
+        long long filter_samples = 0;   // filter samples since the filters last started (k of the definition)
+        SampleRing ring;                // of closed windows; rows [8]: step after the window, year, month, day, hour, minute, counted samples, steps
+        Validity validity;
+        std::vector<Entry> entries;
+        void *alloc = nullptr, *data = nullptr;
+        double *state = nullptr, *y = nullptr, *acc = nullptr;
+        FilTapePlane *planes = nullptr;
+        FilTapeItem *items = nullptr;
+    } filtape;
     // Nudging (spd_model_nudge_*): relaxation of the spectral state toward target fields, the one thing in the device loop that
     // WRITES the state.  In the in-loop mode a launch follows the step_range of every member group on the group's stream, in front
     // of the last step's range check and of every recorder (nudge.hip); spd_model_nudge_apply is the same launch once, on the state

@@ -135,6 +135,9 @@ int spd_model_plev_configure(spd_model_handle m, const double *levels_pa, int n)
     if (m->tracktape.on && m->tracktape.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the track tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_tracktape_configure)");
+    if (m->filtape.on && m->filtape.holds_plev())
+        return m_fail(SPD_E_ARG, std::string(who) + ": the filter tape holds a pressure-level variable; switch it off first "
+                                                    "(spd_model_filtape_off)");
     if (m->verif.on && m->verif.holds_plev())
         return m_fail(SPD_E_ARG, std::string(who) + ": the verification tape holds a pressure-level variable; switch it off first "
                                                     "(spd_model_verif_off)");

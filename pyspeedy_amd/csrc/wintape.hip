@@ -155,8 +155,10 @@ int win_u_id(int id) { return id == kWinWspdGrid ? 0 : kPlevFirst + PLEV_U; }
 const char *const kWinOff = "no window tape configured (spd_model_wintape_configure)";
 const char *const kWinOpNames[kWinNOps] = {"SPD_WIN_SUM", "SPD_WIN_MEAN", "SPD_WIN_MIN", "SPD_WIN_MAX", "SPD_WIN_COUNT_ABOVE", "SPD_WIN_COUNT_BELOW"};
 
-// window kind, `every` and sample_every, as _configure and spd_wintape_plan refuse them
-int win_schedule_check(const char *who, int window, int every, int sample_every) {
+}  // namespace
+
+// window kind, `every` and sample_every, as _configure, spd_wintape_plan and the filter tape refuse them
+int spd::wintape_schedule_check(const char *who, int window, int every, int sample_every) {
     if (window != SPD_WINDOW_STEPS && window != SPD_WINDOW_DAY && window != SPD_WINDOW_MONTH)
         return m_fail(SPD_E_ARG, std::string(who) + ": unknown window kind " + std::to_string(window) +
                                      " (SPD_WINDOW_STEPS, SPD_WINDOW_DAY or SPD_WINDOW_MONTH)");
@@ -166,7 +168,6 @@ int win_schedule_check(const char *who, int window, int every, int sample_every)
     if (sample_every < 1) return m_fail(SPD_E_ARG, std::string(who) + ": sample_every must be at least 1");
     return SPD_OK;
 }
-}  // namespace
 
 WinDecision spd::wintape_advance(const WinSchedule &s, WinOpen &w, int step_after, const Calendar &next, int32_t *row) {
     WinDecision d;
@@ -205,7 +206,7 @@ int spd_wintape_plan(int year, int month, int day, int hour, int minute, int ste
         return m_fail(SPD_E_ARG, std::string(who) + ": bad date");
     if (step0 < 0 || nsteps < 0) return m_fail(SPD_E_ARG, std::string(who) + ": step0 and nsteps must not be negative");
     if (static_cast<long long>(step0) + nsteps > 2147483647LL) return m_fail(SPD_E_ARG, std::string(who) + ": step0 + nsteps does not fit an int");
-    if (int rc = win_schedule_check(who, window, every, sample_every)) return rc;
+    if (int rc = wintape_schedule_check(who, window, every, sample_every)) return rc;
     if (max_rows < 0 || (max_rows > 0 && !rows)) return m_fail(SPD_E_ARG, std::string(who) + ": bad destination");
     Calendar cal;
     cal.set(year, month, day, hour, minute);
@@ -252,7 +253,7 @@ int spd_model_wintape_configure(spd_model_handle m, const char *const *names, co
             if (entries[j].name == entries[k].name && entries[j].op == entries[k].op)
                 return m_fail(SPD_E_ARG, std::string(who) + ": entry ('" + names[k] + "', " + std::to_string(ops[k]) + ") named twice");
     if (n_entries > 0) {
-        if (int rc = win_schedule_check(who, window, every, sample_every)) return rc;
+        if (int rc = wintape_schedule_check(who, window, every, sample_every)) return rc;
         if (capacity < 1) return m_fail(SPD_E_ARG, std::string(who) + ": capacity must be at least 1");
         if (dtype != SPD_TAPE_F32 && dtype != SPD_TAPE_F64) return m_fail(SPD_E_ARG, std::string(who) + ": dtype must be SPD_TAPE_F32 or SPD_TAPE_F64");
     }

@@ -45,6 +45,8 @@ struct WinDecision {
 // The step that leaves the counter at `step_after` and the date at `next`: a sample goes into the open window first; a closing
 // step then fills row[8] (spd_model_wintape_times) and opens the next window at step_after.
 WinDecision wintape_advance(const WinSchedule &s, WinOpen &w, int step_after, const Calendar &next, int32_t *row);
+// window kind, `every` and sample_every as every caller of the schedule refuses them: SPD_OK, or SPD_E_ARG behind the error text
+int wintape_schedule_check(const char *who, int window, int every, int sample_every);
 
 // The step loop's launches for the members [first, first + count) on a step that samples (k >= 1: the front end, then the kernel) or
 // only closes (k = 0: the kernel alone); k, close, n and slot as run_wintape_step (wintape.hip) takes them.

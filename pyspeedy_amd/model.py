@@ -929,6 +929,131 @@ class EnsembleModel:
         lat = lats[j] + np.abs(dj) * (lats[toward] - lats[j])
         return np.where(found, lon, np.nan), np.where(found, lat, np.nan)
 
+    # ---- the filter tape: window means and covariances of time-filtered fields (spd_model_filtape_*, include/pyspeedy_amd.h) --
+    FILTAPE_OPS = {"mean": _lib.SPD_FIL_MEAN, "cov": _lib.SPD_FIL_COV, "last": _lib.SPD_FIL_LAST}
+
+    def _filtape_level(self, name, level):
+        """the 0-based level of an entry: a name on the target levels of plev_configure gives its level in hPa"""
+        if name in self.PLEV_VARIABLES[:5] or name in self.DERIVED_VARIABLES[9:]:
+            levels = self.plev_levels
+            if float(level) not in levels:
+                raise ValueError("%r is not among the configured pressure levels %r (hPa) of %s" % (level, levels, name))
+            return levels.index(float(level))
+        return int(level)
+
+    def filtape_configure(self, filters, entries, window, capacity, sample_every=1, spinup=0, dtype="float32"):
+        """Record window means, covariances and last values of time-filtered fields inside run() / run_checked() calls of any
+        length: the band-passed variance of z_plev at 500 hPa (the storm track), eddy fluxes such as v'T' at 850 hPa, the variance
+        of a low-passed field.  `filters` is a list of 1 ... 8 cascades, each array-like [S][5] (1 <= S <= 4) of second-order
+        sections (b0, b1, b2, a1, a2) as pyspeedy_amd.butterworth_sections returns them, with the sampling interval `sample_every`
+        steps of 40 minutes.  `entries` is a list (at most 64) of (name, level, filter, op) or (name, level, filter, "cov", name_b,
+        level_b): name any of STATS_VARIABLES or DERIVED_VARIABLES, level a 0-based level of the name -- for a name on the target
+        levels of plev_configure the level itself in hPa --, filter an index into `filters`, op "mean" (the window mean of the
+        filtered field), "cov" (the window mean of the product of two filtered fields, the variance of one when no second field is
+        named; a moment about zero: subtract the product of two "mean" entries where the filter passes the mean) or "last" (the
+        filtered field at the window's last counted sample).  A sample is taken after every step that leaves current_step at a
+        multiple of `sample_every` and is what a float64 tape holds; the first `spinup` samples run the filters and are counted
+        in no window.  `window` is a number of steps, "day" or "month" as wintape_configure takes it (wintape_plan tells the
+        windows ahead); the ring in device memory keeps the last `capacity` windows of every member; dtype "float32" (the
+        default) or "float64".  A window without a counted sample holds NaN.  The arithmetic is fixed.  Empties
+        the ring and restarts the filters.  Synchronises the device."""
+        key = str(dtype).replace("torch.", "")
+        if key not in self.TAPE_DTYPES:
+            raise ValueError("dtype must be 'float32' or 'float64', got %r" % (dtype,))
+        if isinstance(window, str):
+            if window not in self.WINTAPE_WINDOWS:
+                raise ValueError("window must be a number of steps, 'day' or 'month', got %r" % (window,))
+            kind, every = self.WINTAPE_WINDOWS[window], 0
+        else:
+            kind, every = _lib.SPD_WINDOW_STEPS, int(window)
+        cascades = [np.ascontiguousarray(f, dtype=np.float64) for f in filters]
+        for f in cascades:
+            if f.ndim != 2 or f.shape[1] != 5:
+                raise ValueError("a filter is [S][5] (b0, b1, b2, a1, a2 per section), got shape %r" % (f.shape,))
+        rows = []
+        for entry in entries:
+            if len(entry) not in (4, 6):
+                raise ValueError("an entry is (name, level, filter, op) or (name, level, filter, op, name_b, level_b), got %r" % (entry,))
+            op = entry[3]
+            if isinstance(op, str):
+                if op not in self.FILTAPE_OPS:
+                    raise ValueError("op must be one of 'mean', 'cov', 'last', got %r" % (op,))
+                op = self.FILTAPE_OPS[op]
+            second = (str(entry[4]), self._filtape_level(str(entry[4]), entry[5])) if len(entry) == 6 else ("", 0)
+            rows.append((str(entry[0]), self._filtape_level(str(entry[0]), entry[1]), int(entry[2]), int(op)) + second)
+        flat = np.concatenate(cascades) if cascades else np.zeros((1, 5))
+        counts = _c_array(C.c_int, (f.shape[0] for f in cascades))
+        names_a, names_b = _c_names(r[0] for r in rows), _c_names(r[4] for r in rows)
+        levels_a, which, ops, levels_b = (_c_array(C.c_int, (r[k] for r in rows)) for k in (1, 2, 3, 5))
+        with torch.cuda.device(self.sp.device):
+            rc = self._lib.spd_model_filtape_configure(self._m, flat.ctypes.data_as(C.POINTER(C.c_double)), counts, len(cascades), names_a,
+                                                       levels_a, which, ops, names_b, levels_b, len(rows), kind, every, int(sample_every),
+                                                       int(spinup), int(capacity), self.TAPE_DTYPES[key][0])
+        if rc != 0:
+            off = lambda: self._lib.spd_model_filtape_info(self._m, *([None] * 12)) != 0  # noqa: E731
+            self._configure_refused("spd_model_filtape_configure", rc, off, "_filtape_entries")
+        self._filtape_entries = tuple(rows)
+
+    def filtape_off(self):
+        """Switch the filter tape off and free it."""
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_filtape_off(self._m), "spd_model_filtape_off")
+        self._filtape_entries = ()
+
+    def filtape_reset(self):
+        """Empty the ring, start a new window at the current step and restart the filters: the next sample starts every section
+        in the steady state of its value (no device work)."""
+        check(self._lib.spd_model_filtape_reset(self._m), "spd_model_filtape_reset")
+
+    @property
+    def filtape_info(self):
+        """dict(taken, held, capacity, window, sample_every, spinup, dtype, filters, planes, entries, filter_samples): windows
+        closed since the last reset, windows the ring holds (min(taken, capacity)), the configuration (window: the number of steps,
+        "day" or "month"; planes: distinct filtered (name, level, filter) planes) and the filter samples taken since the filters
+        last started."""
+        taken, k = C.c_longlong(0), C.c_longlong(0)
+        v = [C.c_int(0) for _ in range(10)]
+        check(self._lib.spd_model_filtape_info(self._m, C.byref(taken), *[C.byref(x) for x in v], C.byref(k)), "spd_model_filtape_info")
+        held, capacity, kind, every, sample_every, spinup, dtype, filters, planes, entries = (x.value for x in v)
+        name = [key for key, val in self.TAPE_DTYPES.items() if val[0] == dtype][0]
+        window = every if kind == _lib.SPD_WINDOW_STEPS else [key for key, val in self.WINTAPE_WINDOWS.items() if val == kind][0]
+        return dict(taken=int(taken.value), held=held, capacity=capacity, window=window, sample_every=sample_every, spinup=spinup,
+                    dtype=name, filters=filters, planes=planes, entries=entries, filter_samples=int(k.value))
+
+    @property
+    def filtape_entries(self):
+        """The configured entries, a tuple of (name, level, filter, op, name_b, level_b) with 0-based levels, op as SPD_FIL_* and
+        name_b "" where there is none, in the order filtape() numbers them (empty: off)."""
+        return getattr(self, "_filtape_entries", ())
+
+    def _filtape_rows(self):
+        return self._ring_rows("spd_model_filtape_times", self.filtape_info["held"], 8)
+
+    def filtape_steps(self):
+        """The model's step counter after the last step of each held window, oldest first (numpy int array)."""
+        return self._row_steps(self._filtape_rows())
+
+    def filtape_times(self):
+        """The date of the state after each held window's last step, oldest first (a list of datetime)."""
+        return self._row_times(self._filtape_rows())
+
+    def filtape_counts(self):
+        """(counted samples, steps) in each held window, oldest first (two numpy int arrays)."""
+        rows = self._filtape_rows()
+        return rows[:, 6].astype(np.int64), rows[:, 7].astype(np.int64)
+
+    def filtape(self, entry, first=0, count=None, t0=0, nt=None):
+        """Members [first, first + count) and windows [t0, t0 + nt) of the held ones (oldest first) of entry number `entry` of
+        filtape_entries: a tensor [count][nt][48][96] on the model's device in the ring's dtype."""
+        first, count = self._range(first, count)
+        info = self.filtape_info
+        t0, nt = _held_span(info, t0, nt)
+        out = torch.empty((count, max(nt, 0), 48, 96), dtype=self.TAPE_DTYPES[info["dtype"]][1], device=self.sp.device)
+        with torch.cuda.device(self.sp.device):
+            check(self._lib.spd_model_filtape_read(self._m, int(entry), first, count, t0, nt, C.c_void_p(out.data_ptr()),
+                                                   out.numel() * out.element_size(), self._stream()), "spd_model_filtape_read(%d)" % int(entry))
+        return out
+
     # ---- nudging: relaxation of the spectral state toward target fields (spd_model_nudge_*, include/pyspeedy_amd.h) ---------
     NUDGE_NAMES = ("vor", "div", "t", "tr", "ps")
 
